@@ -2,7 +2,7 @@
 """bench.py -- Mpaths/s of the MI355X-native GuidedVolPathVSPG hot path on the 1920x1080
 homogeneous-fog scene (BASELINE.json configs[1]).
 
-  python bench.py --gpus N --steps K --warmup W
+  python bench.py --gpus N --steps K --warmup W [--full] [--dump-outputs DIR]
 
 With N > 1 and no torch.distributed environment this process starts its own ranks
 (`python -m torch.distributed.run --nproc-per-node N bench.py ...`) as a CHILD process -- before
@@ -17,10 +17,12 @@ where the buffer updates (1, 2, 4, ... global waves) and the float film tiles at
 RCCL, inside the timed region.  Inputs (scene, film, VSP buffer) are resident in HBM before the
 timed region starts.
 
-The JSON line carries
+A plain run sets up, warms up, times the K steps and prints the JSON line (`value`, `ms_per_step`, ...); its
   roofline     : dominant kernel -- algorithmic bytes per launch (256 B per path
                  segment + 76 B per path [+ 36 B per density query]) / mean launch duration measured
                  with HIP events on the launch stream, against the 8 TB/s HBM peak.
+comes from the timed steps themselves (`traffic`: a committed profile taken on these kernel sources, if any).
+--full adds the legs that take runs of their own:
   cpu_baseline : the CPU oracle (a port of the reference path; the reference itself cannot be
                  built) timed on this box's host cores on a bounded sample.
   relmse       : the metric's second half -- the same waves rendered by the GPU path and by the
@@ -34,6 +36,12 @@ The JSON line carries
   roofline.issue_bound / roofline.traffic : counters of THIS run -- bench.py profiles itself first (three short
                  `rocprofv3 --pmc` child runs of the same workload, before this process touches the GPU): vector
                  instructions per launch, lane utilisation, the issue fraction they price to, HBM bytes per launch.
+
+--dump-outputs DIR writes what the timed steps computed, after the last one, as DIR/<name>.npy (rank 0):
+  film         : float32 (H, W, 4) -- RGB sums and weight sum per pixel, all-reduced over the ranks
+  vsp_buffer   : float32 (H, W)    -- the image-space VSP buffer the post-process steps left
+  counters     : float64 (n,)      -- rank 0's work counters in vspg_get_counters order (paths, segments, ...)
+Past DUMP_BUDGET bytes in all, each per-pixel array keeps a fixed seeded sample of its pixels (row order).
 """
 import argparse
 import ctypes as C
@@ -54,6 +62,7 @@ B_SEGMENT = 256                # 2 x 128 B SoA path state per segm
 B_PATH_FIXED = 32 + 4 + 40     # film RMW + primary-VSP read + ISG sample write
 B_DENSITY_QUERY = 36           # heterogeneous media: 8 voxels x 4 B + 4 B majorant per density query
 RELMSE_EPS = 1e-4              # mean (I_gpu - I_cpu)^2 / (I_cpu^2 + eps)
+DUMP_BUDGET = 64 << 20         # --dump-outputs: bytes in all
 
 
 def csrc_hash():
@@ -199,6 +208,20 @@ def film_image(f):
     return (f[..., :3] / w).astype(np.float64)
 
 
+def dump_outputs(d, arrays):
+    """--dump-outputs: arrays as d/<name>.npy.  Over DUMP_BUDGET in all, every (H, W, ...) array keeps the same fixed seeded
+    sample of its pixels, flattened to (n, ...) in row order; the small arrays are written whole."""
+    import numpy as np
+    os.makedirs(d, exist_ok=True)
+    total = sum(a.nbytes for a in arrays.values())
+    for name, a in arrays.items():
+        if total > DUMP_BUDGET and a.ndim >= 2:
+            flat = a.reshape((a.shape[0] * a.shape[1],) + a.shape[2:])
+            keep = int(flat.shape[0] * (DUMP_BUDGET / total) * 0.99)
+            a = flat[np.sort(np.random.default_rng(0).choice(flat.shape[0], keep, replace=False))]
+        np.save(os.path.join(d, name + ".npy"), np.ascontiguousarray(a))
+
+
 def relmse_leg(pkg, scene, prm, W, H, cpu_film, waves, device, torch):
     """relMSE vs the CPU oracle at equal spp on identical seeds (untimed), plus the relMSE of both
     against a 16x-spp render of an independent seed (the noise floor that separates bias from noise)."""
@@ -275,6 +298,11 @@ def parse_args():
     ap.add_argument("--no-pmc", action="store_true", help="skip the self-profiling child runs (roofline.issue_bound / live traffic)")
     ap.add_argument("--no-fast-arith", action="store_true", help="skip the tolerance-mode leg (fast_arith)")
     ap.add_argument("--no-reference-defaults", action="store_true", help="skip the reference-default-options leg of the default line")
+    ap.add_argument("--full", action="store_true",
+                    help="also the legs beyond the headline figure (self-profiling, generic_instantiation, fast_arith, reference_defaults, "
+                         "cpu_baseline, relmse); each --no-* option above still drops its leg")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps write what they computed (film, VSP buffer, counters) as DIR/<name>.npy")
     ap.add_argument("--pmc-child", action="store_true", help=argparse.SUPPRESS)  # the run rocprofv3 watches: waves only, no output
     return ap.parse_args()
 
@@ -291,8 +319,8 @@ def main():
         raise SystemExit(subprocess.call(cmd, env=env))
 
     # self-profiling (rank 0 of a 1-GPU run): child processes, before anything here has touched the GPU
-    pmc, pmc_note = None, "skipped"
-    if not args.pmc_child and not args.no_pmc and args.gpus == 1 and int(os.environ.get("WORLD_SIZE", "1")) == 1 and args.diag_maxdepth is None:
+    pmc, pmc_note = None, "skipped" if args.full else "skipped (live counters: --full)"
+    if args.full and not args.pmc_child and not args.no_pmc and args.gpus == 1 and int(os.environ.get("WORLD_SIZE", "1")) == 1 and args.diag_maxdepth is None:
         pmc, pmc_note = live_pmc(args)
 
     import torch
@@ -411,7 +439,14 @@ def main():
     segs_rank = cnt["segments"]
     paths_total, segs_total = sh.sum_over_ranks(dist, [paths_rank, segs_rank], world, "cuda")
     kernel_name = r.kernel_name()
-    vsp_trained = r.vsp_buffer(stream)[0].copy() if rank == 0 else None   # (the fast_arith leg loads it: no feedback from film statistics)
+    vsp_trained = None
+    if rank == 0 and (args.full or args.dump_outputs):
+        vsp_trained = r.vsp_buffer(stream)[0].copy()   # (the fast_arith leg loads it: no feedback from film statistics)
+    outputs = None
+    if rank == 0 and args.dump_outputs:
+        import numpy as np
+        outputs = {"film": film.view(H, W, 4).cpu().numpy().copy(), "vsp_buffer": vsp_trained,
+                   "counters": np.array(list(cnt.values()), dtype=np.float64)}
     r.close()
 
     if rank == 0:
@@ -513,7 +548,7 @@ def main():
         if train_ms is not None:
             out["training"] = {"waves": args.train_waves, "ms_per_wave": train_ms,
                                "note": "render with segment recording + PropagateSamples + Field::Update, host-timed, untimed for value"}
-        if args.workload == "fog" and not args.no_generic and world == 1 and not diag:
+        if args.full and args.workload == "fog" and not args.no_generic and world == 1 and not diag:
             # the instantiation a chromatic medium takes: every specialisation off, same scene, same results
             for k in ("VSPG_NO_GREY", "VSPG_NO_GREY_KD", "VSPG_NO_NULLZERO"):
                 os.environ[k] = "1"
@@ -538,7 +573,7 @@ def main():
                                             "kernel_ms": sum(a.elapsed_time(b) for a, b in gev) / 16, "kernel": g.kernel_name(),
                                             "note": "same scene through the instantiation a chromatic medium / coloured walls take"}
             g.close()
-        if args.workload in ("fog", "cloud", "cloud-scene") and not args.no_fast_arith and world == 1 and not diag:
+        if args.full and args.workload in ("fog", "cloud", "cloud-scene") and not args.no_fast_arith and world == 1 and not diag:
             # the tolerance-mode instantiations (csrc/vspg_arith.h): the same waves through vspg_renderer_set_arithmetic.  Untimed for
             # `value` (that stays the bit-exact kernel).  relMSE against the EXACT film at equal spp with the same loaded VSP buffer (what
             # each mode promises is in tests/test_fast_arith.py); flipped paths: replayed (pixel, sample) pairs whose radiance leaves
@@ -585,7 +620,7 @@ def main():
                           "at 2.5 ulp + native log / sin / cos (equal in distribution only: the reference seeds shadow-ray RNGs from position bits, :1193). "
                           "%d spp, VSP buffer loaded (no feedback); kernel_ms = HIP-event time of vspg_render_wave (the whole pipeline pass for the cloud workloads)" % (2 + n_meas))
             out["fast_arith"] = fa
-        if args.workload == "fog" and not args.no_reference_defaults and world == 1 and not diag:
+        if args.full and args.workload == "fog" and not args.no_reference_defaults and world == 1 and not diag:
             # the configuration a `guidedvolpathvspg` user gets by default (:1263-1319): directional guiding + secondary-ray VSP,
             # i.e. the cache query in the loop.  The field trains in-loop for the first waves, like the reference's first 128.
             dprm = pkg.default_params()
@@ -628,13 +663,15 @@ def main():
                 "mean_segments_per_path": gcnt["segments"] / max(1, gcnt["paths"]),
                 "note": "same scene, the reference's default options (surface RIS + volume MIS guiding, primary + secondary VSP): untimed for `value`"}
             g.close()
-        if not args.no_cpu_baseline and world == 1:
+        if args.full and not args.no_cpu_baseline and world == 1:
             # the relMSE leg needs the same waves on both sides: at least 4 spp (training waves would make the oracle
             # side minutes long for fog-guided: that workload reports cpu_baseline on its untrained first waves only)
             rec, cpu_film, waves = cpu_baseline(pkg, scene, prm if not guided else pkg.app_f_params(), W, H)
             out["cpu_baseline"] = rec
             if not guided:
                 out["relmse"] = relmse_leg(pkg, scene, prm, W, H, cpu_film, waves, local_rank, torch)
+        if outputs is not None:
+            dump_outputs(args.dump_outputs, outputs)
         print(json.dumps(out))
         sys.stdout.flush()
     if world > 1:
