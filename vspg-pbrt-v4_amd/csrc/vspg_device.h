@@ -619,6 +619,24 @@ struct DScene {
     // outside the medium (0: the medium fills the scene -- every boundary branch below is skipped, wave-uniformly);
     // camera_in_medium = the camera ray's medium (1 = the scene's medium)
     int32_t n_spheres, has_boundaries, camera_in_medium, pad_b;
+    // The fields the path loops read (camera, medium, integrator parameters, render config) come first, inside the first 4 KB
+    // of the record.  The compiler judges a scene address by the global-memory immediate offset (13 bits signed) even where it
+    // emits a scalar load: a field beyond 4 KB got its own 64-bit base address, formed before the persistent loop and held in an
+    // SGPR pair through it (eleven such pairs in k_render_wave_wg3, most of them spilled).  Below 4 KB the offset folds into the
+    // load and only the record's base stays live.
+    VspgCamera cam;
+    // medium
+    int32_t medium_type;
+    float sigma_a[3], sigma_s[3], Le[3], g;
+    // homogeneous medium: sigma_s + sigma_a and (sigma_t - sigma_a) - sigma_s, formed on the host with the
+    // same IEEE float operations the kernels would use.  They are wave-uniform; the vector ALU is the
+    // only float adder on this chip, so computing them in the kernel parks the results in VGPRs for
+    // the whole persistent loop -- as scalar loads they stay in SGPRs.
+    float sigma_t[3], sigma_n_raw[3];
+    // integrator parameters
+    VspgIntegratorParams prm;
+    // render config
+    int32_t xres, yres, seed, shard_index, shard_count;
     DSphere spheres[VSPG_MAX_SPHERES];
     const DTri *tris;          // in BVH leaf order
     const DBvh4Node *bvh;
@@ -631,15 +649,6 @@ struct DScene {
     IsectRec irec[VSPG_MAX_QUADS];
     int32_t light_quads[VSPG_MAX_QUADS];
     DQuad quads[VSPG_MAX_QUADS];
-    VspgCamera cam;
-    // medium
-    int32_t medium_type;
-    float sigma_a[3], sigma_s[3], Le[3], g;
-    // homogeneous medium: sigma_s + sigma_a and (sigma_t - sigma_a) - sigma_s, formed on the host with the
-    // same IEEE float operations the kernels would use.  They are wave-uniform; the vector ALU is the
-    // only float adder on this chip, so computing them in the kernel parks the results in VGPRs for
-    // the whole persistent loop -- as scalar loads they stay in SGPRs.
-    float sigma_t[3], sigma_n_raw[3];
     // grid medium (GridMedium, media.h:284-390): density samples nx*ny*nz (x fastest) and the 16^3
     // majorant grid (media.cpp:252-269), both in HBM
     int32_t nx, ny, nz;
@@ -669,10 +678,6 @@ struct DScene {
     // layout (only the delta-tracking callback's emission reads it: eight plain loads, no bricks), null = none
     const float *temperature;
     float temperature_offset, temperature_scale, nvdb_le_scale;
-    // integrator parameters
-    VspgIntegratorParams prm;
-    // render config
-    int32_t xres, yres, seed, shard_index, shard_count;
     // TrBuffer (cpu/trbuffer.h): running mean of the primary rays' ratio-tracking transmittance, RGB per pixel;
     // tr_calc = calculateTrBuffer (the resampling routine records), tr_load = trBufferLoad (NDS+ reads)
     float *tr_rgb;

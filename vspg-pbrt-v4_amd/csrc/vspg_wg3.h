@@ -59,6 +59,22 @@ __device__ __forceinline__ void resolve_sample(float4 s, float4 *film_px, float 
     isg.vsp_used = __builtin_fabsf(s.w);
     isg_add_sample_rmw(isg_px, L, isg);
 }
+// An opaque copy of a kernel argument at its point of use.  A wave-uniform flag tested inside the persistent loop is otherwise
+// turned into a 64-bit lane mask once, before the loop, and held there (one pair per test: `single_sample` took two); with more live
+// values than SGPRs those pairs are spilled to VGPR lanes and read back at every use.  The opaque copy keeps the 32-bit argument
+// live instead and forms the mask where it is used.  Integers and pointers only: no float passes through it.
+template <class T>
+__device__ __forceinline__ T w3_at_use(T v) {
+    asm volatile("" : "+s"(v));
+    return v;
+}
+// The lane index, opaque in the same way: a compare of it (`lane == 0`, `lane < Q_COUNT`) is a lane mask, an SGPR pair, which the
+// compiler would otherwise form once before the persistent loop and hold for the whole kernel.
+__device__ __forceinline__ int w3_lane() {
+    int l = (int)(threadIdx.x & 63u);
+    asm volatile("" : "+v"(l));
+    return l;
+}
 constexpr int kWg3Heads = 8, kWg3HeadSetBytes = kWg3Heads * 128;  // k_render_wave_wg3's tile cursors (see the kernel)
 // The global work head is a PAIR of counters used by alternate launches: a launch zeroes the one the NEXT launch will use
 // (nobody reads it meanwhile, launches of a renderer are stream-ordered), so no memset sits between two waves.
@@ -75,7 +91,7 @@ typedef const volatile __attribute__((address_space(3))) w3_u32x4 *w3_lds_v4;
 // returning LDS atomic (lane q reserves for queue q), then the entries, then the four commits as one atomic.
 template <int NP>
 VDEV void ring_push_all(int dq, unsigned entry, unsigned short (*ring)[NP], unsigned int *s_w) {
-    const int lane = threadIdx.x & 63;
+    const int lane = w3_lane();
     const unsigned long long m0 = __ballot(dq == 0), m1 = __ballot(dq == 1), m2 = __ballot(dq == 2), m3 = __ballot(dq == 3);
     const unsigned n0 = (unsigned)__popcll(m0), n1 = (unsigned)__popcll(m1), n2 = (unsigned)__popcll(m2), n3 = (unsigned)__popcll(m3);
     const unsigned myn = lane == 0 ? n0 : lane == 1 ? n1 : lane == 2 ? n2 : n3;
@@ -118,6 +134,9 @@ __global__ __launch_bounds__(kWgBlock, kWgWavesPerSimd) void k_render_wave_wg3(
     int vsp_ready, int wave_end, int first_sample, int single_sample, PcgJump jump, unsigned int tiles_magic,
     unsigned int *__restrict__ work_head, const float4 *__restrict__ prev_samples,
     float4 *__restrict__ wave_samples, unsigned long long *__restrict__ counters, TrainArgs train = TrainArgs{nullptr, nullptr, nullptr, nullptr, 0, 0}) {
+    // (each argument its own register from here on: the four ints arrive as one 128-bit load, and a tuple is spilled as a unit)
+    vsp_ready = w3_at_use(vsp_ready), wave_end = w3_at_use(wave_end), first_sample = w3_at_use(first_sample);
+    single_sample = w3_at_use(single_sample);
     const DScene &S = *Sp;
     const int W = S.xres, H = S.yres;
     const int tilesX = (W + 7) >> 3, tilesY = (H + 7) >> 3;
@@ -189,7 +208,7 @@ __global__ __launch_bounds__(kWgBlock, kWgWavesPerSimd) void k_render_wave_wg3(
     auto emit = [&](int pxy, Spec Lraw, const IsgSample &isg) {
         const Spec L = finish_radiance(Lraw);
         const size_t pidx = (size_t)((unsigned)pxy >> 16) * W + (pxy & 0xffff);
-        if (single_sample) {
+        if (w3_at_use(single_sample)) {
             wave_samples[pidx] = make_float4(L.r, L.g, L.b, isg_code(isg));
         } else {
             film_add_sample(film + pidx, L);
@@ -225,10 +244,10 @@ __global__ __launch_bounds__(kWgBlock, kWgWavesPerSimd) void k_render_wave_wg3(
             const int aVV = avail(wVV, hVV), aVS = avail(wVS, hVS), aA = avail(wA, hA), aF = exh ? 0 : avail(wF, hF);
             const auto claim = [&](unsigned q, unsigned head, unsigned n) {  // compare-and-swap on the queue's head: this wavefront owns [head, head + n)
                 unsigned old = head + 1u;
-                if (lane == 0) old = atomicCAS(s_w + q * QC_STRIDE + QC_HEAD, head, head + n);
+                if (w3_lane() == 0) old = atomicCAS(s_w + q * QC_STRIDE + QC_HEAD, head, head + n);
                 return U(old) == head;
             };
-            const auto bump = [&](int w, int d) { if (lane == 0) atomicAdd(s_w + w, (unsigned)d); };
+            const auto bump = [&](int w, int d) { if (w3_lane() == 0) atomicAdd(s_w + w, (unsigned)d); };
             const auto claim_vertex = [&](int a_first, unsigned h_first, unsigned q_first, int a_second, unsigned h_second, unsigned q_second) {
                 // the larger queue first; a chunk it cannot fill takes the rest from the other one
                 bump(W3_BUSY_V, 1);
@@ -259,7 +278,7 @@ __global__ __launch_bounds__(kWgBlock, kWgWavesPerSimd) void k_render_wave_wg3(
                     tile = n_tiles;
                     while (wtried < (unsigned)kWg3Heads) {
                         unsigned c = 0xffffffffu;
-                        if (lane == 0 && __hip_atomic_load(work_head + wseg * 32u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) * (unsigned)kWg3Heads + wseg < n_tiles)
+                        if (w3_lane() == 0 && __hip_atomic_load(work_head + wseg * 32u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) * (unsigned)kWg3Heads + wseg < n_tiles)
                             c = atomicAdd(work_head + wseg * 32u, 1u);
                         c = U(c);
                         if (c != 0xffffffffu && c * (unsigned)kWg3Heads + wseg < n_tiles) {
@@ -333,13 +352,13 @@ __global__ __launch_bounds__(kWgBlock, kWgWavesPerSimd) void k_render_wave_wg3(
                     pc.path();
                     const int s2 = P.i(LY::SAMPLE, slot) + sample_step;
                     P.i(LY::SAMPLE, slot) = s2;
-                    restart = !single_sample && s2 < wave_end;
+                    restart = !w3_at_use(single_sample) && s2 < wave_end;
                     freed = !restart;
                 }
             }
             ring_push_all<NP>(cont || restart ? Q_A : (freed ? Q_F : -1), (unsigned)slot | (restart ? kRestartBit : 0u), s_ring, s_w);
             const unsigned n_freed = (unsigned)__popcll(__ballot(freed));
-            if (lane == 0) {
+            if (w3_lane() == 0) {
                 if (n_freed) atomicSub(s_w + W3_LIVE, n_freed);
                 atomicSub(s_w + W3_BUSY_V, 1u);
             }
@@ -370,7 +389,7 @@ __global__ __launch_bounds__(kWgBlock, kWgWavesPerSimd) void k_render_wave_wg3(
                 if (primary) {
                     int px, py, smp;
                     if (fresh) {
-                        unsigned ty = tilesX == 1 ? tile : __umulhi(tile, tiles_magic);
+                        unsigned ty = w3_at_use(tilesX) == 1 ? tile : __umulhi(tile, tiles_magic);
                         unsigned tx = tile - ty * (unsigned)tilesX;
                         while (tx >= (unsigned)tilesX) { tx -= (unsigned)tilesX; ty++; }
                         px = (int)(tx * 8u + ((unsigned)lane & 7u));
@@ -379,7 +398,7 @@ __global__ __launch_bounds__(kWgBlock, kWgWavesPerSimd) void k_render_wave_wg3(
                         smp = first_sample;
                         // the PREVIOUS one-sample launch parked this pixel's sample (vspg_render_wave: deferred resolve): it enters
                         // the film now, before this launch's sample of the pixel can (same order of additions as ever)
-                        if (prev_samples != nullptr && px < W && py < H) {
+                        if (w3_at_use(prev_samples) != nullptr && px < W && py < H) {
                             const size_t pidx = (size_t)py * W + px;
                             resolve_sample(prev_samples[pidx], film + pidx, isg_stats + pidx * VSPG_ISG_STATS);
                         }
@@ -391,14 +410,14 @@ __global__ __launch_bounds__(kWgBlock, kWgWavesPerSimd) void k_render_wave_wg3(
                     }
                     valid = px < W && py < H && smp < wave_end;  // tile padding: the slot stays free
                     if (valid) {
-                        if (single_sample)
-                            start_path(S, vsp_buf, vsp_ready, px, py, jump, sampler, st, &ch, isg);
+                        if (w3_at_use(single_sample))
+                            start_path(S, vsp_buf, w3_at_use(vsp_ready), px, py, jump, sampler, st, &ch, isg);
                         else
-                            start_path(S, vsp_buf, vsp_ready, px, py, smp, sampler, st, &ch, isg);
+                            start_path(S, vsp_buf, w3_at_use(vsp_ready), px, py, smp, sampler, st, &ch, isg);
                         P.i(LY::PIXEL, slot) = pxy;
                         P.i(LY::SAMPLE, slot) = smp;
                         if constexpr (TRAIN) { (void)rec_bind(pxy); pc.rec.reset(); }
-                        seg = li_segment_a<Medium, GUIDED, SEG_PRIMARY>(S, medium, vsp_buf, vsp_ready, px, py, st, ch, sampler,
+                        seg = li_segment_a<Medium, GUIDED, SEG_PRIMARY>(S, medium, vsp_buf, w3_at_use(vsp_ready), px, py, st, ch, sampler,
                                                                         isg, pc, vx);
                         alive = seg != LI_END;
                         if (alive) {
@@ -415,7 +434,7 @@ __global__ __launch_bounds__(kWgBlock, kWgWavesPerSimd) void k_render_wave_wg3(
                     const int px = pxy & 0xffff, py = (int)((unsigned)pxy >> 16);
                     if constexpr (TRAIN) { (void)rec_bind(pxy); pool_load_rec<LY>(P, slot, pc.rec); }
                     // (full scenes: a path that crossed a medium boundary on its camera segment is still at depth 0 here)
-                    seg = li_segment_a<Medium, GUIDED, FULL ? SEG_ANY : SEG_SECONDARY>(S, medium, vsp_buf, vsp_ready, px, py, st, ch, sampler,
+                    seg = li_segment_a<Medium, GUIDED, FULL ? SEG_ANY : SEG_SECONDARY>(S, medium, vsp_buf, w3_at_use(vsp_ready), px, py, st, ch, sampler,
                                                                                       isg, pc, vx);
                     alive = seg != LI_END;
                     if (seg == LI_SKIP) {
@@ -436,13 +455,13 @@ __global__ __launch_bounds__(kWgBlock, kWgWavesPerSimd) void k_render_wave_wg3(
                     pc.path();
                     const int s2 = P.i(LY::SAMPLE, slot) + sample_step;
                     P.i(LY::SAMPLE, slot) = s2;
-                    restart = !single_sample && s2 < wave_end;
+                    restart = !w3_at_use(single_sample) && s2 < wave_end;
                     freed = !restart;
                 }
             }
             ring_push_all<NP>(toVV ? Q_VV : toVS ? Q_VS : (toA || restart) ? Q_A : (freed ? Q_F : -1), (unsigned)slot | (restart ? kRestartBit : 0u), s_ring, s_w);
             const unsigned n_freed = (unsigned)__popcll(__ballot(freed));
-            if (lane == 0) {
+            if (w3_lane() == 0) {
                 if (fresh && !tile_ok) atomicExch(s_w + W3_EXH, 1u);
                 if (n_freed) atomicSub(s_w + W3_LIVE, n_freed);
                 atomicSub(s_w + W3_BUSY_S, 1u);
