@@ -24,6 +24,7 @@
 #ifdef VSPG_SINGLE_TU  // diagnostic builds that read device-side globals of the pipeline kernels (VSPG_WF_STATS, VSPG_PROFILE, VSPG_WF_DEBUG)
 #include "vspg_wf_grid.hip"
 #include "vspg_wf_nvdb.hip"
+#include "vspg_wg3_exact.hip"
 #endif
 
 using namespace vspg;
@@ -3417,7 +3418,7 @@ int vspg_render_wave(VspgRenderer *r, int wave_start, int wave_end, void *stream
                     const Wg3Launch L3{r->dscene, r->film, r->isg_stats, r->vsp, r->vsp_ready, wave_end, first, single, jump, tiles_magic, head8, ws_prev, ws_out,
                                        r->counters, (unsigned)wblocks, (hipStream_t)stream, r->medium_grey ? (r->surfaces_grey ? 2 : 1) : 0,
                                        r->medium_grey && r->surfaces_grey && r->null_zero ? 1 : 0};
-                    const int lrc = r->arith == VSPG_ARITH_FAST_WEIGHTS ? vspg_arith1_wg3(&L3) : r->arith == VSPG_ARITH_FAST ? vspg_arith2_wg3(&L3) : wg3_launch_unguided(L3);
+                    const int lrc = r->arith == VSPG_ARITH_FAST_WEIGHTS ? vspg_arith1_wg3(&L3) : r->arith == VSPG_ARITH_FAST ? vspg_arith2_wg3(&L3) : wg3_launch_exact(L3);
                     if (lrc != 0) return fail(VSPG_EHIP, std::string("k_render_wave_wg3: ") + hipGetErrorName((hipError_t)lrc));
                 }
             } else

@@ -509,9 +509,18 @@ VDEV P3i p3i_from_err(V3 p, V3 e) {
     interval_ve(p.z, e.z, &r.lo.z, &r.hi.z);
     return r;
 }
+// off > 0 ? next_float_up(po) : (off < 0 ? next_float_down(po) : po), bit for bit for every input (NaNs included), as ONE step
+// on the bit pattern instead of both neighbours and two selects: the step goes away from zero when po and off have the same sign
+// and toward it otherwise; a zero of either sign becomes the smallest denormal of off's sign, an infinity in off's direction stays.
+// (tests/test_offset_axis_bits.py checks the identity on the host.)
 VDEV float offset_axis(float po, float off) {
-    float up = next_float_up(po), dn = next_float_down(po);
-    return off > 0 ? up : (off < 0 ? dn : po);
+    const uint32_t ui = f2b(po), os = f2b(off) & 0x80000000u;
+    uint32_t r = ui + ((uint32_t)((int32_t)(ui ^ os) >> 31) | 1u);
+    r = (ui << 1) == 0u ? (os | 1u) : r;
+    // po stays where off is +-0 or NaN (neither off > 0 nor off < 0) and where it is the infinity off points to; one select on the
+    // bits (a float select here was turned into a branch around the step)
+    const bool keep = !__builtin_islessgreater(off, 0.f) || (ui ^ os) == 0x7f800000u;
+    return b2f(keep ? ui : r);
 }
 VDEV V3 offset_ray_origin(P3i pi, V3 n, V3 w) {
     float d = dot(vabs(n), pi.err());

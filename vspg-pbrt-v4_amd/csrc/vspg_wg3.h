@@ -504,6 +504,9 @@ struct Wg3Launch {
     int null_zero;     // ... whose null-collision coefficient is exactly 0
 };
 template <int GREY> constexpr int kWg3PoolHomogT = wg3_pool_paths<PoolLayout<false, GREY>>(VSPG_WG3_OTHER);
+// (a template: a plain inline host function that names kernels instantiates them in every translation unit that includes this
+// header, even where nothing calls it -- the exact ones belong to vspg_wg3_exact.hip alone)
+template <int = 0>
 inline int wg3_launch_unguided(const Wg3Launch &L) {
 #define VSPG_WG3_GO(M, NPOOL)                                                                                                                \
     hipLaunchKernelGGL((k_render_wave_wg3<M, false, NPOOL, VSPG_WG_BLOCK, VSPG_WG_WAVES, false>), dim3(L.blocks), dim3(VSPG_WG_BLOCK), 0, L.stream, \
@@ -516,5 +519,7 @@ inline int wg3_launch_unguided(const Wg3Launch &L) {
 #undef VSPG_WG3_GO
     return (int)hipGetLastError();
 }
+// the exact-arithmetic instantiations, compiled in vspg_wg3_exact.hip (flags of their own, csrc/Makefile)
+int wg3_launch_exact(const Wg3Launch &L);
 
 VSPG_NS_END  // namespace vspg
