@@ -353,6 +353,19 @@ int vspg_renderer_set_guiding_field(VspgRenderer *r, const VspgField *surface_fi
  * within the iteration cap returns VSPG_ESCOPE after the samples of the paths that did finish have entered the film. */
 int vspg_render_wave(VspgRenderer *r, int wave_start, int wave_end, void *stream);
 
+/* The same over a pixel window: the film's Bounds2i pixelBounds (the "cropwindow" / "pixelbounds" of src/pbrt/film.cpp:97-172), which
+ * is all the render loop covers (`film.PixelBounds()`, src/pbrt/cpu/integrators.cpp:111,183).  [x0, x1) x [y0, y1) in absolute film
+ * pixels; the library is strict -- 0 <= x0 < x1 <= xres and the same in y, else VSPG_EINVAL (clamping to the frame and the
+ * degenerate-bounds error are the host adapter's job, as they are Film's).  The launch runs EvaluatePixelSample -> Li -> film.AddSample
+ * for the window's pixels and this shard's sample indices of [wave_start, wave_end), and touches nothing that belongs to a pixel
+ * outside the window: film, image-space statistics, TrBuffer, training records and counters.  Every per-pixel buffer keeps its
+ * xres * yres size and absolute indexing (a renderer may be given several windows in its lifetime), and vspg_post_process_wave /
+ * _step stay whole-image.  Pixel samples are independent, so disjoint windows that tile the frame give the film, statistics and
+ * counters of one full-frame launch bit for bit.  Streams, parked one-sample results, shards, the boundary pipeline's host
+ * synchronisation and the VSPG_ESCOPE cases are vspg_render_wave's; the kernel is the one vspg_renderer_kernel_name reports, in
+ * every arithmetic mode.  vspg_render_wave(r, a, b, s) == vspg_render_window(r, 0, 0, xres, yres, a, b, s). */
+int vspg_render_window(VspgRenderer *r, int x0, int y0, int x1, int y1, int wave_start, int wave_end, void *stream);
+
 /* Replaces GuidedVolPathVSPGIntegrator::PostProcessWave
  * (guidedvolpathvspgintegrator.cpp:230-260): waveCounter++, image-space VSP buffer update
  * when waveCounter == 2^bufferWave.  Asynchronous on `stream`. */

@@ -185,6 +185,7 @@ SYMBOLS = [
     ("vspg_renderer_create", C.c_int, [_P(VspgScene), _P(VspgIntegratorParams), _P(VspgRenderConfig), _P(_vp)]),
     ("vspg_renderer_destroy", C.c_int, [_vp]),
     ("vspg_render_wave", C.c_int, [_vp, C.c_int, C.c_int, _vp]),
+    ("vspg_render_window", C.c_int, [_vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _vp]),
     ("vspg_post_process_wave", C.c_int, [_vp, _vp]),
     ("vspg_isg_update_due", C.c_int, [_vp, C.c_int]),
     ("vspg_post_process_step", C.c_int, [_vp, C.c_int, _vp, _vp]),
@@ -474,6 +475,11 @@ class Renderer:
 
     def render_wave(self, w0, w1, stream=None):
         _check(self.lib, self.lib.vspg_render_wave(self.h, w0, w1, _vp(stream or 0)))
+
+    def render_window(self, x0, y0, x1, y1, w0, w1, stream=None):
+        """Sample indices [w0, w1) of the pixel window [x0, x1) x [y0, y1) (absolute film pixels, inside the frame) and of nothing
+        else: every buffer keeps its full size.  render_wave(w0, w1) == render_window(0, 0, xres, yres, w0, w1)."""
+        _check(self.lib, self.lib.vspg_render_window(self.h, int(x0), int(y0), int(x1), int(y1), w0, w1, _vp(stream or 0)))
 
     def isg_update_due(self, n_waves=1):
         return bool(self.lib.vspg_isg_update_due(self.h, int(n_waves)))

@@ -79,13 +79,16 @@ __global__ __launch_bounds__(kBlock, kWavesPerSimd) void k_render_wave(const DSc
                                                         int first_sample, int single_sample, PcgJump jump,
                                                         unsigned static_per_wave, unsigned dyn_base,
                                                         unsigned int *__restrict__ work_head,
-                                                        unsigned long long *__restrict__ counters, TrainArgs train) {
+                                                        unsigned long long *__restrict__ counters, TrainArgs train,
+                                                        PixelWindow win) {
+    // win: the pixels the launch covers (vspg_render_window; the whole frame for vspg_render_wave) -- items count over the 8x8 tiles
+    // of the frame's grid that touch it, pixels outside it are masked like tile padding
     // first_sample: first sample index of this shard in [wave_start, wave_end); single_sample: the
     // launch covers exactly one sample per pixel (the reference's 1-spp waves) and `jump` is the
     // PCG skip-ahead for first_sample*65536
     const DScene &S = *Sp;
-    const int W = S.xres, H = S.yres;
-    const int tilesX = (W + 7) >> 3, tilesY = (H + 7) >> 3;
+    const int W = S.xres;
+    const int tilesX = win_tiles_x(win), tilesY = win_tiles_y(win);
     const unsigned total_items = (unsigned)(tilesX * tilesY) * 64u;
     const int lane = threadIdx.x & 63;
     reset_sibling_head(work_head);
@@ -158,10 +161,10 @@ __global__ __launch_bounds__(kBlock, kWavesPerSimd) void k_render_wave(const DSc
                 VSPG_PROF(PS_START);
                 const unsigned item = local_next + rank;
                 const unsigned tile = item >> 6, l = item & 63u;
-                px = (int)(tile % (unsigned)tilesX) * 8 + (int)(l & 7u);
-                py = (int)(tile / (unsigned)tilesX) * 8 + (int)(l >> 3);
+                px = (win_tile_x0(win) + (int)(tile % (unsigned)tilesX)) * 8 + (int)(l & 7u);
+                py = (win_tile_y0(win) + (int)(tile / (unsigned)tilesX)) * 8 + (int)(l >> 3);
                 s = first_sample;
-                if (px < W && py < H && s < wave_end) {
+                if (win_has(win, px, py) && s < wave_end) {
                     if (single_sample)
                         start_path(S, vsp_buf, vsp_ready, px, py, jump, sampler, st, &ch, isg);
                     else
@@ -720,12 +723,13 @@ template <class Medium, bool GUIDED, int NP, int kWgBlock, int kWgWavesPerSimd>
 __global__ __launch_bounds__(kWgBlock, kWgWavesPerSimd) void k_render_wave_wg(
     const DScene *__restrict__ Sp, float4 *__restrict__ film, float *__restrict__ isg_stats, const float *__restrict__ vsp_buf,
     int vsp_ready, int wave_end, int first_sample, int single_sample, PcgJump jump, unsigned int tiles_magic,
-    unsigned int *__restrict__ work_head, unsigned long long *__restrict__ counters) {
+    unsigned int *__restrict__ work_head, unsigned long long *__restrict__ counters, PixelWindow win) {
+    // win: the pixels the launch covers (see k_render_wave); tilesX / tilesY are the window's tile rectangle
     // tiles_magic = ceil(2^32 / tilesX): the one integer division of the kernel (tile index -> tile row, once
     // per claimed chunk) is a multiply-high by it plus a fix-up; pixels travel as packed (x | y << 16)
     const DScene &S = *Sp;
-    const int W = S.xres, H = S.yres;
-    const int tilesX = (W + 7) >> 3, tilesY = (H + 7) >> 3;
+    const int W = S.xres;
+    const int tilesX = win_tiles_x(win), tilesY = win_tiles_y(win);
     const unsigned total_items = (unsigned)(tilesX * tilesY) * 64u;
     const int lane = threadIdx.x & 63;
     const int sample_step = S.shard_count > 1 ? S.shard_count : 1;
@@ -819,7 +823,7 @@ __global__ __launch_bounds__(kWgBlock, kWgWavesPerSimd) void k_render_wave_wg(
                     const unsigned it = (rnext & 63u) + j;
                     unsigned tx = rtx + (it >> 6), ty = rty;
                     while (tx >= (unsigned)tilesX) { tx -= (unsigned)tilesX; ty++; }
-                    s_item[filled + j] = (tx * 8u + (it & 7u)) | ((ty * 8u + ((it >> 3) & 7u)) << 16);
+                    s_item[filled + j] = ((tx + (unsigned)win_tile_x0(win)) * 8u + (it & 7u)) | (((ty + (unsigned)win_tile_y0(win)) * 8u + ((it >> 3) & 7u)) << 16);
                 }
                 rtx += ((rnext & 63u) + n) >> 6;
                 while (rtx >= (unsigned)tilesX) { rtx -= (unsigned)tilesX; rty++; }
@@ -925,7 +929,7 @@ __global__ __launch_bounds__(kWgBlock, kWgWavesPerSimd) void k_render_wave_wg(
                     }
                     px = pxy & 0xffff;
                     py = (int)((unsigned)pxy >> 16);
-                    valid = px < W && py < H && smp < wave_end;  // tile padding: the slot stays free
+                    valid = win_has(win, px, py) && smp < wave_end;  // tile padding: the slot stays free
                     if (valid) {
                         if (single_sample)
                             start_path(S, vsp_buf, vsp_ready, px, py, jump, sampler, st, &ch, isg);
@@ -1067,10 +1071,11 @@ __global__ __launch_bounds__(kWgBlock, kWgWavesPerSimd) void k_render_wave_wg2(
     const DScene *__restrict__ Sp, float4 *__restrict__ film, float *__restrict__ isg_stats, const float *__restrict__ vsp_buf,
     int vsp_ready, int wave_end, int first_sample, int single_sample, PcgJump jump, unsigned int tiles_magic,
     unsigned int static_tiles, unsigned int *__restrict__ work_head, const float4 *__restrict__ prev_samples,
-    float4 *__restrict__ wave_samples, unsigned long long *__restrict__ counters, TrainArgs train = TrainArgs{nullptr, nullptr, nullptr, nullptr, 0, 0}) {
+    float4 *__restrict__ wave_samples, unsigned long long *__restrict__ counters, TrainArgs train, PixelWindow win) {
+    // win: the pixels the launch covers (see k_render_wave); tiles, static shares and training columns count inside its tile rectangle
     const DScene &S = *Sp;
-    const int W = S.xres, H = S.yres;
-    const int tilesX = (W + 7) >> 3, tilesY = (H + 7) >> 3;
+    const int W = S.xres;
+    const int tilesX = win_tiles_x(win), tilesY = win_tiles_y(win);
     const unsigned n_tiles = (unsigned)(tilesX * tilesY);
     const int lane = threadIdx.x & 63;
     const int sample_step = S.shard_count > 1 ? S.shard_count : 1;
@@ -1122,7 +1127,7 @@ __global__ __launch_bounds__(kWgBlock, kWgWavesPerSimd) void k_render_wave_wg2(
     const auto rec_bind = [&](int pxy) {
         if constexpr (TRAIN) {
             const unsigned px = (unsigned)pxy & 0xffffu, py = (unsigned)pxy >> 16;
-            const unsigned item = ((py >> 3) * (unsigned)tilesX + (px >> 3)) * 64u + ((py & 7u) << 3) + (px & 7u);
+            const unsigned item = (((py >> 3) - (unsigned)win_tile_y0(win)) * (unsigned)tilesX + ((px >> 3) - (unsigned)win_tile_x0(win))) * 64u + ((py & 7u) << 3) + (px & 7u);
             pc.rec.base = train.segbuf + item;
             pc.rec.stride = (int)train.n_items;
             pc.rec.max_seg = train_rec_capacity(S.prm.maxdepth);
@@ -1217,14 +1222,14 @@ __global__ __launch_bounds__(kWgBlock, kWgWavesPerSimd) void k_render_wave_wg2(
                         unsigned ty = tilesX == 1 ? tile : __umulhi(tile, tiles_magic);
                         unsigned tx = tile - ty * (unsigned)tilesX;
                         while (tx >= (unsigned)tilesX) { tx -= (unsigned)tilesX; ty++; }
-                        px = (int)(tx * 8u + (l & 7u));
-                        py = (int)(ty * 8u + (l >> 3));
+                        px = (int)((tx + (unsigned)win_tile_x0(win)) * 8u + (l & 7u));
+                        py = (int)((ty + (unsigned)win_tile_y0(win)) * 8u + (l >> 3));
                         pxy = px | (py << 16);
                         smp = first_sample;
                         valid = tile < (left > 0u ? n_static : n_tiles);
                         // the PREVIOUS one-sample launch parked this pixel's sample (vspg_render_wave: deferred resolve): it enters
                         // the film now, before this launch's sample of the pixel can (same order of additions as ever)
-                        if (prev_samples != nullptr && valid && px < W && py < H) {
+                        if (prev_samples != nullptr && valid && win_has(win, px, py)) {
                             const size_t pidx = (size_t)py * W + px;
                             resolve_sample(prev_samples[pidx], film + pidx, isg_stats + pidx * VSPG_ISG_STATS);
                         }
@@ -1235,7 +1240,7 @@ __global__ __launch_bounds__(kWgBlock, kWgWavesPerSimd) void k_render_wave_wg2(
                         px = pxy & 0xffff;
                         py = (int)((unsigned)pxy >> 16);
                     }
-                    valid = valid && px < W && py < H && smp < wave_end;  // tile padding: the slot stays free
+                    valid = valid && win_has(win, px, py) && smp < wave_end;  // tile padding: the slot stays free
                     if (valid) {
                         if (single_sample)
                             start_path(S, vsp_buf, vsp_ready, px, py, jump, sampler, st, &ch, isg);
@@ -1363,10 +1368,13 @@ __global__ __launch_bounds__(kWgBlock, kWgWavesPerSimd) void k_render_wave_wg2(
 }
 
 // film += the launch's sample buffer; ISG statistics likewise (the same read-modify-write forms the in-kernel flush used)
-__global__ __launch_bounds__(kBlock) void k_film_resolve(size_t npix, const float4 *__restrict__ wave_samples, float4 *__restrict__ film,
+// (over the window of the launch that parked them: the planes hold nothing of that launch outside it)
+__global__ __launch_bounds__(kBlock) void k_film_resolve(int W, PixelWindow win, const float4 *__restrict__ wave_samples, float4 *__restrict__ film,
                                                          float *__restrict__ isg_stats) {
-    const size_t i = (size_t)blockIdx.x * kBlock + threadIdx.x;
-    if (i >= npix) return;
+    const size_t j = (size_t)blockIdx.x * kBlock + threadIdx.x;
+    const size_t ww = (size_t)(win.x1 - win.x0);
+    if (j >= ww * (size_t)(win.y1 - win.y0)) return;
+    const size_t i = ((size_t)win.y0 + j / ww) * (size_t)W + (size_t)win.x0 + j % ww;
     resolve_sample(wave_samples[i], film + i, isg_stats + i * VSPG_ISG_STATS);
 }
 
@@ -1701,6 +1709,7 @@ struct VspgRenderer {
     float4 *wave_samples[2] = {nullptr, nullptr};
     int ws_cur = 0;
     bool ws_parked = false;
+    PixelWindow ws_win = {0, 0, 0, 0};  // the window of the launch that parked them (vspg_render_window)
     hipStream_t ws_stream = nullptr;  // the stream of the launch that parked them
     hipEvent_t ws_event = nullptr;    // recorded behind that launch: whoever touches the parked samples on another stream waits on it
     unsigned int *wf_lists = nullptr;   // 4 x n_items: active (even / odd iterations), walk, shadow
@@ -2536,8 +2545,8 @@ static bool wf_merged_walks(const VspgRenderer *r, bool guided) {
     if (const char *e = getenv("VSPG_WF_MERGED")) { if (e[0] == '0') merged = false; else if (e[0] == '1') merged = true; }
     return merged;
 }
-static int wf_render_pass(VspgRenderer *r, int sample, hipStream_t s, bool nvdb, bool guided, bool train, bool grey) {
-    const int tilesX = (r->cfg.xres + 7) / 8, tilesY = (r->cfg.yres + 7) / 8;
+static int wf_render_pass(VspgRenderer *r, const PixelWindow &win, int sample, hipStream_t s, bool nvdb, bool guided, bool train, bool grey) {
+    const int tilesX = win_tiles_x(win), tilesY = win_tiles_y(win);  // the pass's slots: the pixels of the window's tiles
     const size_t items = (size_t)tilesX * tilesY * 64;
     // Path-loop iterations of a pass.  Without medium boundaries every iteration ends at a vertex and raises the depth: maxdepth + 1
     // of them.  With boundaries an iteration may instead cross an interface (Li's `continue` at :399-404, depth unchanged): the loop
@@ -2546,7 +2555,7 @@ static int wf_render_pass(VspgRenderer *r, int sample, hipStream_t s, bool nvdb,
     const int base_iters = r->prm.maxdepth + 1;
     const int max_iters = bnd ? 4 * (r->prm.maxdepth + 2) + 16 : base_iters;
     const int n_iters = max_iters + 1;
-    if (!r->wf_pool || r->wf_items != items) {
+    if (!r->wf_pool || r->wf_items < items) {  // (grown, never shrunk: a renderer may be given several windows)
         if (r->wf_pool) (void)hipFree(r->wf_pool);
         if (r->wf_lists) (void)hipFree(r->wf_lists);
         if (r->wf_iters) (void)hipFree(r->wf_iters);
@@ -2569,6 +2578,8 @@ static int wf_render_pass(VspgRenderer *r, int sample, hipStream_t s, bool nvdb,
     a.jump = pcg_jump((unsigned long long)sample * 65536ull);
     a.n_items = (unsigned)items;
     a.tilesX = (unsigned)tilesX;
+    a.pix_org = (unsigned)(win.x0 & ~7) | ((unsigned)(win.y0 & ~7) << 16);
+    a.win = win;
     a.list_active = r->wf_lists;
     a.list_active2 = r->wf_lists + items;
     a.list_walk = r->wf_lists + 2 * items;
@@ -3211,7 +3222,8 @@ static int order_after_parking(VspgRenderer *r, hipStream_t s) {
 static int flush_parked_samples(VspgRenderer *r, hipStream_t s) {
     if (!r->ws_parked) return 0;
     if (const int rc = order_after_parking(r, s)) return rc;
-    hipLaunchKernelGGL(k_film_resolve, dim3((unsigned)((r->npix + kBlock - 1) / kBlock)), dim3(kBlock), 0, s, r->npix,
+    const size_t n_win = (size_t)(r->ws_win.x1 - r->ws_win.x0) * (size_t)(r->ws_win.y1 - r->ws_win.y0);
+    hipLaunchKernelGGL(k_film_resolve, dim3((unsigned)((n_win + kBlock - 1) / kBlock)), dim3(kBlock), 0, s, r->cfg.xres, r->ws_win,
                        r->wave_samples[r->ws_cur ^ 1], r->film, r->isg_stats);
     HIPCHK(hipGetLastError());
     r->ws_parked = false;
@@ -3286,12 +3298,25 @@ static const char *kernel_name_exact(VspgRenderer *r) {
 }
 
 int vspg_render_wave(VspgRenderer *r, int wave_start, int wave_end, void *stream) {
-    const RoctxRange range("vspg_render_wave");
+    const RoctxRange range("vspg_render_wave");  // (around the window call's own range: traces keep the name they filter on)
     if (!r) return fail(VSPG_EINVAL, "null renderer");
+    return vspg_render_window(r, 0, 0, r->cfg.xres, r->cfg.yres, wave_start, wave_end, stream);
+}
+
+// The window's tiles are those of the frame's 8x8 grid that touch it (PixelWindow, vspg_device.h): everything a launch sizes -- blocks,
+// static shares, tile cursors, the pipeline's lists, the training columns -- follows `items`, the pixels of those tiles.
+int vspg_render_window(VspgRenderer *r, int x0, int y0, int x1, int y1, int wave_start, int wave_end, void *stream) {
+    const RoctxRange range("vspg_render_window");
+    if (!r) return fail(VSPG_EINVAL, "null renderer");
+    if (x0 < 0 || y0 < 0 || x1 <= x0 || y1 <= y0 || x1 > r->cfg.xres || y1 > r->cfg.yres)
+        return fail(VSPG_EINVAL, "pixel window [" + std::to_string(x0) + "," + std::to_string(x1) + ") x [" + std::to_string(y0) + "," + std::to_string(y1) +
+                                     ") is empty or not inside the " + std::to_string(r->cfg.xres) + " x " + std::to_string(r->cfg.yres) + " film");
     if (wave_end < wave_start || wave_start < 0) return fail(VSPG_EINVAL, "bad wave range");
     if (wave_end == wave_start) return 0;
     HIPCHK(hipSetDevice(r->cfg.device));
-    const int tilesX = (r->cfg.xres + 7) / 8, tilesY = (r->cfg.yres + 7) / 8;
+    const PixelWindow win = {x0, y0, x1, y1};
+    const bool whole = x0 == 0 && y0 == 0 && x1 == r->cfg.xres && y1 == r->cfg.yres;
+    const int tilesX = win_tiles_x(win), tilesY = win_tiles_y(win);
     const long long items = (long long)tilesX * tilesY * 64;
     // persistent grid: exactly the resident wavefronts (never more blocks than tiles of work)
     long long blocks = (long long)r->num_cus * kBlocksPerCU;
@@ -3316,8 +3341,10 @@ int vspg_render_wave(VspgRenderer *r, int wave_start, int wave_end, void *stream
     if (guided && !r->field_set) return fail(VSPG_ESCOPE, "guiding enabled but the renderer holds no guiding field");
     // a one-sample launch of k_render_wave_wg2 resolves the samples its predecessor parked; every other launch adds to the film
     // itself, so the parked samples go in first
+    // (a launch resolves parked samples pixel by pixel as it starts them: those of ANOTHER window go in through k_film_resolve first)
     const bool defer = !uses_wf_pipeline(r) && uses_wg2(r) && n_samples == 1 && wg2_defer_enabled();
-    if (!defer) { const int rc = flush_parked_samples(r, (hipStream_t)stream); if (rc) return rc; }
+    const bool same_win = r->ws_win.x0 == x0 && r->ws_win.y0 == y0 && r->ws_win.x1 == x1 && r->ws_win.y1 == y1;
+    if (!defer || !same_win) { const int rc = flush_parked_samples(r, (hipStream_t)stream); if (rc) return rc; }
     if (uses_wf_pipeline(r)) {  // one pass per sample index of this shard, in order
 #ifdef VSPG_WF_DEBUG
         auto checksum = [&](const void *dptr, size_t bytes) -> unsigned long long {
@@ -3338,7 +3365,7 @@ int vspg_render_wave(VspgRenderer *r, int wave_start, int wave_end, void *stream
 #endif
         for (int w = first; w < wave_end; w += sc > 1 ? sc : 1) {
             const hipStream_t hs = (hipStream_t)stream;
-            const int rc = wf_render_pass(r, w, hs, nvdb, guided, guided && r->training, r->medium_grey);
+            const int rc = wf_render_pass(r, win, w, hs, nvdb, guided, guided && r->training, r->medium_grey);
             if (rc) return rc;
         }
 #ifdef VSPG_WF_DEBUG
@@ -3358,7 +3385,7 @@ int vspg_render_wave(VspgRenderer *r, int wave_start, int wave_end, void *stream
     if (train) {
         if (n_samples > 1) {  // a training launch covers one sample per pixel (the record buffer is sized for that): split
             for (int w = first; w < wave_end; w += sc > 1 ? sc : 1) {
-                const int rc = vspg_render_wave(r, w, w + 1, stream);
+                const int rc = vspg_render_window(r, x0, y0, x1, y1, w, w + 1, stream);
                 if (rc) return rc;
             }
             return 0;
@@ -3374,11 +3401,11 @@ int vspg_render_wave(VspgRenderer *r, int wave_start, int wave_end, void *stream
         if (G && train)                                                                                                   \
             hipLaunchKernelGGL((k_render_wave<M, G, G>), dim3((unsigned)blocks), dim3(kBlock), 0, (hipStream_t)stream,    \
                                r->dscene, r->film, r->isg_stats, r->vsp, r->vsp_ready, wave_start, wave_end, first,        \
-                               n_samples == 1 ? 1 : 0, jump, static_per_wave, dyn_base, work_head, r->counters, targs); \
+                               n_samples == 1 ? 1 : 0, jump, static_per_wave, dyn_base, work_head, r->counters, targs, win); \
         else                                                                                                              \
             hipLaunchKernelGGL((k_render_wave<M, G, false>), dim3((unsigned)blocks), dim3(kBlock), 0, (hipStream_t)stream, \
                                r->dscene, r->film, r->isg_stats, r->vsp, r->vsp_ready, wave_start, wave_end, first,        \
-                               n_samples == 1 ? 1 : 0, jump, static_per_wave, dyn_base, work_head, r->counters, targs); \
+                               n_samples == 1 ? 1 : 0, jump, static_per_wave, dyn_base, work_head, r->counters, targs, win); \
     } while (0)
     const bool use_wg = uses_wg_kernel(r);
     if (use_wg) {
@@ -3407,7 +3434,7 @@ int vspg_render_wave(VspgRenderer *r, int wave_start, int wave_end, void *stream
             const unsigned static_tiles = (unsigned)((n_tiles * (64 - tail64) / 64) / wblocks * wblocks);
 #define VSPG_LAUNCH_WG2(M, G, NPOOL, BLK, WV)                                                                                         \
     hipLaunchKernelGGL((k_render_wave_wg2<M, G, NPOOL, BLK, WV>), dim3((unsigned)wblocks), dim3(BLK), 0, (hipStream_t)stream, r->dscene, \
-                       r->film, r->isg_stats, r->vsp, r->vsp_ready, wave_end, first, single, jump, tiles_magic, static_tiles, work_head, ws_prev, ws_out, r->counters)
+                       r->film, r->isg_stats, r->vsp, r->vsp_ready, wave_end, first, single, jump, tiles_magic, static_tiles, work_head, ws_prev, ws_out, r->counters, targs, win)
             if (uses_wg3(r)) {
                 {  // the unguided rectangle-scene instantiations (the headline workload): also built in the tolerance modes
                     static_assert(kWgBlockHomog == VSPG_WG_BLOCK && kWgWavesHomog == VSPG_WG_WAVES, "wg3_launch_unguided's launch shape");
@@ -3417,7 +3444,7 @@ int vspg_render_wave(VspgRenderer *r, int wave_start, int wave_end, void *stream
                     r->head_parity ^= 1u;  // (undo the toggle above: no launch used that pair)
                     const Wg3Launch L3{r->dscene, r->film, r->isg_stats, r->vsp, r->vsp_ready, wave_end, first, single, jump, tiles_magic, head8, ws_prev, ws_out,
                                        r->counters, (unsigned)wblocks, (hipStream_t)stream, r->medium_grey ? (r->surfaces_grey ? 2 : 1) : 0,
-                                       r->medium_grey && r->surfaces_grey && r->null_zero ? 1 : 0};
+                                       r->medium_grey && r->surfaces_grey && r->null_zero ? 1 : 0, whole ? 0 : 1, win};
                     const int lrc = r->arith == VSPG_ARITH_FAST_WEIGHTS ? vspg_arith1_wg3(&L3) : r->arith == VSPG_ARITH_FAST ? vspg_arith2_wg3(&L3) : wg3_launch_exact(L3);
                     if (lrc != 0) return fail(VSPG_EHIP, std::string("k_render_wave_wg3: ") + hipGetErrorName((hipError_t)lrc));
                 }
@@ -3425,11 +3452,11 @@ int vspg_render_wave(VspgRenderer *r, int wave_start, int wave_end, void *stream
             if (gwg && train && guided_grey_simple(r))
                 hipLaunchKernelGGL((k_render_wave_wg2<HomogeneousMediumGreySceneNullZero, true, kWg2PoolTrainT<2>, kWgBlockGuided, kWgWavesGuided, true>), dim3((unsigned)wblocks),
                                    dim3(kWgBlockGuided), 0, (hipStream_t)stream, r->dscene, r->film, r->isg_stats, r->vsp, r->vsp_ready, wave_end, first, single, jump,
-                                   tiles_magic, static_tiles, work_head, ws_prev, ws_out, r->counters, targs);
+                                   tiles_magic, static_tiles, work_head, ws_prev, ws_out, r->counters, targs, win);
             else if (gwg && train)
                 hipLaunchKernelGGL((k_render_wave_wg2<HomogeneousMediumSimple, true, kWg2PoolTrainT<0>, kWgBlockGuided, kWgWavesGuided, true>), dim3((unsigned)wblocks),
                                    dim3(kWgBlockGuided), 0, (hipStream_t)stream, r->dscene, r->film, r->isg_stats, r->vsp, r->vsp_ready, wave_end, first, single, jump,
-                                   tiles_magic, static_tiles, work_head, ws_prev, ws_out, r->counters, targs);
+                                   tiles_magic, static_tiles, work_head, ws_prev, ws_out, r->counters, targs, win);
             else if (gwg && guided_grey_simple(r)) VSPG_LAUNCH_WG2(HomogeneousMediumGreySceneNullZero, true, kWg2PoolGuidedT<2>, kWgBlockGuided, kWgWavesGuided);
             else if (gwg) VSPG_LAUNCH_WG2(HomogeneousMediumSimple, true, kWg2PoolGuidedT<0>, kWgBlockGuided, kWgWavesGuided);
             else if (uses_wg_full(r)) VSPG_LAUNCH_WG2(HomogeneousMedium, false, kWg2PoolFull, kWgBlockHomog, kWgWavesHomog);
@@ -3442,6 +3469,7 @@ int vspg_render_wave(VspgRenderer *r, int wave_start, int wave_end, void *stream
             if (single) {  // this launch's samples are parked in ws_out (its predecessor's, if any were, have just been resolved)
                 r->ws_cur ^= 1;
                 r->ws_parked = true;
+                r->ws_win = win;
                 r->ws_stream = (hipStream_t)stream;
                 if (!r->ws_event) HIPCHK(hipEventCreateWithFlags(&r->ws_event, hipEventDisableTiming));
                 HIPCHK(hipEventRecord(r->ws_event, (hipStream_t)stream));
@@ -3450,7 +3478,7 @@ int vspg_render_wave(VspgRenderer *r, int wave_start, int wave_end, void *stream
         } else {
 #define VSPG_LAUNCH_WG(M, NPOOL, BLK, WV)                                                                                            \
     hipLaunchKernelGGL((k_render_wave_wg<M, false, NPOOL, BLK, WV>), dim3((unsigned)wblocks), dim3(BLK), 0, (hipStream_t)stream, r->dscene, \
-                       r->film, r->isg_stats, r->vsp, r->vsp_ready, wave_end, first, single, jump, tiles_magic, work_head, r->counters)
+                       r->film, r->isg_stats, r->vsp, r->vsp_ready, wave_end, first, single, jump, tiles_magic, work_head, r->counters, win)
             if (grid) VSPG_LAUNCH_WG(GridMedium, kWgPoolGrid, kWgBlockGrid, kWgWavesGrid);
             else if (r->medium_grey && r->surfaces_grey && r->null_zero) VSPG_LAUNCH_WG(HomogeneousMediumGreySceneNullZero, kWgPoolHomogT<2>, kWgBlockHomog, kWgWavesHomog);  // ... and the null-collision coefficient is exactly 0
             else if (r->medium_grey && r->surfaces_grey) VSPG_LAUNCH_WG(HomogeneousMediumGreyScene, kWgPoolHomogT<2>, kWgBlockHomog, kWgWavesHomog);  // ... and every Kd bitwise grey: beta is grey by construction too

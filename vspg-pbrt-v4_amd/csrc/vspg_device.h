@@ -621,6 +621,18 @@ struct DBvh4Node {
 static_assert(sizeof(DBvh4Node) == 128, "one node = eight 16-byte loads");
 constexpr int32_t kBvhAbsent = (int32_t)0x80000000;
 constexpr int kBvhStack = 48;   // entries; a node leaves at most three behind per level, the builder bounds the depth at 15
+// A pixel window [x0, x1) x [y0, y1) in absolute film pixels (the Bounds2i pixelBounds of film.cpp:97; vspg_render_window).  The 8x8
+// tile grid of the path kernels stays anchored to the frame: a launch enumerates the tile rectangle [x0 >> 3, (x1 + 7) >> 3) x
+// [y0 >> 3, (y1 + 7) >> 3) -- tile indices and work items count inside that rectangle -- and masks the pixels outside the window.
+// Every per-pixel buffer keeps its W * H size and its absolute index py * W + px.
+struct PixelWindow {
+    int32_t x0, y0, x1, y1;
+};
+__host__ __device__ __forceinline__ int win_tile_x0(const PixelWindow &w) { return w.x0 >> 3; }
+__host__ __device__ __forceinline__ int win_tile_y0(const PixelWindow &w) { return w.y0 >> 3; }
+__host__ __device__ __forceinline__ int win_tiles_x(const PixelWindow &w) { return ((w.x1 + 7) >> 3) - (w.x0 >> 3); }
+__host__ __device__ __forceinline__ int win_tiles_y(const PixelWindow &w) { return ((w.y1 + 7) >> 3) - (w.y0 >> 3); }
+__host__ __device__ __forceinline__ bool win_has(const PixelWindow &w, int px, int py) { return px >= w.x0 && px < w.x1 && py >= w.y0 && py < w.y1; }
 struct DScene {
     int32_t n_quads, n_lights;
     int32_t n_tris, n_bvh_nodes;

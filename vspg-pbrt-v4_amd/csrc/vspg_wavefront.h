@@ -234,7 +234,10 @@ struct WfArgs {
     int sample;                  // the sample index this pass renders
     PcgJump jump;                // PCG skip-ahead for sample * 65536
     unsigned int n_items;        // tiles * 64
-    unsigned int tilesX;
+    unsigned int tilesX;         // ... of the pass's tile rectangle: the frame's, or the window's (vspg_render_window)
+    unsigned int pix_org;        // pixel origin of that rectangle, (x0 & ~7) | (y0 & ~7) << 16 (resolutions stop at 32768): ONE scalar,
+                                 // all that the kernels past the start of a path need of the window (wf_pixel_of)
+    PixelWindow win;             // the pixels the pass covers: read only where paths start (k_wf_start, the first k_wf_segment_vertex)
     unsigned int *list_active;   // slots with a segment in flight, even iterations
     unsigned int *list_active2;  // ... odd iterations (k_wf_vertex reads one and writes the other)
     unsigned int *list_walk;
@@ -268,11 +271,12 @@ VDEV void wf_rec_store(const WfArgs &, unsigned, const NullRecorder &) {}
 VDEV void wf_rec_finish(const WfArgs &a, unsigned slot, const PathRecorder &rec) { a.train.seg_count[slot] = rec.n; }  // PropagateSamples (:627) follows in k_propagate
 VDEV void wf_rec_finish(const WfArgs &, unsigned, const NullRecorder &) {}
 
-VDEV void wf_pixel_of(unsigned slot, unsigned tilesX, int *px, int *py) {
+template <class Args>
+VDEV void wf_pixel_of(unsigned slot, const Args &a, int *px, int *py) {
     const unsigned tile = slot >> 6, l = slot & 63u;
-    const unsigned ty = tile / tilesX, tx = tile - ty * tilesX;
-    *px = (int)(tx * 8u + (l & 7u));
-    *py = (int)(ty * 8u + (l >> 3));
+    const unsigned ty = tile / a.tilesX, tx = tile - ty * a.tilesX;
+    *px = (int)(tx * 8u + (l & 7u) + (a.pix_org & 0xffffu));
+    *py = (int)(ty * 8u + (l >> 3) + (a.pix_org >> 16));
 }
 
 // Appending to a global list.  One returning atomic per WAVEFRONT on the list's counter is too many: a single hot
@@ -438,7 +442,7 @@ VDEV typename Medium::Iter wf_load_iter(const WfPool &P, unsigned slot, const Me
 // pass, so nobody else touches the pixel: plain read-modify-write (film_add_sample_rmw).
 VDEV void wf_finish_path(const WfArgs &a, unsigned slot, const PathState &st, const IsgSample &isg) {
     int px, py;
-    wf_pixel_of(slot, a.tilesX, &px, &py);
+    wf_pixel_of(slot, a, &px, &py);
     const size_t pidx = (size_t)py * a.scene->xres + px;
     const Spec L = finish_radiance(st.L);
     film_add_sample_rmw(a.film + pidx, L);
@@ -782,7 +786,7 @@ VDEV void wf_segment_begin(const WfArgs &a, const DScene &S, const Medium &mediu
         bool guide = false;
         if (has_bnd<Medium::kBnd>(S) && st.depth == 0) {  // the camera segment may reach the medium through a boundary, an iteration or more after
             int px, py;                           // the path started: the pixel's primary VSP is read where it is used
-            wf_pixel_of(slot, a.tilesX, &px, &py);
+            wf_pixel_of(slot, a, &px, &py);
             st.vsp0 = (a.vsp_ready & VSP_READY) ? a.vsp_buf[(size_t)py * S.xres + px] : 0.5f;
         }
         const float vsp = fetch_vsp<GUIDED>(S, st, &guide);
@@ -907,8 +911,8 @@ __global__ __launch_bounds__(kWfBlock, 3) void k_wf_start(WfArgs a) {
         bool alive = false, walk = false;
         if (slot < n) {
             int px, py;
-            wf_pixel_of(slot, a.tilesX, &px, &py);
-            if (px < S.xres && py < S.yres) {
+            wf_pixel_of(slot, a, &px, &py);
+            if (win_has(a.win, px, py)) {
                 PathState st;
                 Sampler sampler;
                 IsgSample isg;
@@ -1195,7 +1199,7 @@ VDEV int wf_vertex(const WfArgs &a, const DScene &S, const Medium &medium, unsig
     if constexpr (GUIDED) {
         {   // guided RR (:274-285): the pixel's contribution estimate, once the image-space buffer is ready
             int qx, qy;
-            wf_pixel_of(slot, a.tilesX, &qx, &qy);
+            wf_pixel_of(slot, a, &qx, &qy);
             st.guideRR = S.prm.rrguiding && S.contrib_ready;
             st.pce = st.guideRR ? S.contrib[(size_t)qy * S.xres + qx] : 0.f;
         }
@@ -1391,7 +1395,7 @@ __global__ __launch_bounds__(kWfBlock, GUIDED ? VSPG_WF_VERTEX_WAVES_GUIDED : (M
                 // the path ended at the previous vertex; that addition was all it waited for
             } else {
                 int px, py;
-                wf_pixel_of(slot, a.tilesX, &px, &py);
+                wf_pixel_of(slot, a, &px, &py);
                 Isect si;
                 si.hit = (fl & WFL_HIT) != 0;
                 si.quad = P.i(WF_VXG, slot);
@@ -1598,14 +1602,14 @@ __global__ __launch_bounds__(kWfBlock, 2) void k_wf_segment_vertex(WfArgs a, int
         if (idx < n) {
             slot = first ? idx : list_in[idx];
             int px, py;
-            wf_pixel_of(slot, a.tilesX, &px, &py);
+            wf_pixel_of(slot, a, &px, &py);
             PathState st;
             Sampler sampler;
             IsgSample isg;
             int ch = 0;
             bool run = false;
             if (first) {
-                if (px < S.xres && py < S.yres) {
+                if (win_has(a.win, px, py)) {
                     start_path(S, a.vsp_buf, a.vsp_ready, px, py, a.jump, sampler, st, &ch, isg);
                     if constexpr (TRAIN) {
                         wf_rec_load(a, slot, pc.rec);

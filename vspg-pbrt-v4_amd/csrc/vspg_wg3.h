@@ -128,19 +128,29 @@ constexpr int wg3_pool_paths(int other_bytes) {
     return n < VSPG_WG3_NP_CAP ? n : VSPG_WG3_NP_CAP;
 }
 
-template <class Medium, bool GUIDED, int NP, int kWgBlock, int kWgWavesPerSimd, bool TRAIN = false>
-__global__ __launch_bounds__(kWgBlock, kWgWavesPerSimd) void k_render_wave_wg3(
+// The kernel's body.  WINDOW: the launch covers the pixel window `win` (vspg_render_window) instead of the frame.  The 8x8 tile grid stays
+// anchored to the frame; the launch enumerates the tile rectangle that covers the window (tile index -> window-local row / column, plus
+// the rectangle's origin) and masks the lanes outside the window the way the full-frame launch masks lanes past W / H.  The full-frame
+// instantiation takes none of it: `win` is unused there and its code is what it was (it is pinned at its SGPR limit and within five
+// selects / compares of its ceiling, tests/test_headline_kernel_census.py).
+template <class Medium, bool GUIDED, int NP, int kWgBlock, int kWgWavesPerSimd, bool TRAIN, bool WINDOW>
+__device__ __forceinline__ void wg3_render(
     const DScene *__restrict__ Sp, float4 *__restrict__ film, float *__restrict__ isg_stats, const float *__restrict__ vsp_buf,
     int vsp_ready, int wave_end, int first_sample, int single_sample, PcgJump jump, unsigned int tiles_magic,
     unsigned int *__restrict__ work_head, const float4 *__restrict__ prev_samples,
-    float4 *__restrict__ wave_samples, unsigned long long *__restrict__ counters, TrainArgs train = TrainArgs{nullptr, nullptr, nullptr, nullptr, 0, 0}) {
+    float4 *__restrict__ wave_samples, unsigned long long *__restrict__ counters, TrainArgs train, const PixelWindow win) {
     // (each argument its own register from here on: the four ints arrive as one 128-bit load, and a tuple is spilled as a unit)
     vsp_ready = w3_at_use(vsp_ready), wave_end = w3_at_use(wave_end), first_sample = w3_at_use(first_sample);
     single_sample = w3_at_use(single_sample);
     const DScene &S = *Sp;
     const int W = S.xres, H = S.yres;
-    const int tilesX = (W + 7) >> 3, tilesY = (H + 7) >> 3;
+    const int tilesX = WINDOW ? win_tiles_x(win) : (W + 7) >> 3, tilesY = WINDOW ? win_tiles_y(win) : (H + 7) >> 3;
     const unsigned n_tiles = (unsigned)(tilesX * tilesY);
+    // is pixel (px, py) of a claimed tile part of the launch?  (tile padding past the frame / outside the window)
+    const auto in_launch = [&](int px, int py) {
+        if constexpr (WINDOW) return win_has(win, px, py);
+        else return px < W && py < H;
+    };
     const int lane = threadIdx.x & 63;
     const int sample_step = S.shard_count > 1 ? S.shard_count : 1;
     // The tile head: kWg3Heads cursors, each on a 128-byte line of its own, cursor k handing out tiles k, k + kWg3Heads, ...  One cursor
@@ -185,7 +195,8 @@ __global__ __launch_bounds__(kWgBlock, kWgWavesPerSimd) void k_render_wave_wg3(
     const auto rec_bind = [&](int pxy) {
         if constexpr (TRAIN) {
             const unsigned px = (unsigned)pxy & 0xffffu, py = (unsigned)pxy >> 16;
-            const unsigned item = ((py >> 3) * (unsigned)tilesX + (px >> 3)) * 64u + ((py & 7u) << 3) + (px & 7u);
+            const unsigned tcol = WINDOW ? (px >> 3) - (unsigned)win_tile_x0(win) : px >> 3, trow = WINDOW ? (py >> 3) - (unsigned)win_tile_y0(win) : py >> 3;
+            const unsigned item = (trow * (unsigned)tilesX + tcol) * 64u + ((py & 7u) << 3) + (px & 7u);
             pc.rec.base = train.segbuf + item;
             pc.rec.stride = (int)train.n_items;
             pc.rec.max_seg = train_rec_capacity(S.prm.maxdepth);
@@ -229,6 +240,7 @@ __global__ __launch_bounds__(kWgBlock, kWgWavesPerSimd) void k_render_wave_wg3(
         // Lane 0 performs the claims.  Order: a FULL chunk of one kind (volume vertices, surface vertices, segments, a fresh
         // tile) before a vertex chunk mixed from both vertex queues, before partial chunks (only while their producers idle).
         unsigned kind = W3_NONE, pos0 = 0, n0 = 0, pos1 = 0, n1 = 0, q0 = Q_VV, tile = 0;
+        unsigned fresh_entry = 0;  // a FRESH chunk's free-ring entry of this lane
         {
             const auto U = [](unsigned v) { return (unsigned)__builtin_amdgcn_readfirstlane((int)v); };
             const w3_lds_v4 qw = (w3_lds_v4)(s_w);
@@ -275,6 +287,16 @@ __global__ __launch_bounds__(kWgBlock, kWgWavesPerSimd) void k_render_wave_wg3(
                 bump(W3_LIVE, 64);  // BEFORE the tile is claimed: `live == 0` then says nobody can still start a path
                 if (claim(Q_F, hF, 64u)) {
                     kind = W3_FRESH; pos0 = hF; n0 = 64u;
+                    // The claimed entries are read HERE, before the tile cursors are asked.  The free ring starts full (RES = COM = NP), so a
+                    // sibling that claims the next 64 entries, ends paths and pushes their slots writes at index NP % NP = 0 onwards: over
+                    // entries claimed but not read yet, if the reader is still going round dry cursors (small images and small windows: the
+                    // cursors run dry in the first lap; on a later lap a claimed-unread chunk plus NP - 64 outstanding pushes reaches it the
+                    // same way).  A slot would then be handed out twice.  Read at once, the window shrinks from the whole cursor loop to
+                    // the few instructions between the CAS and this LDS read, in which a sibling would have to claim, run a segment and
+                    // push.  That is a timing argument, not an ordering guarantee: rings 2 * NP deep or a producer-side RES - HEAD < NP
+                    // check would exclude it by construction (DESIGN.md 4.5 says what they cost).
+                    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");
+                    fresh_entry = s_ring[Q_F][(hF + (unsigned)lane) % (unsigned)NP];
                     tile = n_tiles;
                     while (wtried < (unsigned)kWg3Heads) {
                         unsigned c = 0xffffffffu;
@@ -373,10 +395,10 @@ __global__ __launch_bounds__(kWgBlock, kWgWavesPerSimd) void k_render_wave_wg3(
             const bool fresh = kind == W3_FRESH;
             const bool tile_ok = !fresh || tile < n_tiles;  // (the head has run dry: the 64 slots go back)
             if (fresh && !tile_ok) {
-                slot = s_ring[Q_F][(pos0 + (unsigned)lane) % (unsigned)NP];
+                slot = (int)fresh_entry;
                 freed = true;
             } else if ((unsigned)lane < n0) {
-                const unsigned e = s_ring[fresh ? Q_F : Q_A][(pos0 + (unsigned)lane) % (unsigned)NP];
+                const unsigned e = fresh ? fresh_entry : s_ring[Q_A][(pos0 + (unsigned)lane) % (unsigned)NP];
                 slot = (int)(e & (kRestartBit - 1u));
                 const bool primary = fresh || (e & kRestartBit) != 0u;
                 Sampler sampler;
@@ -392,13 +414,14 @@ __global__ __launch_bounds__(kWgBlock, kWgWavesPerSimd) void k_render_wave_wg3(
                         unsigned ty = w3_at_use(tilesX) == 1 ? tile : __umulhi(tile, tiles_magic);
                         unsigned tx = tile - ty * (unsigned)tilesX;
                         while (tx >= (unsigned)tilesX) { tx -= (unsigned)tilesX; ty++; }
+                        if constexpr (WINDOW) { tx += (unsigned)win_tile_x0(win); ty += (unsigned)win_tile_y0(win); }
                         px = (int)(tx * 8u + ((unsigned)lane & 7u));
                         py = (int)(ty * 8u + ((unsigned)lane >> 3));
                         pxy = px | (py << 16);
                         smp = first_sample;
                         // the PREVIOUS one-sample launch parked this pixel's sample (vspg_render_wave: deferred resolve): it enters
                         // the film now, before this launch's sample of the pixel can (same order of additions as ever)
-                        if (w3_at_use(prev_samples) != nullptr && px < W && py < H) {
+                        if (w3_at_use(prev_samples) != nullptr && in_launch(px, py)) {
                             const size_t pidx = (size_t)py * W + px;
                             resolve_sample(prev_samples[pidx], film + pidx, isg_stats + pidx * VSPG_ISG_STATS);
                         }
@@ -408,7 +431,7 @@ __global__ __launch_bounds__(kWgBlock, kWgWavesPerSimd) void k_render_wave_wg3(
                         px = pxy & 0xffff;
                         py = (int)((unsigned)pxy >> 16);
                     }
-                    valid = px < W && py < H && smp < wave_end;  // tile padding: the slot stays free
+                    valid = in_launch(px, py) && smp < wave_end;  // tile padding: the slot stays free
                     if (valid) {
                         if (w3_at_use(single_sample))
                             start_path(S, vsp_buf, w3_at_use(vsp_ready), px, py, jump, sampler, st, &ch, isg);
@@ -478,6 +501,27 @@ __global__ __launch_bounds__(kWgBlock, kWgWavesPerSimd) void k_render_wave_wg3(
     if (threadIdx.x < CNT_COUNT) atomicAdd(&counters[threadIdx.x], (unsigned long long)s_counters[threadIdx.x]);
 }
 
+template <class Medium, bool GUIDED, int NP, int kWgBlock, int kWgWavesPerSimd, bool TRAIN = false>
+__global__ __launch_bounds__(kWgBlock, kWgWavesPerSimd) void k_render_wave_wg3(
+    const DScene *__restrict__ Sp, float4 *__restrict__ film, float *__restrict__ isg_stats, const float *__restrict__ vsp_buf,
+    int vsp_ready, int wave_end, int first_sample, int single_sample, PcgJump jump, unsigned int tiles_magic,
+    unsigned int *__restrict__ work_head, const float4 *__restrict__ prev_samples,
+    float4 *__restrict__ wave_samples, unsigned long long *__restrict__ counters, TrainArgs train = TrainArgs{nullptr, nullptr, nullptr, nullptr, 0, 0}) {
+    wg3_render<Medium, GUIDED, NP, kWgBlock, kWgWavesPerSimd, TRAIN, false>(Sp, film, isg_stats, vsp_buf, vsp_ready, wave_end, first_sample, single_sample, jump,
+                                                                            tiles_magic, work_head, prev_samples, wave_samples, counters, train, PixelWindow{0, 0, 0, 0});
+}
+// the same kernel over a pixel window (a kernel name of its own: the full-frame instantiations stay the only ones of theirs);
+// tiles_magic = ceil(2^32 / the window's tile columns)
+template <class Medium, bool GUIDED, int NP, int kWgBlock, int kWgWavesPerSimd, bool TRAIN = false>
+__global__ __launch_bounds__(kWgBlock, kWgWavesPerSimd) void k_render_wave_wg3_window(
+    const DScene *__restrict__ Sp, float4 *__restrict__ film, float *__restrict__ isg_stats, const float *__restrict__ vsp_buf,
+    int vsp_ready, int wave_end, int first_sample, int single_sample, PcgJump jump, unsigned int tiles_magic,
+    unsigned int *__restrict__ work_head, const float4 *__restrict__ prev_samples,
+    float4 *__restrict__ wave_samples, unsigned long long *__restrict__ counters, TrainArgs train, PixelWindow win) {
+    wg3_render<Medium, GUIDED, NP, kWgBlock, kWgWavesPerSimd, TRAIN, true>(Sp, film, isg_stats, vsp_buf, vsp_ready, wave_end, first_sample, single_sample, jump,
+                                                                           tiles_magic, work_head, prev_samples, wave_samples, counters, train, win);
+}
+
 // ---- host side: the unguided rectangle-scene instantiations behind one call (what vspg_capi.hip launches for them, and what the
 // fast-arithmetic translation units export: vspg_fast.hip, vspg_arith.h) -------------------------------------------------------
 #ifndef VSPG_WG_WAVES
@@ -502,6 +546,8 @@ struct Wg3Launch {
     hipStream_t stream;
     int grey;          // 0: chromatic; 1: grey medium; 2: grey medium and grey surfaces (HomogeneousMediumT)
     int null_zero;     // ... whose null-collision coefficient is exactly 0
+    int windowed;      // the launch covers `win`, not the frame (vspg_render_window): k_render_wave_wg3_window
+    PixelWindow win;
 };
 template <int GREY> constexpr int kWg3PoolHomogT = wg3_pool_paths<PoolLayout<false, GREY>>(VSPG_WG3_OTHER);
 // (a template: a plain inline host function that names kernels instantiates them in every translation unit that includes this
@@ -509,9 +555,16 @@ template <int GREY> constexpr int kWg3PoolHomogT = wg3_pool_paths<PoolLayout<fal
 template <int = 0>
 inline int wg3_launch_unguided(const Wg3Launch &L) {
 #define VSPG_WG3_GO(M, NPOOL)                                                                                                                \
-    hipLaunchKernelGGL((k_render_wave_wg3<M, false, NPOOL, VSPG_WG_BLOCK, VSPG_WG_WAVES, false>), dim3(L.blocks), dim3(VSPG_WG_BLOCK), 0, L.stream, \
-                       L.dscene, L.film, L.isg_stats, L.vsp, L.vsp_ready, L.wave_end, L.first_sample, L.single_sample, L.jump, L.tiles_magic,  \
-                       L.work_head, L.ws_prev, L.ws_out, L.counters, TrainArgs{nullptr, nullptr, nullptr, nullptr, 0, 0})
+    do {                                                                                                                                     \
+        if (L.windowed)                                                                                                                      \
+            hipLaunchKernelGGL((k_render_wave_wg3_window<M, false, NPOOL, VSPG_WG_BLOCK, VSPG_WG_WAVES, false>), dim3(L.blocks), dim3(VSPG_WG_BLOCK), 0, \
+                               L.stream, L.dscene, L.film, L.isg_stats, L.vsp, L.vsp_ready, L.wave_end, L.first_sample, L.single_sample, L.jump, \
+                               L.tiles_magic, L.work_head, L.ws_prev, L.ws_out, L.counters, TrainArgs{nullptr, nullptr, nullptr, nullptr, 0, 0}, L.win); \
+        else                                                                                                                                 \
+            hipLaunchKernelGGL((k_render_wave_wg3<M, false, NPOOL, VSPG_WG_BLOCK, VSPG_WG_WAVES, false>), dim3(L.blocks), dim3(VSPG_WG_BLOCK), 0, L.stream, \
+                               L.dscene, L.film, L.isg_stats, L.vsp, L.vsp_ready, L.wave_end, L.first_sample, L.single_sample, L.jump, L.tiles_magic, \
+                               L.work_head, L.ws_prev, L.ws_out, L.counters, TrainArgs{nullptr, nullptr, nullptr, nullptr, 0, 0});          \
+    } while (0)
     if (L.grey >= 2 && L.null_zero) VSPG_WG3_GO(HomogeneousMediumGreySceneNullZero, kWg3PoolHomogT<2>);
     else if (L.grey >= 2) VSPG_WG3_GO(HomogeneousMediumGreyScene, kWg3PoolHomogT<2>);
     else if (L.grey == 1) VSPG_WG3_GO(HomogeneousMediumGrey, kWg3PoolHomogT<1>);

@@ -405,6 +405,7 @@ GuidedVolPathVSPGIntegrator::GuidedVolPathVSPGIntegrator(const VspgIntegratorPar
     std::memset(&cfg, 0, sizeof cfg);
     cfg.xres = xres; cfg.yres = yres; cfg.spp = pixelSamples; cfg.seed = seed;
     cfg.shard_index = 0; cfg.shard_count = 1; cfg.device = device;
+    bounds[2] = xres; bounds[3] = yres;
     int rc = vspg_renderer_create(&scene, &params, &cfg, &renderer);
     if (rc != 0) throw Error(std::string("GuidedVolPathVSPGIntegrator: ") + vspg_last_error());
     if (cacheSettings.load) {  // :116-125: FileExists() ? load (guideTraining = false) : warn and train a fresh field
@@ -654,7 +655,7 @@ void GuidedVolPathVSPGIntegrator::Render() {
     while (waveStart < spp) {
         const auto t0 = std::chrono::steady_clock::now();
         const std::string kernel = waveLog ? vspg_renderer_kernel_name(renderer) : "";
-        if (vspg_render_wave(renderer, waveStart, waveEnd, nullptr) != 0) throw Error(vspg_last_error());
+        if (vspg_render_window(renderer, bounds[0], bounds[1], bounds[2], bounds[3], waveStart, waveEnd, nullptr) != 0) throw Error(vspg_last_error());
         PostProcessWave();
         if (waveLog) {  // one JSON line per wave: the counter read synchronises the stream, so `ms` is the wave's wall time
             VspgCounters c;
@@ -680,11 +681,21 @@ std::string GuidedVolPathVSPGIntegrator::ToString() const {
                   params.regularize ? "true" : "false");
     return buf;
 }
+void GuidedVolPathVSPGIntegrator::SetPixelBounds(int x0, int y0, int x1, int y1) {
+    if (x0 < 0 || y0 < 0 || x1 <= x0 || y1 <= y0 || x1 > cfg.xres || y1 > cfg.yres) throw Error("pixel bounds are empty or not inside the film");
+    bounds[0] = x0; bounds[1] = y0; bounds[2] = x1; bounds[3] = y1;
+}
 Film GuidedVolPathVSPGIntegrator::GetFilm() {
+    std::vector<float> whole((size_t)cfg.xres * cfg.yres * 4);
+    if (vspg_film_read(renderer, whole.data(), nullptr) != 0) throw Error(vspg_last_error());
+    return CropFilm(whole, cfg.xres, bounds[0], bounds[1], bounds[2], bounds[3]);
+}
+Film CropFilm(const std::vector<float> &rgbw, int xres, int x0, int y0, int x1, int y1) {
     Film f;
-    f.xres = cfg.xres; f.yres = cfg.yres;
-    f.rgbw.resize((size_t)cfg.xres * cfg.yres * 4);
-    if (vspg_film_read(renderer, f.rgbw.data(), nullptr) != 0) throw Error(vspg_last_error());
+    f.xres = x1 - x0; f.yres = y1 - y0; f.x0 = x0; f.y0 = y0;
+    f.rgbw.resize((size_t)f.xres * f.yres * 4);
+    for (int y = y0; y < y1; ++y)
+        std::memcpy(&f.rgbw[(size_t)(y - y0) * f.xres * 4], &rgbw[((size_t)y * xres + x0) * 4], (size_t)f.xres * 4 * sizeof(float));
     return f;
 }
 VspgCounters GuidedVolPathVSPGIntegrator::Counters() {

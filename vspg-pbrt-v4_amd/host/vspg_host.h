@@ -83,12 +83,16 @@ VspgMedium CreateMedium(const std::string &name, const ParameterDictionary &para
                         std::vector<float> *temperatureStorage = nullptr);
 
 struct Film {
-    int xres = 0, yres = 0;
-    std::vector<float> rgbw;  // W*H*4: sum w*r, sum w*g, sum w*b, sum w
+    int xres = 0, yres = 0;   // the size of the film's pixelBounds: the window that was rendered (the whole frame by default)
+    int x0 = 0, y0 = 0;       // ... and its origin in the frame; pixel (x, y) below is relative to it
+    std::vector<float> rgbw;  // xres*yres*4: sum w*r, sum w*g, sum w*b, sum w
     // RGBFilm::GetPixelRGB (film.h:269-287) without the output colour transform
     void GetPixelRGB(int x, int y, float rgb[3]) const;
     void WritePFM(const std::string &filename) const;
 };
+
+// the pixels [x0, x1) x [y0, y1) of a whole-frame film (xres pixels per row)
+Film CropFilm(const std::vector<float> &rgbw, int xres, int x0, int y0, int x1, int y1);
 
 // Guiding-cache file (openpgl::cpp::Field::Store / Field(device, file), guidedvolpathvspgintegrator.cpp:
 // 117-128, 210-213).  Format "VSPGFLD1", little endian:
@@ -144,6 +148,9 @@ class Integrator {
     virtual ~Integrator() = default;
     virtual void Render() = 0;
     virtual std::string ToString() const = 0;
+    // the film's pixelBounds [x0, x1) x [y0, y1), inside the frame and not empty (film.cpp:97-172; the scene-file reader resolves
+    // "cropwindow" / "pixelbounds"): Render() covers these pixels only (integrators.cpp:183).  Default: the whole frame.
+    virtual void SetPixelBounds(int x0, int y0, int x1, int y1) = 0;
     // Integrator::Create: "guidedvolpathvspg"; "guidedvolpath" is accepted as an alias ONLY when
     // the dictionary carries "vspguiding" (the option BASELINE.json names), see SURVEY.md 0.1
     static std::unique_ptr<Integrator> Create(const std::string &name, const ParameterDictionary &parameters,
@@ -163,7 +170,8 @@ class GuidedVolPathVSPGIntegrator : public Integrator {
     void Render() override;       // wave loop: 1 spp per wave, PostProcessWave after each
     void PostProcessWave();       // guidedvolpathvspgintegrator.cpp:230-260
     std::string ToString() const override;
-    Film GetFilm();
+    Film GetFilm();               // the pixels of the pixel bounds (RGBFilm::WriteImage, film.cpp:541-557)
+    void SetPixelBounds(int x0, int y0, int x1, int y1) override;
     VspgCounters Counters();
     VspgTrainStats TrainingStats();      // guideTraining / guiding_field->GetIteration()
     GuidingCache GetGuidingCache();      // the field as it stands (trained in-loop or loaded)
@@ -178,6 +186,7 @@ class GuidedVolPathVSPGIntegrator : public Integrator {
     VspgIntegratorParams params;
     VspgRenderConfig cfg;
     VspgRenderer *renderer = nullptr;
+    int bounds[4] = {0, 0, 0, 0};  // x0, y0, x1, y1
     int spp;
     GuidingCacheSettings cacheSettings;
     TrBufferSettings trSettings;

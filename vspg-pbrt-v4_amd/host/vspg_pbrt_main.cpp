@@ -1,5 +1,6 @@
 // vspg_pbrt -- render a pbrt-v4 scene file (the subset of vspg_scenefile.h) with the MI355X-native GuidedVolPathVSPG path.
 //   vspg_pbrt scene.pbrt [--spp N] [--outfile image.pfm] [--seed S] [--device D] [--wave-log waves.jsonl] [--parse-only]
+//             [--cropwindow x0,x1,y0,y1] [--pixelbounds x0,x1,y0,y1]   (cmd/pbrt.cpp:132-153; they override the file's Film parameters)
 // The counterpart of `pbrt scene.pbrt` for this integrator (cmd/pbrt.cpp -> RenderCPU, cpu/render.cpp:56-57); the image is
 // written as PFM (RGBFilm::WriteImage's EXR needs OpenEXR, an absent submodule).
 #include <cstdio>
@@ -14,6 +15,8 @@ int main(int argc, char **argv) {
     int spp = -1, seed = -1, device = 0;
     std::string waveLogPath;
     bool parseOnly = false;
+    vspg::FilmOverrides film;
+    std::string cropArg, boundsArg;
     for (int i = 1; i < argc; ++i) {
         const std::string a = argv[i];
         auto next = [&]() -> const char * { if (i + 1 >= argc) { std::fprintf(stderr, "%s needs a value\n", a.c_str()); std::exit(2); } return argv[++i]; };
@@ -23,12 +26,17 @@ int main(int argc, char **argv) {
         else if (a == "--device") device = std::atoi(next());
         else if (a == "--wave-log") waveLogPath = next();
         else if (a == "--parse-only") parseOnly = true;
+        else if (a == "--cropwindow") cropArg = next();
+        else if (a == "--pixelbounds") boundsArg = next();
         else if (!a.empty() && a[0] == '-') { std::fprintf(stderr, "unknown option %s\n", a.c_str()); return 2; }
         else scene = a;
     }
-    if (scene.empty()) { std::fprintf(stderr, "usage: vspg_pbrt scene.pbrt [--spp N] [--outfile image.pfm] [--seed S] [--device D] [--wave-log waves.jsonl] [--parse-only]\n"); return 2; }
+    if (scene.empty()) { std::fprintf(stderr, "usage: vspg_pbrt scene.pbrt [--spp N] [--outfile image.pfm] [--seed S] [--device D] [--wave-log waves.jsonl] [--parse-only] [--cropwindow x0,x1,y0,y1] [--pixelbounds x0,x1,y0,y1]\n"); return 2; }
     try {
+        if (!cropArg.empty()) vspg::ParseCropWindowArg(cropArg, &film);
+        if (!boundsArg.empty()) vspg::ParsePixelBoundsArg(boundsArg, &film);
         auto sd = vspg::ParseSceneFile(scene);
+        vspg::ResolvePixelBounds(*sd, film);
         if (spp > 0) sd->pixelSamples = spp;
         if (seed >= 0) sd->seed = seed;
         if (!out.empty()) sd->filmFilename = out;
@@ -48,6 +56,7 @@ int main(int argc, char **argv) {
         }
         if (sd->scene.medium.temperature) std::printf("; temperature grid (blackbody emission under \"vspsamplingmethod\" \"nds\")");
         std::printf("\n");
+        std::printf("pixel bounds: [ (%d, %d) - (%d, %d) ]\n", sd->boundsX0, sd->boundsY0, sd->boundsX1, sd->boundsY1);
         if (parseOnly) return 0;
         auto integrator = vspg::CreateIntegrator(*sd, device);
         std::printf("%s\n", integrator->ToString().c_str());

@@ -1,5 +1,6 @@
 // vspg_pbrt_sharded -- one rank of a multi-GPU render of a pbrt scene file, all C++.
 //   RANK=r WORLD_SIZE=N LOCAL_RANK=r [MASTER_PORT=p] vspg_pbrt_sharded scene.pbrt [--spp S] [--outfile image.pfm]
+//                                                    [--cropwindow x0,x1,y0,y1] [--pixelbounds x0,x1,y0,y1]
 // Start N processes (one per GPU of the node) with the same arguments; rank 0 writes the image.  Every step covers N
 // consecutive sample indices, rank r renders index step * N + r; the image-space VSP statistics are summed over the ranks
 // where the buffer updates and the float film at frame end -- both through RCCL (include/vspg_rccl.h).  With N = 1 this is
@@ -16,10 +17,13 @@
 int main(int argc, char **argv) {
     std::string scene, out;
     int spp = -1;
+    std::string cropArg, boundsArg;
     for (int i = 1; i < argc; ++i) {
         const std::string a = argv[i];
         if (a == "--spp" && i + 1 < argc) spp = std::atoi(argv[++i]);
         else if (a == "--outfile" && i + 1 < argc) out = argv[++i];
+        else if (a == "--cropwindow" && i + 1 < argc) cropArg = argv[++i];
+        else if (a == "--pixelbounds" && i + 1 < argc) boundsArg = argv[++i];
         else if (!a.empty() && a[0] == '-') { std::fprintf(stderr, "unknown option %s\n", a.c_str()); return 2; }
         else scene = a;
     }
@@ -29,7 +33,11 @@ int main(int argc, char **argv) {
     VspgRenderer *r = nullptr;
     int code = 0;
     try {
+        vspg::FilmOverrides film;
+        if (!cropArg.empty()) vspg::ParseCropWindowArg(cropArg, &film);
+        if (!boundsArg.empty()) vspg::ParsePixelBoundsArg(boundsArg, &film);
         auto sd = vspg::ParseSceneFile(scene);
+        vspg::ResolvePixelBounds(*sd, film);
         if (spp > 0) sd->pixelSamples = spp;
         if (!out.empty()) sd->filmFilename = out;
         if (sd->integratorName != "guidedvolpathvspg" && sd->integratorName != "guidedvolpath") throw vspg::Error(sd->integratorName + ": integrator type unknown.");
@@ -47,7 +55,7 @@ int main(int argc, char **argv) {
         const int steps = (sd->pixelSamples + world - 1) / world;
         for (int s = 0; s < steps; ++s) {
             const int w0 = s * world, w1 = (s + 1) * world < sd->pixelSamples ? (s + 1) * world : sd->pixelSamples;
-            if (vspg_render_wave(r, w0, w1, nullptr) != 0) throw vspg::Error(vspg_last_error());   // this rank's index of the step
+            if (vspg_render_window(r, sd->boundsX0, sd->boundsY0, sd->boundsX1, sd->boundsY1, w0, w1, nullptr) != 0) throw vspg::Error(vspg_last_error());   // this rank's index of the step
             // the last step of a frame whose sample count is not a multiple of the rank count covers w1 - w0 < world indices
             if (vspg_rccl_post_process_step_n(r, w1 - w0, world, comm, nullptr) != 0) throw vspg::Error(std::string("post-process step: ") + vspg_last_error());
         }
@@ -55,11 +63,9 @@ int main(int argc, char **argv) {
         VspgCounters c;
         if (vspg_rccl_sum_counters(r, comm, nullptr, &c) != 0) throw vspg::Error("counter reduction failed");
         if (rank == 0) {
-            vspg::Film film;
-            film.xres = cfg.xres; film.yres = cfg.yres;
-            film.rgbw.resize((size_t)cfg.xres * cfg.yres * 4);
-            if (vspg_film_read(r, film.rgbw.data(), nullptr) != 0) throw vspg::Error(vspg_last_error());
-            film.WritePFM(sd->filmFilename);
+            std::vector<float> whole((size_t)cfg.xres * cfg.yres * 4);
+            if (vspg_film_read(r, whole.data(), nullptr) != 0) throw vspg::Error(vspg_last_error());
+            vspg::CropFilm(whole, cfg.xres, sd->boundsX0, sd->boundsY0, sd->boundsX1, sd->boundsY1).WritePFM(sd->filmFilename);
             std::printf("ranks %d: paths %llu segments %llu -> %s\n", world, (unsigned long long)c.paths, (unsigned long long)c.segments, sd->filmFilename.c_str());
         }
     } catch (const std::exception &e) {

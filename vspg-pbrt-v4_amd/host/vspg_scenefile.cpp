@@ -8,6 +8,7 @@
 #include <fstream>
 #include <map>
 #include <sstream>
+#include <type_traits>
 
 namespace vspg {
 namespace {
@@ -234,6 +235,8 @@ class Parser {
             sd->xres = p.GetOneInt("xresolution", 1280);
             sd->yres = p.GetOneInt("yresolution", 720);
             sd->filmFilename = p.GetOneString("filename", "pbrt.pfm");
+            sd->cropWindow = p.GetFloatArray("cropwindow");
+            sd->pixelBoundsParam = p.GetIntArray("pixelbounds");   // (resolved once the command line is known: ResolvePixelBounds)
             p.ReportUnused();
         } else if (d == "Integrator") {
             sd->integratorName = str();
@@ -529,7 +532,100 @@ std::unique_ptr<SceneDescription> ParseSceneFile(const std::string &filename) {
     return Parser(ss.str(), slash == std::string::npos ? std::string(".") : filename.substr(0, slash)).run();
 }
 std::unique_ptr<Integrator> CreateIntegrator(const SceneDescription &sd, int device) {
-    return Integrator::Create(sd.integratorName, sd.integratorParams, sd.scene, sd.xres, sd.yres, sd.pixelSamples, sd.seed, device);
+    // the bounds a host resolved with its command line, else the file's own (a throw-away copy takes the warnings)
+    int b[4] = {sd.boundsX0, sd.boundsY0, sd.boundsX1, sd.boundsY1};
+    if (!sd.boundsResolved) {
+        SceneDescription own;
+        own.xres = sd.xres; own.yres = sd.yres; own.cropWindow = sd.cropWindow; own.pixelBoundsParam = sd.pixelBoundsParam;
+        ResolvePixelBounds(own);
+        b[0] = own.boundsX0; b[1] = own.boundsY0; b[2] = own.boundsX1; b[3] = own.boundsY1;
+    }
+    auto integrator = Integrator::Create(sd.integratorName, sd.integratorParams, sd.scene, sd.xres, sd.yres, sd.pixelSamples, sd.seed, device);
+    integrator->SetPixelBounds(b[0], b[1], b[2], b[3]);
+    return integrator;
+}
+
+template <class T>
+static std::vector<T> split_numbers(const std::string &arg, const char *option) {
+    std::vector<T> v;
+    size_t pos = 0;
+    while (pos <= arg.size()) {
+        const size_t comma = std::min(arg.find(',', pos), arg.size());
+        const std::string item = arg.substr(pos, comma - pos);
+        char *end = nullptr;
+        if (std::is_integral<T>::value) {  // (an integer option takes integers: "1.5" is refused, not truncated)
+            const long n = std::strtol(item.c_str(), &end, 10);
+            if (item.empty() || *end != 0) throw Error(std::string(option) + ": \"" + item + "\" is not an integer");
+            v.push_back((T)n);
+        } else {
+            const double d = std::strtod(item.c_str(), &end);
+            if (item.empty() || *end != 0) throw Error(std::string(option) + ": \"" + item + "\" is not a number");
+            v.push_back((T)d);
+        }
+        pos = comma + 1;
+    }
+    return v;
+}
+void ParseCropWindowArg(const std::string &arg, FilmOverrides *o) {
+    const std::vector<float> c = split_numbers<float>(arg, "--cropwindow");
+    if (c.size() != 4) throw Error("Didn't find four values after --cropwindow");  // cmd/pbrt.cpp:134
+    o->haveCropWindow = true;
+    for (int i = 0; i < 4; ++i) o->cropWindow[i] = c[i];
+}
+void ParsePixelBoundsArg(const std::string &arg, FilmOverrides *o) {
+    const std::vector<int> p = split_numbers<int>(arg, "--pixelbounds");
+    if (p.size() != 4) throw Error("Didn't find four integer values after --pixelbounds");  // cmd/pbrt.cpp:150
+    o->havePixelBounds = true;
+    for (int i = 0; i < 4; ++i) o->pixelBounds[i] = p[i];
+}
+
+void ResolvePixelBounds(SceneDescription &sd, const FilmOverrides &o) {
+    const int W = sd.xres, H = sd.yres;
+    int x0 = 0, y0 = 0, x1 = W, y1 = H;  // film.cpp:97: the whole frame
+    // a Bounds2 built from two corners orders them per axis, and Intersect may leave it empty (film.cpp:100-103, 113-117)
+    const auto pixel_bounds = [&](const int pb[4]) {
+        const int bx0 = std::min(pb[0], pb[1]), bx1 = std::max(pb[0], pb[1]), by0 = std::min(pb[2], pb[3]), by1 = std::max(pb[2], pb[3]);
+        x0 = std::max(bx0, 0); x1 = std::min(bx1, W); y0 = std::max(by0, 0); y1 = std::min(by1, H);
+        if (x0 != bx0 || x1 != bx1 || y0 != by0 || y1 != by1) sd.warnings.push_back("Supplied pixel bounds extend beyond image resolution. Clamping.");
+    };
+    // film.cpp:134-137, 157-166: ceil(resolution * crop) in float, corner by corner
+    const auto crop_bounds = [&](float cx0, float cx1, float cy0, float cy1) {
+        x0 = (int)std::ceil((float)W * cx0); y0 = (int)std::ceil((float)H * cy0);
+        x1 = (int)std::ceil((float)W * cx1); y1 = (int)std::ceil((float)H * cy1);
+    };
+    const auto clamp01 = [](float v) { return v < 0.f ? 0.f : (v > 1.f ? 1.f : v); };
+    const bool filePb = !sd.pixelBoundsParam.empty(), fileCrop = !sd.cropWindow.empty();
+    if (o.havePixelBounds) {  // film.cpp:99-108
+        pixel_bounds(o.pixelBounds);
+        if (filePb) sd.warnings.push_back("Pixel bounds supplied on command line will override pixel bounds specified with Film.");
+    } else if (filePb) {      // film.cpp:109-120
+        if (sd.pixelBoundsParam.size() != 4) throw Error(std::to_string(sd.pixelBoundsParam.size()) + " values supplied for \"pixelbounds\". Expected 4.");
+        pixel_bounds(sd.pixelBoundsParam.data());
+    }
+    if (o.haveCropWindow) {   // film.cpp:123-144
+        const float *c = o.cropWindow;
+        const float cx0 = std::min(c[0], c[1]), cx1 = std::max(c[0], c[1]), cy0 = std::min(c[2], c[3]), cy1 = std::max(c[2], c[3]);
+        if (cx0 < 0.f || cx1 > 1.f || cy0 < 0.f || cy1 > 1.f)
+            sd.warnings.push_back("Film crop window is not in [0,1] range; did you mean to use \"pixelbounds\"? Clamping to valid range.");
+        crop_bounds(clamp01(cx0), clamp01(cx1), clamp01(cy0), clamp01(cy1));
+        if (fileCrop) sd.warnings.push_back("Crop window supplied on command line will override crop window specified with Film.");
+        if (o.havePixelBounds || filePb) sd.warnings.push_back("Both pixel bounds and crop window were specified. Using the crop window.");
+    } else if (fileCrop) {    // film.cpp:145-168
+        if (o.havePixelBounds) {
+            sd.warnings.push_back("Ignoring \"cropwindow\" since pixel bounds were specified on the command line.");
+        } else if (sd.cropWindow.size() == 4) {
+            if (filePb) sd.warnings.push_back("Both pixel bounds and crop window were specified. Using the crop window.");
+            const std::vector<float> &c = sd.cropWindow;
+            crop_bounds(clamp01(std::min(c[0], c[1])), clamp01(std::max(c[0], c[1])), clamp01(std::min(c[2], c[3])), clamp01(std::max(c[2], c[3])));
+        } else {
+            throw Error(std::to_string(sd.cropWindow.size()) + " values supplied for \"cropwindow\". Expected 4.");
+        }
+    }
+    if (x1 <= x0 || y1 <= y0)  // film.cpp:170-171
+        throw Error("Degenerate pixel bounds provided to film: [ (" + std::to_string(x0) + ", " + std::to_string(y0) + ") - (" + std::to_string(x1) + ", " +
+                    std::to_string(y1) + ") ].");
+    sd.boundsX0 = x0; sd.boundsY0 = y0; sd.boundsX1 = x1; sd.boundsY1 = y1;
+    sd.boundsResolved = true;
 }
 
 }  // namespace vspg

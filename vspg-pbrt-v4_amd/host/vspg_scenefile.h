@@ -40,8 +40,31 @@ struct SceneDescription {
     int pixelSamples = 16;               // Sampler default
     int seed = 0;
     std::string filmFilename = "pbrt.pfm";
+    // Film "cropwindow" / "pixelbounds" as the file gives them (x0 x1 y0 y1; empty = not given), and the film's pixelBounds
+    // [x0, x1) x [y0, y1) resolved from them by ResolvePixelBounds: all the render loop covers and the written image holds
+    std::vector<float> cropWindow;
+    std::vector<int> pixelBoundsParam;
+    int boundsX0 = 0, boundsY0 = 0, boundsX1 = 1280, boundsY1 = 720;
+    bool boundsResolved = false;         // ResolvePixelBounds has run (the parser only stores the two arrays)
     std::vector<std::string> warnings;   // directives that were accepted and ignored (Option, ColorSpace)
 };
+
+// --cropwindow x0,x1,y0,y1 / --pixelbounds x0,x1,y0,y1 (cmd/pbrt.cpp:132-153): they take precedence over the file's
+struct FilmOverrides {
+    bool haveCropWindow = false, havePixelBounds = false;
+    float cropWindow[4] = {0, 1, 0, 1};   // x0 x1 y0 y1, fractions of the frame
+    int pixelBounds[4] = {0, 0, 0, 0};    // x0 x1 y0 y1, pixels
+};
+// "x0,x1,y0,y1" -> four numbers; throws Error when there are not exactly four
+void ParseCropWindowArg(const std::string &arg, FilmOverrides *o);
+void ParsePixelBoundsArg(const std::string &arg, FilmOverrides *o);
+// The film's pixelBounds by the rules of RGBFilm's base (film.cpp:97-172): the command line over the file, a crop window over
+// pixel bounds; the file's crop window is min/max-ordered and clamped to [0,1], bounds are ceil(resolution * crop) in float;
+// pixel bounds are clamped to the frame with a warning; a wrong value count and empty bounds are errors (vspg::Error).
+// Called ONCE, when the command line is known: with overrides the file's own values are not even examined where the reference
+// does not examine them (a malformed "cropwindow" under --cropwindow is no error, film.cpp:123).  CreateIntegrator resolves the
+// file's own values itself when no host has.
+void ResolvePixelBounds(SceneDescription &sd, const FilmOverrides &overrides = FilmOverrides());
 
 // Parse scene text (the contents of a .pbrt file).  Throws vspg::Error on anything outside the subset above.
 std::unique_ptr<SceneDescription> ParseSceneString(const std::string &text);

@@ -5,12 +5,51 @@ The renderer (C-ABI `shard_index/shard_count`, include/vspg.h) runs wave w iff
 w % world == rank, so handing every rank the SAME global wave range [step*world, (step+1)*world)
 gives each rank exactly one 1-spp wave per step, and the union over ranks covers every sample
 index once.  `torch.distributed` is only the transport (backend "nccl" == RCCL over xGMI on the
-GPU box, "gloo" in the CPU tests)."""
+GPU box, "gloo" in the CPU tests).
+
+Band (pixel) sharding is the other split: every rank renders ALL sample indices of ITS band of rows
+(`window_bands`, `BandShard`, `Renderer.render_window`, renderers created with shard_count = 1) and the same frame-end
+all-reduce adds the bands up.  A pixel then gets all its samples from one rank, in order, and every other
+rank contributes 0 to it: the summed film and the summed image-space statistics are ONE renderer's bit for bit
+(`x + 0 == x`), where sample-index sharding is equal only up to float summation order."""
 
 
 def step_wave_range(step, world):
     """Global wave range every rank passes to render_wave() at `step`."""
     return step * world, (step + 1) * world
+
+
+def window_bands(yres, world):
+    """`world` disjoint row bands [y0, y1) that cover [0, yres) in order, every inner boundary on a multiple of 8 (the path kernels'
+    tile height: no tile is shared by two ranks).  The 8-row groups are dealt out as evenly as they go; with fewer groups than
+    ranks the last bands are empty (y0 == y1) and their ranks render nothing.  No equal-work claim is made: a band's cost
+    follows what its pixels see."""
+    if yres <= 0 or world <= 0:
+        raise ValueError("window_bands: yres and world must be positive")
+    groups = (yres + 7) // 8
+    cuts = [min(yres, 8 * ((groups * k + world - 1) // world)) for k in range(world + 1)]
+    return [(cuts[k], cuts[k + 1]) for k in range(world)]
+
+
+class BandShard:
+    """Band mode: this rank's band of the frame, rendered for ALL sample indices of a step.  The renderer was created with
+    shard_count = 1.  In-loop training of the guiding field is refused, once, here: the field update wants every rank's records,
+    and a band holds only its own (the question costs a host synchronisation, so it is not asked per step; a renderer that is
+    not training does not start to).  `renderer` speaks render_window(x0, y0, x1, y1, w0, w1, stream) and training_stats()."""
+
+    def __init__(self, renderer, xres, yres, rank, world):
+        if not hasattr(renderer, "training_stats") or not hasattr(renderer, "render_window"):
+            raise TypeError("BandShard needs a renderer with render_window() and training_stats()")
+        if renderer.training_stats().get("training"):
+            raise RuntimeError("band sharding does not cover in-loop training of the guiding field (every rank's field would be fitted "
+                               "from its own band's records): upload a trained field, or shard by sample index")
+        self.r, self.xres = renderer, xres
+        self.y0, self.y1 = window_bands(yres, world)[rank]
+
+    def render(self, w0, w1, stream=None):
+        """sample indices [w0, w1) of the band; a rank whose band is empty renders nothing"""
+        if self.y1 > self.y0:
+            self.r.render_window(0, self.y0, self.xres, self.y1, w0, w1, stream)
 
 
 def ordered_after(torch, device, stream, fn):
@@ -94,8 +133,11 @@ class ShardSync:
     isg_update_due(n), post_process_step(n, ptr_or_None, stream), set_exchange(fn).  `wrap(ptr, n)` makes a tensor of the
     transport's kind over memory the renderer owns (default: device memory, for RCCL)."""
 
-    def __init__(self, dist, renderer, world, torch, device=None, wrap=None):
+    def __init__(self, dist, renderer, world, torch, device=None, wrap=None, waves_per_step=None):
         self.dist, self.r, self.world, self.torch, self.device = dist, renderer, world, torch, device
+        # sample indices a step covers: `world` under sample-index sharding (one per rank); under band sharding (BandShard)
+        # whatever the step renders -- every rank renders all of them for its band
+        self.n_waves = world if waves_per_step is None else int(waves_per_step)
         self.wrap = wrap or device_tensor(torch, device)
         self._stats = None
         self._sum = None
@@ -124,10 +166,10 @@ class ShardSync:
 
     def post_process_step(self, stream=None):
         if self.world <= 1:
-            self.r.post_process_step(1, None, stream)
+            self.r.post_process_step(self.n_waves, None, stream)
             return
         total = None
-        if self.r.isg_update_due(self.world):
+        if self.r.isg_update_due(self.n_waves):
             st = self._stats_tensor(stream)
             if self._sum is None:
                 self._sum = self.torch.empty_like(st)
@@ -138,4 +180,4 @@ class ShardSync:
             # the wave that filled `st` ran on `stream`, and the update that reads the sum runs there next
             self._ordered(stream, _sum_over_ranks)
             total = self._sum
-        self.r.post_process_step(self.world, total.data_ptr() if total is not None else None, stream)
+        self.r.post_process_step(self.n_waves, total.data_ptr() if total is not None else None, stream)
