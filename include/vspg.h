@@ -426,7 +426,13 @@ int vspg_renderer_get_arithmetic(VspgRenderer *r);
  * wait for that stream, so what the pointer shows is complete AT THE TIME OF THE CALL.  The pointer VALUE is fixed for the
  * renderer's lifetime, the CONTENTS are not: a host that keeps the pointer across waves (to all-reduce the film or the
  * statistics plane itself) must call vspg_flush(r, stream) -- asynchronous, no host wait -- after the last vspg_render_wave and
- * before it reads through the pointer on `stream` (or on work ordered behind it); a no-op when nothing is parked. */
+ * before it reads through the pointer on `stream` (or on work ordered behind it); a no-op when nothing is parked.
+ * The same contract covers PATHS: a one-sample wave of the barrier-free workgroup kernel may also leave the paths that were in flight
+ * when its tiles ran out suspended beside the film; the next such wave resumes them, and until then the film, the statistics and
+ * the counters lack them as well as the parked samples.  vspg_flush and every accessor named above -- and vspg_get_counters,
+ * vspg_reset_counters, vspg_renderer_set_arithmetic, the buffer setters, the due update of vspg_post_process_step -- finish them
+ * first (one short launch on the call's stream); vspg_renderer_destroy drops them.  VSPG_WG3_CARRY=0 in the environment (read
+ * per wave) makes every wave finish its own paths. */
 int vspg_flush(VspgRenderer *r, void *stream);
 int vspg_film_device_ptr(VspgRenderer *r, float **dev_ptr, size_t *n_floats);
 int vspg_film_read(VspgRenderer *r, float *host_rgbw /* W*H*4 */, void *stream);

@@ -1375,7 +1375,9 @@ __global__ __launch_bounds__(kBlock) void k_film_resolve(int W, PixelWindow win,
     const size_t ww = (size_t)(win.x1 - win.x0);
     if (j >= ww * (size_t)(win.y1 - win.y0)) return;
     const size_t i = ((size_t)win.y0 + j / ww) * (size_t)W + (size_t)win.x0 + j % ww;
-    resolve_sample(wave_samples[i], film + i, isg_stats + i * VSPG_ISG_STATS);
+    const float4 parked = wave_samples[i];
+    if (carry_sentinel(parked.w)) return;  // (a path still in flight, vspg_wg3.h CARRY: none is left behind the drain that runs before this kernel)
+    resolve_sample(parked, film + i, isg_stats + i * VSPG_ISG_STATS);
 }
 
 // (k_trace_paths: vspg_trace.h)
@@ -1712,6 +1714,15 @@ struct VspgRenderer {
     PixelWindow ws_win = {0, 0, 0, 0};  // the window of the launch that parked them (vspg_render_window)
     hipStream_t ws_stream = nullptr;  // the stream of the launch that parked them
     hipEvent_t ws_event = nullptr;    // recorded behind that launch: whoever touches the parked samples on another stream waits on it
+    // k_render_wave_wg3_carry (vspg_wg3.h, CARRY): the paths a one-sample launch left in flight, one image per workgroup.  The next launch
+    // of the same shape resumes them; anything else drains them first (drain_carried_paths, through flush_parked_samples).  Two
+    // buffers like the sample planes: a launch resumes from the one its predecessor suspended into and suspends into the other.
+    unsigned int *carry_img[2] = {nullptr, nullptr};
+    int carry_cur = 0;
+    bool carry_pending = false;
+    Wg3Launch carry_shape = {};       // the launch that wrote the pending image: instantiation, grid, window
+    int carry_arith = 0;              // ... and its arithmetic mode
+    unsigned long long carry_resumes = 0;  // launches that resumed from an image (vspg_debug_carry_resumes)
     unsigned int *wf_lists = nullptr;   // 4 x n_items: active (even / odd iterations), walk, shadow
     hipStream_t wf_stream2 = nullptr;   // the shadow walks' stream (wf_render_pass)
     hipEvent_t wf_ev_vertex = nullptr, wf_ev_shadow = nullptr;
@@ -3090,6 +3101,7 @@ int vspg_renderer_destroy(VspgRenderer *r) {
     if (r->bvh) (void)hipFree(r->bvh);
     for (int k = 0; k < 2; ++k) if (r->wave_samples[k]) (void)hipFree(r->wave_samples[k]);
     if (r->ws_event) (void)hipEventDestroy(r->ws_event);
+    for (int k = 0; k < 2; ++k) if (r->carry_img[k]) (void)hipFree(r->carry_img[k]);  // (paths still in flight end with their renderer)
     if (r->wf_pool) (void)hipFree(r->wf_pool);
     if (r->wf_lists) (void)hipFree(r->wf_lists);
     if (r->wf_iters) (void)hipFree(r->wf_iters);
@@ -3219,7 +3231,40 @@ static int order_after_parking(VspgRenderer *r, hipStream_t s) {
     if (r->ws_parked && r->ws_event && s != r->ws_stream) HIPCHK(hipStreamWaitEvent(s, r->ws_event, 0));
     return 0;
 }
+// One-sample launches of k_render_wave_wg3 carry their in-flight paths into the next launch (VSPG_WG3_CARRY=0: every launch drains
+// its own, today's kernel; so does VSPG_WG2_DEFER=0 -- nothing is carried where nothing is parked).
+static bool wg3_carry_enabled() {  // (read per launch: a test flips it)
+    const char *e = getenv("VSPG_WG3_CARRY");
+    return !(e && e[0] == '0') && wg2_defer_enabled();
+}
+static int wg3_launch_any(int arith, const Wg3Launch &L) {
+    return arith == VSPG_ARITH_FAST_WEIGHTS ? vspg_arith1_wg3(&L) : arith == VSPG_ARITH_FAST ? vspg_arith2_wg3(&L) : wg3_launch_exact(L);
+}
+// The drain: the pending image's paths run to their ends in a launch of the shape that suspended them -- no tiles, nothing suspended.
+// Each parks its sample over its pixel's sentinel: behind it the renderer is where a self-contained launch would have left it.
+static int drain_carried_paths(VspgRenderer *r, hipStream_t s) {
+    if (!r->carry_pending) return 0;
+    if (const int rc = order_after_parking(r, s)) return rc;
+    Wg3Launch L = r->carry_shape;
+    L.vsp_ready = r->vsp_ready;
+    L.first_sample = -1;  // (no path of this launch: every resumed one is an old one)
+    L.work_head = r->work_head8 + (r->head8_parity & 1u) * (unsigned)(kWg3HeadSetBytes / 4);  // (claims nothing; the next launch's set stays zero)
+    L.ws_prev = nullptr;
+    L.ws_out = r->wave_samples[r->ws_cur ^ 1];
+    L.stream = s;
+    L.carry = 1;
+    L.resume = r->carry_img[r->carry_cur ^ 1];
+    L.suspend = nullptr;
+    const int lrc = wg3_launch_any(r->carry_arith, L);
+    if (lrc != 0) return fail(VSPG_EHIP, std::string("k_render_wave_wg3_carry (drain): ") + hipGetErrorName((hipError_t)lrc));
+    r->carry_pending = false;
+    // (the parked plane is complete behind THIS launch now: whoever touches it on another stream waits on it)
+    r->ws_stream = s;
+    if (r->ws_event) HIPCHK(hipEventRecord(r->ws_event, s));
+    return 0;
+}
 static int flush_parked_samples(VspgRenderer *r, hipStream_t s) {
+    if (const int rc = drain_carried_paths(r, s)) return rc;
     if (!r->ws_parked) return 0;
     if (const int rc = order_after_parking(r, s)) return rc;
     const size_t n_win = (size_t)(r->ws_win.x1 - r->ws_win.x0) * (size_t)(r->ws_win.y1 - r->ws_win.y0);
@@ -3245,6 +3290,10 @@ int vspg_renderer_set_arithmetic(VspgRenderer *r, int mode) {
     if (mode != VSPG_ARITH_EXACT && !arith_covered(r))
         return fail(VSPG_ESCOPE, "the tolerance-mode instantiations cover unguided renders of rectangle scenes over a homogeneous medium and unguided "
                                  "\"resampling\" renders over a uniformgrid medium (this renderer runs " + std::string(kernel_name_exact(r)) + ")");
+    if (mode != r->arith && r->carry_pending) {  // (paths in flight end in the arithmetic they started in)
+        HIPCHK(hipSetDevice(r->cfg.device));
+        if (const int rc = drain_carried_paths(r, r->ws_stream)) return rc;
+    }
     r->arith = mode;
     return 0;
 }
@@ -3345,6 +3394,10 @@ int vspg_render_window(VspgRenderer *r, int x0, int y0, int x1, int y1, int wave
     const bool defer = !uses_wf_pipeline(r) && uses_wg2(r) && n_samples == 1 && wg2_defer_enabled();
     const bool same_win = r->ws_win.x0 == x0 && r->ws_win.y0 == y0 && r->ws_win.x1 == x1 && r->ws_win.y1 == y1;
     if (!defer || !same_win) { const int rc = flush_parked_samples(r, (hipStream_t)stream); if (rc) return rc; }
+    // ... and a k_render_wave_wg3 launch of that kind also takes over the paths its predecessor left in flight (below); any other drains them
+    // (not where the paths themselves keep a per-pixel running mean, the TrBuffer's: two samples of a pixel would be in flight at once)
+    const bool carry = defer && uses_wg3(r) && !r->hscene.tr_calc && wg3_carry_enabled();
+    if (r->carry_pending && !carry) { const int rc = drain_carried_paths(r, (hipStream_t)stream); if (rc) return rc; }
     if (uses_wf_pipeline(r)) {  // one pass per sample index of this shard, in order
 #ifdef VSPG_WF_DEBUG
         auto checksum = [&](const void *dptr, size_t bytes) -> unsigned long long {
@@ -3416,16 +3469,27 @@ int vspg_render_window(VspgRenderer *r, int x0, int y0, int x1, int y1, int wave
         const long long wmax = (items + kWgChunk - 1) / kWgChunk;
         if (wblocks > wmax) wblocks = wmax;
         const int single = n_samples == 1 ? 1 : 0;
+        const long long n_tiles_all = (long long)tilesX * tilesY;
         // Two schedulers (uses_wg2): k_render_wave_wg2 (tiles from a global head, parked samples, two barriers) by default,
         // k_render_wave_wg (film flush between the phases, three barriers) for grid media and under VSPG_WG_SCHED=1.
         const bool sched2 = uses_wg2(r);
         if (sched2) {
             for (int k = 0; k < 2; ++k)
                 if (!r->wave_samples[k]) HIPCHK(hipMalloc(&r->wave_samples[k], r->npix * sizeof(float4)));
+            // CARRY (vspg_wg3.h): the pending image is resumed by a launch of the shape that wrote it, whose sample index differs from
+            // the suspended paths' (that is how the kernel tells them apart); otherwise it is drained first
+            const int wg3_grey = r->medium_grey ? (r->surfaces_grey ? 2 : 1) : 0, wg3_null_zero = r->medium_grey && r->surfaces_grey && r->null_zero ? 1 : 0;
+            if (carry && wblocks > n_tiles_all) wblocks = n_tiles_all;
+            if (r->carry_pending) {
+                const Wg3Launch &P = r->carry_shape;
+                const bool same_shape = carry && P.grey == wg3_grey && P.null_zero == wg3_null_zero && P.blocks == (unsigned)wblocks && P.windowed == (whole ? 0 : 1) &&
+                                        r->carry_arith == r->arith && P.first_sample != first && P.dscene == r->dscene;
+                if (!same_shape) { const int rc = drain_carried_paths(r, (hipStream_t)stream); if (rc) return rc; }
+            }
             float4 *const ws_out = r->wave_samples[r->ws_cur];
             const float4 *const ws_prev = defer && r->ws_parked ? r->wave_samples[r->ws_cur ^ 1] : nullptr;
             if (ws_prev) { const int rc = order_after_parking(r, (hipStream_t)stream); if (rc) return rc; }
-            const long long n_tiles = (long long)tilesX * tilesY;
+            const long long n_tiles = n_tiles_all;
             if (wblocks > n_tiles) wblocks = n_tiles;
             // the share of the frame handed out from the global head, in 64ths (VSPG_WG2_TAIL; the rest is dealt to the workgroups
             // up front, interleaved).  Measured on the reference-default guided workload / the unguided one (ms per 1080p wave):
@@ -3442,11 +3506,26 @@ int vspg_render_window(VspgRenderer *r, int x0, int y0, int x1, int y1, int wave
                     unsigned int *const head8 = r->work_head8 + (r->head8_parity & 1u) * (unsigned)(kWg3HeadSetBytes / 4);
                     r->head8_parity ^= 1u;
                     r->head_parity ^= 1u;  // (undo the toggle above: no launch used that pair)
-                    const Wg3Launch L3{r->dscene, r->film, r->isg_stats, r->vsp, r->vsp_ready, wave_end, first, single, jump, tiles_magic, head8, ws_prev, ws_out,
-                                       r->counters, (unsigned)wblocks, (hipStream_t)stream, r->medium_grey ? (r->surfaces_grey ? 2 : 1) : 0,
-                                       r->medium_grey && r->surfaces_grey && r->null_zero ? 1 : 0, whole ? 0 : 1, win};
-                    const int lrc = r->arith == VSPG_ARITH_FAST_WEIGHTS ? vspg_arith1_wg3(&L3) : r->arith == VSPG_ARITH_FAST ? vspg_arith2_wg3(&L3) : wg3_launch_exact(L3);
+                    Wg3Launch L3{r->dscene, r->film, r->isg_stats, r->vsp, r->vsp_ready, wave_end, first, single, jump, tiles_magic, head8, ws_prev, ws_out,
+                                 r->counters, (unsigned)wblocks, (hipStream_t)stream, wg3_grey, wg3_null_zero, whole ? 0 : 1, win, 0, nullptr, nullptr};
+                    if (carry) {
+                        // (an image per workgroup of the largest grid a launch of this renderer can have, at the largest instantiation's size)
+                        const size_t img_bytes = (size_t)r->num_cus * (size_t)(kWgWavesHomog * 4 / (kWgBlockHomog / 64)) * (size_t)kWg3ImageStrideMax * sizeof(unsigned int);
+                        for (int k = 0; k < 2; ++k)
+                            if (!r->carry_img[k]) HIPCHK(hipMalloc(&r->carry_img[k], img_bytes));
+                        L3.carry = 1;
+                        L3.resume = r->carry_pending ? r->carry_img[r->carry_cur ^ 1] : nullptr;
+                        L3.suspend = r->carry_img[r->carry_cur];
+                    }
+                    const int lrc = wg3_launch_any(r->arith, L3);
                     if (lrc != 0) return fail(VSPG_EHIP, std::string("k_render_wave_wg3: ") + hipGetErrorName((hipError_t)lrc));
+                    if (carry) {
+                        if (r->carry_pending) r->carry_resumes++;
+                        r->carry_cur ^= 1;
+                        r->carry_pending = true;
+                        r->carry_shape = L3;
+                        r->carry_arith = r->arith;
+                    }
                 }
             } else
             if (gwg && train && guided_grey_simple(r))
@@ -3644,6 +3723,8 @@ int vspg_flush(VspgRenderer *r, void *stream) {
     HIPCHK(hipSetDevice(r->cfg.device));
     return flush_parked_samples(r, (hipStream_t)stream);
 }
+// how many launches of this renderer resumed paths their predecessor left in flight (tests: the carry path was taken)
+long long vspg_debug_carry_resumes(VspgRenderer *r) { return r ? (long long)r->carry_resumes : -1; }
 int vspg_film_device_ptr(VspgRenderer *r, float **dev_ptr, size_t *n_floats) {
     if (!r || !dev_ptr || !n_floats) return fail(VSPG_EINVAL, "null argument");
     if (r->ws_parked) {  // the caller reads the film on a stream of its own: the parked samples go in, and are in, before it gets the pointer
@@ -3702,6 +3783,7 @@ int vspg_renderer_set_tr_buffer(VspgRenderer *r, const float *host_rgb, void *st
     if (!r || !host_rgb) return fail(VSPG_EINVAL, "null argument");
     HIPCHK(hipSetDevice(r->cfg.device));
     hipStream_t s = (hipStream_t)stream;
+    if (const int rc = flush_parked_samples(r, s)) return rc;  // (paths in flight end under the scene they started in)
     if (!r->tr_rgb) HIPCHK(hipMalloc(&r->tr_rgb, r->npix * 3 * sizeof(float)));
     HIPCHK(hipMemcpyAsync(r->tr_rgb, host_rgb, r->npix * 3 * sizeof(float), hipMemcpyHostToDevice, s));
     // trBufferLoad = true, calculateTrBuffer = false (:182-184).  Only these members are rewritten: the field
@@ -3717,6 +3799,7 @@ int vspg_renderer_set_tr_buffer(VspgRenderer *r, const float *host_rgb, void *st
 int vspg_vsp_buffer_load(VspgRenderer *r, const float *host, void *stream) {
     if (!r || !host) return fail(VSPG_EINVAL, "null argument");
     HIPCHK(hipSetDevice(r->cfg.device));
+    if (const int rc = flush_parked_samples(r, (hipStream_t)stream)) return rc;  // (paths in flight end under the buffer they started with)
     HIPCHK(hipMemcpyAsync(r->vsp, host, r->npix * sizeof(float), hipMemcpyHostToDevice, (hipStream_t)stream));
     HIPCHK(hipStreamSynchronize((hipStream_t)stream));
     r->vsp_ready = 1;
@@ -3738,6 +3821,7 @@ int vspg_isg_stats_device_ptr(VspgRenderer *r, float **dev_ptr, size_t *n_floats
 int vspg_get_counters(VspgRenderer *r, VspgCounters *out, void *stream) {
     if (!r || !out) return fail(VSPG_EINVAL, "null argument");
     HIPCHK(hipSetDevice(r->cfg.device));
+    if (const int rc = drain_carried_paths(r, (hipStream_t)stream)) return rc;  // (the counters of paths in flight: they end first)
     unsigned long long h[kNumCounters];
     HIPCHK(hipMemcpyAsync(h, r->counters, sizeof h, hipMemcpyDeviceToHost, (hipStream_t)stream));
     HIPCHK(hipStreamSynchronize((hipStream_t)stream));
@@ -3749,6 +3833,7 @@ int vspg_get_counters(VspgRenderer *r, VspgCounters *out, void *stream) {
 int vspg_reset_counters(VspgRenderer *r, void *stream) {
     if (!r) return fail(VSPG_EINVAL, "null renderer");
     HIPCHK(hipSetDevice(r->cfg.device));
+    if (const int rc = drain_carried_paths(r, (hipStream_t)stream)) return rc;  // (... and are counted before the reset)
     HIPCHK(hipMemsetAsync(r->counters, 0, kNumCounters * sizeof(unsigned long long), (hipStream_t)stream));
     return 0;
 }
@@ -3900,6 +3985,7 @@ int vspg_renderer_set_guiding_field(VspgRenderer *r, const VspgField *surface_fi
     if (!r) return fail(VSPG_EINVAL, "null renderer");
     HIPCHK(hipSetDevice(r->cfg.device));
     hipStream_t s = (hipStream_t)stream;
+    if (const int frc = flush_parked_samples(r, s)) return frc;  // (paths in flight end under the scene record they started with)
     HIPCHK(hipStreamSynchronize(s));  // no launch may still read the old field
     r->training = false;                // a loaded cache is not trained further (:117-122)
     int rc = upload_field(r, 0, surface_field, s);

@@ -38,6 +38,10 @@ VSPG_NS_BEGIN
 enum { Q_VV = 0, Q_VS = 1, Q_A = 2, Q_F = 3, Q_COUNT = 4 };
 enum { QC_RES = 0, QC_COM = 1, QC_HEAD = 2, QC_STRIDE = 4 };
 enum { W3_BUSY_S = Q_COUNT * QC_STRIDE, W3_BUSY_V, W3_EXH, W3_LIVE, W3_COUNT };  // (one 16-byte group behind the queues')
+// CARRY, the spare words of the queue groups: resumed paths still in flight (+ kCarryDrainBit in a launch that suspends nothing: the
+// word then never reads 0), and the suspend buffer's address -- parked in LDS over the persistent loop, whose SGPRs are all spoken for
+enum { W3_OLD = Q_VV * QC_STRIDE + 3, W3_SUSP_LO = Q_VS * QC_STRIDE + 3, W3_SUSP_HI = Q_A * QC_STRIDE + 3 };
+constexpr unsigned kCarryDrainBit = 0x80000000u;
 enum { W3_NONE = 0, W3_VERTEX = 1, W3_SEGMENT = 2, W3_FRESH = 3, W3_EXIT = 4 };
 constexpr unsigned kRestartBit = 0x8000u;
 
@@ -75,6 +79,35 @@ __device__ __forceinline__ int w3_lane() {
     asm volatile("" : "+v"(l));
     return l;
 }
+// ---- CARRY: in-flight paths cross the boundary between two one-sample launches -----------------------------------------------
+// A self-contained launch ends with every workgroup draining its pool through ever thinner chunks on a chip that empties
+// (profiles/carry_drain_profile.txt: the last exit comes ~118 us after the median wavefront sees the cursors dry, of a 639 us
+// launch), and the next one starts from empty pools.  In CARRY mode (k_render_wave_wg3_carry, launched by vspg_render_window where
+// the deferred resolve applies) a workgroup whose cursors are dry SUSPENDS instead: it writes pool, rings and queue words -- its
+// image -- to global memory, and the same workgroup of the next launch RESUMES from it, with a full pool and the scheduler's state as
+// it was.  The contract is the parked samples': nothing reads the film between two such launches; whoever does drains first
+// (vspg_capi.hip: drain_carried_paths, a CARRY launch without tiles and without a suspend buffer; flush_parked_samples runs it first).
+//   * a resumed path is told by its sample index (SAMPLE != first_sample); when it ends it adds its sample to the film and the
+//     statistics itself (resolve_sample) and lowers `old_live`.  In the drain launch (first_sample < 0) it PARKS the sample
+//     instead, over its pixel's sentinel: what the drain leaves is the state a self-contained launch leaves, parked samples and
+//     nothing else, for whoever resolves them next;
+//   * for every path it suspends, a workgroup writes kCarrySentinel into the pixel's entry of this launch's wave_samples plane: the
+//     next launch does not resolve that entry at the start of the pixel (k_film_resolve skips it too) -- the resumed path will.
+//     So sample N of a pixel enters the film in launch N + 1 either way, once, and sample N + 1 no earlier than launch N + 2: the
+//     additions per pixel keep their order and the film its bits;
+//   * a workgroup suspends only once `old_live` is 0 (until then it serves every queue as ever): a path is carried at most once,
+//     whatever the frame size, and every slot in flight at the suspension belongs to this launch.
+// The free ring and the claimed-unread hazard (see the FRESH claim below): a resumed ring is no longer "full from index 0", it is a
+// ring on a later lap, which the same argument already covers -- the claimed entries are read right behind the CAS, and a sibling
+// would have to claim, run a chunk and push within those few instructions.  The queue words are rebased on resume (HEAD < NP), so
+// ring positions never come near 2^32 however many launches pass between two drains.
+constexpr float kCarrySentinel = 2.f;  // (a legal ISG code lies in [-0.999, 0.999])
+__device__ __forceinline__ bool carry_sentinel(float w) { return w > 1.f; }
+template <class LY, int NP> constexpr int kWg3ImagePool = LY::COUNT * NP;                 // dwords: the pool,
+template <class LY, int NP> constexpr int kWg3ImageWords = LY::COUNT * NP + Q_COUNT * NP / 2;  // ... the four rings, then the queue words
+template <class LY, int NP> constexpr int kWg3ImageStride = kWg3ImageWords<LY, NP> + 32;  // per workgroup
+static_assert(W3_COUNT <= 32, "the image's queue words");
+
 constexpr int kWg3Heads = 8, kWg3HeadSetBytes = kWg3Heads * 128;  // k_render_wave_wg3's tile cursors (see the kernel)
 // The global work head is a PAIR of counters used by alternate launches: a launch zeroes the one the NEXT launch will use
 // (nobody reads it meanwhile, launches of a renderer are stream-ordered), so no memset sits between two waves.
@@ -128,24 +161,55 @@ constexpr int wg3_pool_paths(int other_bytes) {
     return n < VSPG_WG3_NP_CAP ? n : VSPG_WG3_NP_CAP;
 }
 
+// Diagnostic build only (-DVSPG_W3_TIMELINE, csrc/Makefile target `timeline`; scripts/carry_drain_profile.py reads it): per wavefront
+// of the last launch, 100 MHz stamps of {loop entry, first full vertex chunk, cursors first seen dry, exit} and, for each of the three
+// phases these stamps bound (ramp, steady, drain) and each chunk kind (vertex, segment, fresh), {chunks, lanes, ticks in chunks}.
+// The shipped library contains none of this.
+#ifdef VSPG_W3_TIMELINE
+enum { W3T_BEGIN = 0, W3T_FULL, W3T_EXH, W3T_EXIT, W3T_SUMS, W3T_WORDS = W3T_SUMS + 27, W3T_MAX_BLOCKS = 2048 };
+__device__ unsigned long long g_w3_timeline[W3T_MAX_BLOCKS][8][32];
+struct W3Timeline {
+    unsigned long long *rec, t0;
+    unsigned phase;
+    __device__ __forceinline__ bool mine() const { return (threadIdx.x & 63u) == 0u && blockIdx.x < (unsigned)W3T_MAX_BLOCKS; }
+    __device__ __forceinline__ W3Timeline() : rec(&g_w3_timeline[blockIdx.x % W3T_MAX_BLOCKS][(threadIdx.x >> 6) & 7u][0]), t0(0), phase(0) { stamp(W3T_BEGIN); }
+    __device__ __forceinline__ void stamp(int i) { const unsigned long long t = __builtin_amdgcn_s_memrealtime(); if (mine()) rec[i] = t; }
+    __device__ __forceinline__ void enter(unsigned p, int i) { if (phase < p) { phase = p; stamp(i); } }
+    __device__ __forceinline__ void chunk_begin() { t0 = __builtin_amdgcn_s_memrealtime(); }
+    __device__ __forceinline__ void chunk_end(unsigned kind, unsigned lanes) {
+        const unsigned long long t1 = __builtin_amdgcn_s_memrealtime();
+        if (mine()) {
+            unsigned long long *r = rec + W3T_SUMS + (phase * 3u + kind) * 3u;
+            atomicAdd(r, 1ull); atomicAdd(r + 1, (unsigned long long)lanes); atomicAdd(r + 2, t1 - t0);
+        }
+    }
+};
+#define VSPG_W3T(x) x
+#else
+#define VSPG_W3T(x)
+#endif
+
 // The kernel's body.  WINDOW: the launch covers the pixel window `win` (vspg_render_window) instead of the frame.  The 8x8 tile grid stays
 // anchored to the frame; the launch enumerates the tile rectangle that covers the window (tile index -> window-local row / column, plus
 // the rectangle's origin) and masks the lanes outside the window the way the full-frame launch masks lanes past W / H.  The full-frame
 // instantiation takes none of it: `win` is unused there and its code is what it was (it is pinned at its SGPR limit and within five
 // selects / compares of its ceiling, tests/test_headline_kernel_census.py).
-template <class Medium, bool GUIDED, int NP, int kWgBlock, int kWgWavesPerSimd, bool TRAIN, bool WINDOW>
+template <class Medium, bool GUIDED, int NP, int kWgBlock, int kWgWavesPerSimd, bool TRAIN, bool WINDOW, bool CARRY = false>
 __device__ __forceinline__ void wg3_render(
     const DScene *__restrict__ Sp, float4 *__restrict__ film, float *__restrict__ isg_stats, const float *__restrict__ vsp_buf,
     int vsp_ready, int wave_end, int first_sample, int single_sample, PcgJump jump, unsigned int tiles_magic,
     unsigned int *__restrict__ work_head, const float4 *__restrict__ prev_samples,
-    float4 *__restrict__ wave_samples, unsigned long long *__restrict__ counters, TrainArgs train, const PixelWindow win) {
+    float4 *__restrict__ wave_samples, unsigned long long *__restrict__ counters, TrainArgs train, const PixelWindow win,
+    const unsigned int *__restrict__ resume = nullptr, unsigned int *__restrict__ suspend = nullptr) {
+    static_assert(!CARRY || (!TRAIN && !GUIDED), "CARRY serves the unguided one-sample launches");
     // (each argument its own register from here on: the four ints arrive as one 128-bit load, and a tuple is spilled as a unit)
     vsp_ready = w3_at_use(vsp_ready), wave_end = w3_at_use(wave_end), first_sample = w3_at_use(first_sample);
     single_sample = w3_at_use(single_sample);
     const DScene &S = *Sp;
     const int W = S.xres, H = S.yres;
     const int tilesX = WINDOW ? win_tiles_x(win) : (W + 7) >> 3, tilesY = WINDOW ? win_tiles_y(win) : (H + 7) >> 3;
-    const unsigned n_tiles = (unsigned)(tilesX * tilesY);
+    // (CARRY without a suspend buffer is the drain launch: no tiles, the resumed paths run to their ends)
+    const unsigned n_tiles = CARRY && w3_at_use(suspend) == nullptr ? 0u : (unsigned)(tilesX * tilesY);
     // is pixel (px, py) of a claimed tile part of the launch?  (tile padding past the frame / outside the window)
     const auto in_launch = [&](int px, int py) {
         if constexpr (WINDOW) return win_has(win, px, py);
@@ -209,17 +273,67 @@ __device__ __forceinline__ void wg3_render(
 
     stage_scene_lds(S);
     if (threadIdx.x < CNT_COUNT) s_counters[threadIdx.x] = 0;
-    if (threadIdx.x < W3_COUNT) s_w[threadIdx.x] = 0;
-    for (int i = threadIdx.x; i < NP; i += kWgBlock) s_ring[Q_F][i] = (unsigned short)i;
-    __syncthreads();
-    if (threadIdx.x == 0) { s_w[Q_F * QC_STRIDE + QC_RES] = NP; s_w[Q_F * QC_STRIDE + QC_COM] = NP; }
+    constexpr int kImgPool = kWg3ImagePool<LY, NP>, kImgWords = kWg3ImageWords<LY, NP>, kImgStride = kWg3ImageStride<LY, NP>;
+    bool resumed = false;
+    if constexpr (CARRY) {
+        // RESUME: the workgroup's image of the previous launch, verbatim, if it holds paths
+        const unsigned int *const img = resume + (size_t)blockIdx.x * kImgStride;
+        resumed = resume != nullptr && img[kImgWords + W3_LIVE] != 0u;
+        if (resumed) {
+            unsigned int *const pool32 = reinterpret_cast<unsigned int *>(s_pool);
+#pragma unroll 8
+            for (int i = threadIdx.x; i < kImgPool; i += kWgBlock) pool32[i] = img[i];
+            unsigned short *const ring16 = &s_ring[0][0];
+#pragma unroll 3
+            for (int i = threadIdx.x; i < Q_COUNT * NP / 2; i += kWgBlock) {
+                const unsigned v = img[kImgPool + i];
+                ring16[2 * i] = (unsigned short)(v & 0xffffu);
+                ring16[2 * i + 1] = (unsigned short)(v >> 16);
+            }
+            if (threadIdx.x < W3_COUNT) s_w[threadIdx.x] = img[kImgWords + threadIdx.x];
+            __syncthreads();
+            // what belongs to the launch: every resumed path is an old one, the cursors are this launch's (a drain launch has none),
+            // no chunk is in flight; ring positions rebased below NP
+            if (threadIdx.x < Q_COUNT) {
+                const unsigned h = s_w[threadIdx.x * QC_STRIDE + QC_HEAD], n = s_w[threadIdx.x * QC_STRIDE + QC_COM] - h, h2 = h % (unsigned)NP;
+                s_w[threadIdx.x * QC_STRIDE + QC_HEAD] = h2;
+                s_w[threadIdx.x * QC_STRIDE + QC_RES] = h2 + n;
+                s_w[threadIdx.x * QC_STRIDE + QC_COM] = h2 + n;
+            }
+            if (threadIdx.x == 0) {
+                s_w[W3_OLD] = s_w[W3_LIVE];
+                s_w[W3_EXH] = 0u;
+                s_w[W3_BUSY_S] = 0u;
+                s_w[W3_BUSY_V] = 0u;
+            }
+        }
+    }
+    if (!resumed) {
+        if (threadIdx.x < W3_COUNT) s_w[threadIdx.x] = 0;
+        for (int i = threadIdx.x; i < NP; i += kWgBlock) s_ring[Q_F][i] = (unsigned short)i;
+        __syncthreads();
+        if (threadIdx.x == 0) {
+            s_w[Q_F * QC_STRIDE + QC_RES] = NP; s_w[Q_F * QC_STRIDE + QC_COM] = NP;
+        }
+    }
+    if constexpr (CARRY) {
+        __syncthreads();
+        if (threadIdx.x == 0) {
+            if (suspend == nullptr) { s_w[W3_EXH] = 1u; s_w[W3_OLD] |= kCarryDrainBit; }  // the drain launch: no tiles, nothing suspended
+            s_w[W3_SUSP_LO] = (unsigned)reinterpret_cast<uintptr_t>(suspend);
+            s_w[W3_SUSP_HI] = (unsigned)(reinterpret_cast<uintptr_t>(suspend) >> 32);
+        }
+    }
     __syncthreads();
 
     // a path ends: its sample leaves the kernel
-    auto emit = [&](int pxy, Spec Lraw, const IsgSample &isg) {
+    // (CARRY, `old`: a resumed path -- its sample goes where the next launch would have put it, see the header)
+    auto emit = [&](int pxy, Spec Lraw, const IsgSample &isg, bool old) {
         const Spec L = finish_radiance(Lraw);
         const size_t pidx = (size_t)((unsigned)pxy >> 16) * W + (pxy & 0xffff);
-        if (w3_at_use(single_sample)) {
+        if (CARRY && old && w3_at_use(first_sample) >= 0) {
+            resolve_sample(make_float4(L.r, L.g, L.b, isg_code(isg)), film + pidx, isg_stats + pidx * VSPG_ISG_STATS);
+        } else if (w3_at_use(single_sample)) {
             wave_samples[pidx] = make_float4(L.r, L.g, L.b, isg_code(isg));
         } else {
             film_add_sample(film + pidx, L);
@@ -231,6 +345,7 @@ __device__ __forceinline__ void wg3_render(
     VSPG_PROF_ACC(prof_decide, PS_WG_R);      // diagnostic build: the scheduler (decisions that found a chunk)
     VSPG_PROF_ACC(prof_idle, PS_WG_BAR_A);    // ... and the polls that found none, the sleep included
     unsigned idle_polls = 0;
+    VSPG_W3T(W3Timeline tl);
     while (true) {
         VSPG_PROF_ACC_BEGIN(prof_decide);
         VSPG_PROF_ACC_BEGIN(prof_idle);
@@ -247,7 +362,9 @@ __device__ __forceinline__ void wg3_render(
             const w3_u32x4 wVV = qw[Q_VV], wVS = qw[Q_VS], wA = qw[Q_A], wF = qw[Q_F], wM = qw[Q_COUNT];
             const unsigned hVV = U(wVV.z), hVS = U(wVS.z), hA = U(wA.z), hF = U(wF.z);
             const unsigned busyS = U(wM.x), busyV = U(wM.y), live = U(wM.w);
+            const unsigned old_word = CARRY ? U(wVV.w) : 1u;
             const bool exh = U(wM.z) != 0u;
+            VSPG_W3T(if (exh) tl.enter(2u, W3T_EXH));
             const auto avail = [&](w3_u32x4 q, unsigned head) {  // committed entries nobody has claimed; 0 while a push is between its reservation and its commit
                 const unsigned r = U(q.x), c = U(q.y);
                 const int a = (int)(c - head);
@@ -279,7 +396,9 @@ __device__ __forceinline__ void wg3_render(
                 else bump(W3_BUSY_S, -1);
             };
             const int aV = aVV + aVS;
-            if (aVV >= 64) claim_vertex(aVV, hVV, Q_VV, 0, hVS, Q_VS);
+            // CARRY: the cursors are dry and every resumed path has ended -- the workgroup suspends what it holds (behind the loop)
+            if (CARRY && exh && old_word == 0u) kind = W3_EXIT;
+            else if (aVV >= 64) claim_vertex(aVV, hVV, Q_VV, 0, hVS, Q_VS);
             else if (aVS >= 64) claim_vertex(aVS, hVS, Q_VS, 0, hVV, Q_VV);
             else if (aA >= 64) claim_segment();
             else if (aF >= 64) {
@@ -335,12 +454,13 @@ __device__ __forceinline__ void wg3_render(
         }
         VSPG_PROF_ACC_END(prof_decide);
         idle_polls = 0;
+        VSPG_W3T(if (kind == W3_VERTEX && n0 + n1 == 64u) tl.enter(1u, W3T_FULL); tl.chunk_begin());
         __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");
 
         if (kind == W3_VERTEX) {
             // ---- V: vertex processing (NEE, Russian roulette, new direction) ----------------------------
             VSPG_PROF(PS_WG_B);
-            bool cont = false, restart = false, freed = false;
+            bool cont = false, restart = false, freed = false, old_done = false;
             int slot = 0;
             if ((unsigned)lane < n0 + n1) {
                 slot = (unsigned)lane < n0 ? s_ring[q0][(pos0 + (unsigned)lane) % (unsigned)NP]
@@ -369,7 +489,8 @@ __device__ __forceinline__ void wg3_render(
                 if (alive) {
                     cont = true;
                 } else {
-                    emit(P.i(LY::PIXEL, slot), st.L, isg);
+                    if constexpr (CARRY) old_done = P.i(LY::SAMPLE, slot) != first_sample;
+                    emit(P.i(LY::PIXEL, slot), st.L, isg, old_done);
                     if constexpr (TRAIN) train.seg_count[rec_bind(P.i(LY::PIXEL, slot))] = pc.rec.n;
                     pc.path();
                     const int s2 = P.i(LY::SAMPLE, slot) + sample_step;
@@ -380,17 +501,20 @@ __device__ __forceinline__ void wg3_render(
             }
             ring_push_all<NP>(cont || restart ? Q_A : (freed ? Q_F : -1), (unsigned)slot | (restart ? kRestartBit : 0u), s_ring, s_w);
             const unsigned n_freed = (unsigned)__popcll(__ballot(freed));
+            const unsigned n_old = CARRY ? (unsigned)__popcll(__ballot(old_done)) : 0u;
             if (w3_lane() == 0) {
+                if (CARRY && n_old) atomicSub(s_w + W3_OLD, n_old);
                 if (n_freed) atomicSub(s_w + W3_LIVE, n_freed);
                 atomicSub(s_w + W3_BUSY_V, 1u);
             }
+            VSPG_W3T(tl.chunk_end(0u, n0 + n1));
             continue;
         }
 
         // ---- S: camera ray + primary segment for new paths, one secondary segment for the others ------
         {
             VSPG_PROF(PS_WG_A);
-            bool toVV = false, toVS = false, toA = false, restart = false, freed = false;
+            bool toVV = false, toVS = false, toA = false, restart = false, freed = false, old_done = false;
             int slot = 0;
             const bool fresh = kind == W3_FRESH;
             const bool tile_ok = !fresh || tile < n_tiles;  // (the head has run dry: the 64 slots go back)
@@ -423,7 +547,9 @@ __device__ __forceinline__ void wg3_render(
                         // the film now, before this launch's sample of the pixel can (same order of additions as ever)
                         if (w3_at_use(prev_samples) != nullptr && in_launch(px, py)) {
                             const size_t pidx = (size_t)py * W + px;
-                            resolve_sample(prev_samples[pidx], film + pidx, isg_stats + pidx * VSPG_ISG_STATS);
+                            const float4 parked = prev_samples[pidx];
+                            if (!(CARRY && carry_sentinel(parked.w)))  // (... unless its path is still in flight: it resumed in this launch)
+                                resolve_sample(parked, film + pidx, isg_stats + pidx * VSPG_ISG_STATS);
                         }
                     } else {
                         pxy = P.i(LY::PIXEL, slot);
@@ -473,7 +599,8 @@ __device__ __forceinline__ void wg3_render(
                     toVV = vx.volume;
                     toVS = !vx.volume;
                 } else if (valid) {
-                    emit(pxy, st.L, isg);
+                    if constexpr (CARRY) old_done = !primary && P.i(LY::SAMPLE, slot) != first_sample;
+                    emit(pxy, st.L, isg, old_done);
                     if constexpr (TRAIN) train.seg_count[rec_bind(pxy)] = pc.rec.n;  // PropagateSamples (:627) follows in k_propagate
                     pc.path();
                     const int s2 = P.i(LY::SAMPLE, slot) + sample_step;
@@ -484,13 +611,17 @@ __device__ __forceinline__ void wg3_render(
             }
             ring_push_all<NP>(toVV ? Q_VV : toVS ? Q_VS : (toA || restart) ? Q_A : (freed ? Q_F : -1), (unsigned)slot | (restart ? kRestartBit : 0u), s_ring, s_w);
             const unsigned n_freed = (unsigned)__popcll(__ballot(freed));
+            const unsigned n_old = CARRY ? (unsigned)__popcll(__ballot(old_done)) : 0u;
             if (w3_lane() == 0) {
+                if (CARRY && n_old) atomicSub(s_w + W3_OLD, n_old);
                 if (fresh && !tile_ok) atomicExch(s_w + W3_EXH, 1u);
                 if (n_freed) atomicSub(s_w + W3_LIVE, n_freed);
                 atomicSub(s_w + W3_BUSY_S, 1u);
             }
+            VSPG_W3T(tl.chunk_end(fresh ? 2u : 1u, tile_ok ? n0 : 0u));
         }
     }
+    VSPG_W3T(tl.stamp(W3T_EXIT));
     if constexpr (!GUIDED) {
         atomicAdd(&s_counters[CNT_PATHS], pc.paths); atomicAdd(&s_counters[CNT_SEGMENTS], pc.segments);
         atomicAdd(&s_counters[CNT_VOLUME_SCATTERS], pc.volume_scatters); atomicAdd(&s_counters[CNT_SURFACE_HITS], pc.surface_hits);
@@ -499,6 +630,29 @@ __device__ __forceinline__ void wg3_render(
     }
     __syncthreads();
     if (threadIdx.x < CNT_COUNT) atomicAdd(&counters[threadIdx.x], (unsigned long long)s_counters[threadIdx.x]);
+    if constexpr (CARRY) {
+        // SUSPEND (every wavefront has left the loop: no chunk in flight, every push committed): the image, and the sentinel of every
+        // path it holds -- the entries of the three path queues
+        unsigned int *const susp = reinterpret_cast<unsigned int *>((uintptr_t)s_w[W3_SUSP_LO] | ((uintptr_t)s_w[W3_SUSP_HI] << 32));
+        if (susp != nullptr) {
+            unsigned int *const img = susp + (size_t)blockIdx.x * kImgStride;
+            if (threadIdx.x < W3_COUNT) img[kImgWords + threadIdx.x] = s_w[threadIdx.x];
+            if (s_w[W3_LIVE] != 0u) {
+                const unsigned int *const pool32 = reinterpret_cast<const unsigned int *>(s_pool);
+                for (int i = threadIdx.x; i < kImgPool; i += kWgBlock) img[i] = pool32[i];
+                const unsigned short *const ring16 = &s_ring[0][0];
+                for (int i = threadIdx.x; i < Q_COUNT * NP / 2; i += kWgBlock) img[kImgPool + i] = (unsigned)ring16[2 * i] | ((unsigned)ring16[2 * i + 1] << 16);
+                for (int q = 0; q < Q_F; ++q) {
+                    const unsigned h = s_w[q * QC_STRIDE + QC_HEAD], n = s_w[q * QC_STRIDE + QC_COM] - h;
+                    for (unsigned i = threadIdx.x; i < n && i < (unsigned)NP; i += kWgBlock) {
+                        const int pxy = P.i(LY::PIXEL, (int)(s_ring[q][(h + i) % (unsigned)NP] & (kRestartBit - 1u)) % NP);
+                        const unsigned px = (unsigned)pxy & 0xffffu, py = (unsigned)pxy >> 16;
+                        if (in_launch((int)px, (int)py)) wave_samples[(size_t)py * W + px].w = kCarrySentinel;
+                    }
+                }
+            }
+        }
+    }
 }
 
 template <class Medium, bool GUIDED, int NP, int kWgBlock, int kWgWavesPerSimd, bool TRAIN = false>
@@ -520,6 +674,19 @@ __global__ __launch_bounds__(kWgBlock, kWgWavesPerSimd) void k_render_wave_wg3_w
     float4 *__restrict__ wave_samples, unsigned long long *__restrict__ counters, TrainArgs train, PixelWindow win) {
     wg3_render<Medium, GUIDED, NP, kWgBlock, kWgWavesPerSimd, TRAIN, true>(Sp, film, isg_stats, vsp_buf, vsp_ready, wave_end, first_sample, single_sample, jump,
                                                                            tiles_magic, work_head, prev_samples, wave_samples, counters, train, win);
+}
+
+// the same kernel in CARRY mode (see the header of this file): `resume` / `suspend` are per-workgroup images, either may be null
+template <class Medium, bool GUIDED, int NP, int kWgBlock, int kWgWavesPerSimd, bool WINDOW>
+__global__ __launch_bounds__(kWgBlock, kWgWavesPerSimd) void k_render_wave_wg3_carry(
+    const DScene *__restrict__ Sp, float4 *__restrict__ film, float *__restrict__ isg_stats, const float *__restrict__ vsp_buf,
+    int vsp_ready, int wave_end, int first_sample, int single_sample, PcgJump jump, unsigned int tiles_magic,
+    unsigned int *__restrict__ work_head, const float4 *__restrict__ prev_samples,
+    float4 *__restrict__ wave_samples, unsigned long long *__restrict__ counters, PixelWindow win,
+    const unsigned int *__restrict__ resume, unsigned int *__restrict__ suspend) {
+    wg3_render<Medium, GUIDED, NP, kWgBlock, kWgWavesPerSimd, false, WINDOW, true>(Sp, film, isg_stats, vsp_buf, vsp_ready, wave_end, first_sample, single_sample, jump,
+                                                                                   tiles_magic, work_head, prev_samples, wave_samples, counters,
+                                                                                   TrainArgs{nullptr, nullptr, nullptr, nullptr, 0, 0}, win, resume, suspend);
 }
 
 // ---- host side: the unguided rectangle-scene instantiations behind one call (what vspg_capi.hip launches for them, and what the
@@ -548,15 +715,30 @@ struct Wg3Launch {
     int null_zero;     // ... whose null-collision coefficient is exactly 0
     int windowed;      // the launch covers `win`, not the frame (vspg_render_window): k_render_wave_wg3_window
     PixelWindow win;
+    int carry;         // k_render_wave_wg3_carry: resume from / suspend into the per-workgroup images (either may be null)
+    const unsigned int *resume;
+    unsigned int *suspend;
 };
 template <int GREY> constexpr int kWg3PoolHomogT = wg3_pool_paths<PoolLayout<false, GREY>>(VSPG_WG3_OTHER);
+// dwords of a workgroup's image, the largest of the instantiations below (what the host allocates per workgroup)
+template <int GREY> constexpr int kWg3ImageStrideT = kWg3ImageStride<PoolLayout<false, GREY>, kWg3PoolHomogT<GREY>>;
+constexpr int kWg3ImageStrideMax = kWg3ImageStrideT<0> > kWg3ImageStrideT<1> ? (kWg3ImageStrideT<0> > kWg3ImageStrideT<2> ? kWg3ImageStrideT<0> : kWg3ImageStrideT<2>)
+                                                                             : (kWg3ImageStrideT<1> > kWg3ImageStrideT<2> ? kWg3ImageStrideT<1> : kWg3ImageStrideT<2>);
 // (a template: a plain inline host function that names kernels instantiates them in every translation unit that includes this
 // header, even where nothing calls it -- the exact ones belong to vspg_wg3_exact.hip alone)
 template <int = 0>
 inline int wg3_launch_unguided(const Wg3Launch &L) {
 #define VSPG_WG3_GO(M, NPOOL)                                                                                                                \
     do {                                                                                                                                     \
-        if (L.windowed)                                                                                                                      \
+        if (L.carry && L.windowed)                                                                                                           \
+            hipLaunchKernelGGL((k_render_wave_wg3_carry<M, false, NPOOL, VSPG_WG_BLOCK, VSPG_WG_WAVES, true>), dim3(L.blocks), dim3(VSPG_WG_BLOCK), 0, \
+                               L.stream, L.dscene, L.film, L.isg_stats, L.vsp, L.vsp_ready, L.wave_end, L.first_sample, L.single_sample, L.jump, \
+                               L.tiles_magic, L.work_head, L.ws_prev, L.ws_out, L.counters, L.win, L.resume, L.suspend);                    \
+        else if (L.carry)                                                                                                                    \
+            hipLaunchKernelGGL((k_render_wave_wg3_carry<M, false, NPOOL, VSPG_WG_BLOCK, VSPG_WG_WAVES, false>), dim3(L.blocks), dim3(VSPG_WG_BLOCK), 0, \
+                               L.stream, L.dscene, L.film, L.isg_stats, L.vsp, L.vsp_ready, L.wave_end, L.first_sample, L.single_sample, L.jump, \
+                               L.tiles_magic, L.work_head, L.ws_prev, L.ws_out, L.counters, PixelWindow{0, 0, 0, 0}, L.resume, L.suspend);   \
+        else if (L.windowed)                                                                                                                      \
             hipLaunchKernelGGL((k_render_wave_wg3_window<M, false, NPOOL, VSPG_WG_BLOCK, VSPG_WG_WAVES, false>), dim3(L.blocks), dim3(VSPG_WG_BLOCK), 0, \
                                L.stream, L.dscene, L.film, L.isg_stats, L.vsp, L.vsp_ready, L.wave_end, L.first_sample, L.single_sample, L.jump, \
                                L.tiles_magic, L.work_head, L.ws_prev, L.ws_out, L.counters, TrainArgs{nullptr, nullptr, nullptr, nullptr, 0, 0}, L.win); \

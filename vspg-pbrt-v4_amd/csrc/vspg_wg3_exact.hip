@@ -13,3 +13,17 @@
 VSPG_NS_BEGIN
 int wg3_launch_exact(const Wg3Launch &L) { return wg3_launch_unguided(L); }
 VSPG_NS_END  // namespace vspg
+
+#ifdef VSPG_W3_TIMELINE
+// diagnostic build only: the last launch's per-wavefront records (vspg_wg3.h), read and cleared
+extern "C" int vspg_w3_timeline_read(unsigned long long *out, int blocks) {
+    using namespace vspg;
+    if (blocks < 0 || blocks > (int)W3T_MAX_BLOCKS) return -1;
+    const size_t bytes = (size_t)blocks * 8 * 32 * sizeof(unsigned long long);
+    if (hipDeviceSynchronize() != hipSuccess) return -2;
+    if (hipMemcpyFromSymbol(out, HIP_SYMBOL(g_w3_timeline), bytes) != hipSuccess) return -3;
+    void *p = nullptr;
+    if (hipGetSymbolAddress(&p, HIP_SYMBOL(g_w3_timeline)) != hipSuccess || hipMemset(p, 0, sizeof(g_w3_timeline)) != hipSuccess) return -4;
+    return 0;
+}
+#endif
