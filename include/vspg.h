@@ -432,11 +432,51 @@ int vspg_renderer_get_arithmetic(VspgRenderer *r);
  * the counters lack them as well as the parked samples.  vspg_flush and every accessor named above -- and vspg_get_counters,
  * vspg_reset_counters, vspg_renderer_set_arithmetic, the buffer setters, the due update of vspg_post_process_step -- finish them
  * first (one short launch on the call's stream); vspg_renderer_destroy drops them.  VSPG_WG3_CARRY=0 in the environment (read
- * per wave) makes every wave finish its own paths. */
+ * per wave) makes every wave finish its own paths.
+ * vspg_film_error_enqueue (below) reads the film and belongs to this list: it finishes parked samples and suspended paths first, on
+ * its stream, so its record is of the COMPLETE film -- a host that records after every wave therefore gives up the carry of
+ * in-flight paths between waves (every wave is followed by the short drain launch). */
 int vspg_flush(VspgRenderer *r, void *stream);
 int vspg_film_device_ptr(VspgRenderer *r, float **dev_ptr, size_t *n_floats);
 int vspg_film_read(VspgRenderer *r, float *host_rgbw /* W*H*4 */, void *stream);
 int vspg_film_clear(VspgRenderer *r, void *stream);
+
+/* Film error against a reference image, reduced on the device: what ImageTileIntegrator::Render computes after every wave when
+ * --mse-reference-image is given (src/pbrt/cpu/integrators.cpp:129-158, :243-262) -- Image::MSE (src/pbrt/util/image.cpp:575-607) and
+ * its relative form Image::MRSE (:609-639) of the film against the reference image -- without reading the film back.
+ * Over the window [x0,x1) x [y0,y1) and per channel c, with v_c = RGBFilm::GetPixelRGB (film.h:269-287: w != 0 ? rgbSum_c / w :
+ * rgbSum_c, one float division):
+ *   se  = Sqr(double(v_c) - double(ref_c))                              (image.cpp:594)
+ *   rse = Sqr(double(v_c) - double(ref_c)) / Sqr(ref_c + 0.01)          (image.cpp:626; the sum and the square in double)
+ * a term that IsInf is skipped, a NaN term is not (:595-597, :627-629).  A record carries the six SUMS in double and the window's
+ * pixel count: sums of disjoint windows add, means do not.  The reference's last step is the caller's:
+ *   mse_c = Float(sum_se[c] / (Float(x1 - x0) * Float(y1 - y0))) (image.cpp:603-606), Average() = (mse_0 + mse_1 + mse_2) / 3 in Float
+ *   (image.h:205-210).
+ * The order in which a sum is associated is a fixed function of the window alone (csrc/vspg_film_error.h): the same film and window
+ * give the same bits on every call.  device_ticks is the device's constant-rate clock at the moment the record was completed, so
+ * error-over-time curves need no host synchronisation per wave; tick_khz is its rate. */
+typedef struct VspgFilmError {
+    int32_t  x0, y0, x1, y1;   /* the window */
+    int32_t  tag;              /* caller's label, e.g. samples per pixel so far */
+    uint32_t tick_khz;         /* rate of device_ticks (hipDeviceAttributeWallClockRate), filled in at read */
+    uint64_t n_pixels;         /* (x1-x0)*(y1-y0): the divisor of Image::MSE */
+    uint64_t device_ticks;     /* device clock when the record was completed */
+    double   sum_se[3];        /* image.cpp:575-607 before the division */
+    double   sum_rse[3];       /* image.cpp:609-639 before the division */
+} VspgFilmError;
+#define VSPG_FILM_ERROR_LOG_RECORDS 4096
+/* The reference image: full frame, absolute indexing, like every per-pixel buffer (a renderer may be given several windows).  The
+ * first call allocates the device copy (a float4 per pixel), the per-row partial sums and the log of VSPG_FILM_ERROR_LOG_RECORDS
+ * records; a renderer that never calls it allocates and launches nothing.  NULL removes the image (records already in the log stay).
+ * Synchronises `stream`. */
+int vspg_renderer_set_reference_image(VspgRenderer *r, const float *host_rgb /* W*H*3, row-major, top row first; NULL removes */, void *stream);
+/* Appends one record of the film as it stands to the device-side log.  Asynchronous on `stream`; window rules are
+ * vspg_render_window's.  VSPG_EINVAL without a reference image and on a full log (nothing is dropped silently).  It reads the film
+ * only.  Enqueues of one renderer on different streams are ordered behind each other by an event. */
+int vspg_film_error_enqueue(VspgRenderer *r, int x0, int y0, int x1, int y1, int tag, void *stream);
+/* Synchronises `stream`, copies the records in enqueue order and empties the log.  max_records smaller than the log's content:
+ * VSPG_EINVAL, log untouched. */
+int vspg_film_error_read(VspgRenderer *r, VspgFilmError *out, size_t max_records, size_t *n_out, void *stream);
 
 /* Image-space VSP buffer (stands in for openpgl ImageSpaceGuidingBuffer,
  * guidedvolpathvspgintegrator.cpp:161-178, 1098-1112). */

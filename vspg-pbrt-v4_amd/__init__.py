@@ -109,6 +109,62 @@ class VspgCounters(C.Structure):
         return {k: int(getattr(self, k)) for k, _ in self._fields_}
 
 
+class VspgFilmError(C.Structure):
+    _fields_ = [("x0", C.c_int32), ("y0", C.c_int32), ("x1", C.c_int32), ("y1", C.c_int32), ("tag", C.c_int32),
+                ("tick_khz", C.c_uint32), ("n_pixels", C.c_uint64), ("device_ticks", C.c_uint64),
+                ("sum_se", C.c_double * 3), ("sum_rse", C.c_double * 3)]
+
+
+FILM_ERROR_LOG_RECORDS = 4096
+
+
+class FilmError:
+    """One record of the film-error log (include/vspg.h, VspgFilmError): the six sums in double over a pixel window.  mse() /
+    mrse() perform the reference's last step: per channel Float(sum / (Float(width) * Float(height))) (src/pbrt/util/image.cpp:603-606,
+    :635-638), then ImageChannelValues::Average() in Float (image.h:205-210).  A record combined from several windows
+    (sharding.combine_film_errors) is no rectangle: its divisor is Float(n_pixels)."""
+
+    def __init__(self, x0, y0, x1, y1, tag, tick_khz, n_pixels, device_ticks, sum_se, sum_rse):
+        self.x0, self.y0, self.x1, self.y1, self.tag = int(x0), int(y0), int(x1), int(y1), int(tag)
+        self.tick_khz, self.n_pixels, self.device_ticks = int(tick_khz), int(n_pixels), int(device_ticks)
+        self.sum_se, self.sum_rse = [float(v) for v in sum_se], [float(v) for v in sum_rse]
+
+    @classmethod
+    def from_c(cls, rec):
+        return cls(rec.x0, rec.y0, rec.x1, rec.y1, rec.tag, rec.tick_khz, rec.n_pixels, rec.device_ticks, list(rec.sum_se),
+                   list(rec.sum_rse))
+
+    def window(self):
+        return self.x0, self.y0, self.x1, self.y1
+
+    def channel_means(self, sums):
+        import numpy as np
+        if self.n_pixels == (self.x1 - self.x0) * (self.y1 - self.y0):
+            div = np.float32(self.x1 - self.x0) * np.float32(self.y1 - self.y0)
+        else:
+            div = np.float32(self.n_pixels)
+        with np.errstate(all="ignore"):
+            return [np.float32(np.float64(s) / np.float64(div)) for s in sums]   # double / Float, stored as Float
+
+    def _average(self, sums):
+        import numpy as np
+        acc = np.float32(0)
+        with np.errstate(all="ignore"):
+            for v in self.channel_means(sums):
+                acc = np.float32(acc + v)
+            return float(np.float32(acc / np.float32(3)))
+
+    def mse(self):
+        return self._average(self.sum_se)
+
+    def mrse(self):
+        return self._average(self.sum_rse)
+
+    def __repr__(self):
+        return "FilmError(window=%r, tag=%d, n_pixels=%d, sum_se=%r, sum_rse=%r, device_ticks=%d)" % (
+            self.window(), self.tag, self.n_pixels, self.sum_se, self.sum_rse, self.device_ticks)
+
+
 class VspgTrainSample(C.Structure):
     _fields_ = [("p", C.c_float * 3), ("dir", C.c_float * 3), ("weight", C.c_float), ("pdf", C.c_float),
                 ("distance", C.c_float), ("flags", C.c_uint32)]
@@ -198,6 +254,9 @@ SYMBOLS = [
     ("vspg_film_device_ptr", C.c_int, [_vp, _P(_vp), _P(C.c_size_t)]),
     ("vspg_film_read", C.c_int, [_vp, _P(C.c_float), _vp]),
     ("vspg_film_clear", C.c_int, [_vp, _vp]),
+    ("vspg_renderer_set_reference_image", C.c_int, [_vp, _P(C.c_float), _vp]),
+    ("vspg_film_error_enqueue", C.c_int, [_vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _vp]),
+    ("vspg_film_error_read", C.c_int, [_vp, _P(VspgFilmError), C.c_size_t, _P(C.c_size_t), _vp]),
     ("vspg_vsp_buffer_device_ptr", C.c_int, [_vp, _P(_vp), _P(C.c_size_t)]),
     ("vspg_vsp_buffer_read", C.c_int, [_vp, _P(C.c_float), _P(C.c_int), _vp]),
     ("vspg_vsp_buffer_load", C.c_int, [_vp, _P(C.c_float), _vp]),
@@ -549,6 +608,30 @@ class Renderer:
 
     def film_clear(self, stream=None):
         _check(self.lib, self.lib.vspg_film_clear(self.h, _vp(stream or 0)))
+
+    def set_reference_image(self, img, stream=None):
+        """The reference image of the film-error records: (H, W, 3) float32, full frame, top row first; None removes it."""
+        if img is None:
+            _check(self.lib, self.lib.vspg_renderer_set_reference_image(self.h, None, _vp(stream or 0)))
+            return
+        import numpy as np
+        v = np.ascontiguousarray(img, dtype=np.float32)
+        if v.shape != (self.yres, self.xres, 3):
+            raise ValueError("reference image has shape %r, the frame is %r" % (v.shape, (self.yres, self.xres, 3)))
+        _check(self.lib, self.lib.vspg_renderer_set_reference_image(self.h, v.ctypes.data_as(_P(C.c_float)), _vp(stream or 0)))
+
+    def film_error_enqueue(self, window=None, tag=0, stream=None):
+        """Appends the error sums of the film as it stands over window = (x0, y0, x1, y1) (default: the frame) against the
+        reference image to the device-side log: asynchronous on `stream`, no film read-back (vspg_film_error_enqueue)."""
+        x0, y0, x1, y1 = window if window is not None else (0, 0, self.xres, self.yres)
+        _check(self.lib, self.lib.vspg_film_error_enqueue(self.h, int(x0), int(y0), int(x1), int(y1), int(tag), _vp(stream or 0)))
+
+    def film_errors(self, stream=None):
+        """Synchronises `stream`, returns the log's records (FilmError) in enqueue order and empties the log."""
+        buf = (VspgFilmError * FILM_ERROR_LOG_RECORDS)()
+        n = C.c_size_t()
+        _check(self.lib, self.lib.vspg_film_error_read(self.h, buf, FILM_ERROR_LOG_RECORDS, C.byref(n), _vp(stream or 0)))
+        return [FilmError.from_c(buf[i]) for i in range(n.value)]
 
     def vsp_buffer(self, stream=None):
         import numpy as np

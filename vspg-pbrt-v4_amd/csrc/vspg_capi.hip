@@ -21,6 +21,7 @@
 #include "vspg_trace.h"
 #include "vspg_wavefront.h"
 #include "vspg_wf_launch.h"
+#include "vspg_film_error.h"
 #ifdef VSPG_SINGLE_TU  // diagnostic builds that read device-side globals of the pipeline kernels (VSPG_WF_STATS, VSPG_PROFILE, VSPG_WF_DEBUG)
 #include "vspg_wf_grid.hip"
 #include "vspg_wf_nvdb.hip"
@@ -1733,6 +1734,15 @@ struct VspgRenderer {
     bool vsp_loaded = false;  // ImageSpaceGuidingBuffer(fileName): no further updates
     int wave_counter = 0, buffer_wave = 0;
     size_t npix = 0;
+    // film error against a reference image (vspg_film_error.h): allocated by the first vspg_renderer_set_reference_image
+    float4 *fe_ref = nullptr;            // the reference image, a padded float4 per pixel, full frame
+    bool fe_ref_set = false;
+    double *fe_partials = nullptr;       // six sums per row of the window being reduced (yres rows)
+    VspgFilmError *fe_log = nullptr;     // VSPG_FILM_ERROR_LOG_RECORDS records
+    size_t fe_count = 0;                 // records enqueued since the last read (the host's count: enqueue order is host order)
+    hipStream_t fe_stream = nullptr;     // the stream of the last enqueue ...
+    hipEvent_t fe_event = nullptr;       // ... and an event behind it: the partial sums are shared, an enqueue on another stream waits
+    bool fe_inflight = false;
 };
 
 // ---- host float helpers for scene preprocessing (same formulas as the kernels use) ----
@@ -3114,6 +3124,10 @@ int vspg_renderer_destroy(VspgRenderer *r) {
     if (r->le_scale) (void)hipFree(r->le_scale);
     if (r->temperature) (void)hipFree(r->temperature);
     if (r->majorant) (void)hipFree(r->majorant);
+    if (r->fe_ref) (void)hipFree(r->fe_ref);
+    if (r->fe_partials) (void)hipFree(r->fe_partials);
+    if (r->fe_log) (void)hipFree(r->fe_log);
+    if (r->fe_event) (void)hipEventDestroy(r->fe_event);
     delete r;
     return 0;
 }
@@ -3750,6 +3764,76 @@ int vspg_film_clear(VspgRenderer *r, void *stream) {
     HIPCHK(hipSetDevice(r->cfg.device));
     if (const int rc = flush_parked_samples(r, (hipStream_t)stream)) return rc;  // (their statistics stay; the film is cleared after)
     HIPCHK(hipMemsetAsync(r->film, 0, r->npix * sizeof(float4), (hipStream_t)stream));
+    return 0;
+}
+// ---- film error against a reference image (include/vspg.h, vspg_film_error.h) ----
+// (work of an earlier enqueue that still reads the reference image or writes the partial sums: the host waits for it)
+static int film_error_wait(VspgRenderer *r) {
+    if (r->fe_inflight) HIPCHK(hipEventSynchronize(r->fe_event));
+    r->fe_inflight = false;
+    return 0;
+}
+int vspg_renderer_set_reference_image(VspgRenderer *r, const float *host_rgb, void *stream) {
+    if (!r) return fail(VSPG_EINVAL, "null renderer");
+    HIPCHK(hipSetDevice(r->cfg.device));
+    if (const int rc = film_error_wait(r)) return rc;
+    if (!host_rgb) {
+        r->fe_ref_set = false;
+        return 0;
+    }
+    hipStream_t s = (hipStream_t)stream;
+    if (!r->fe_ref) HIPCHK(hipMalloc(&r->fe_ref, r->npix * sizeof(float4)));
+    if (!r->fe_partials) HIPCHK(hipMalloc(&r->fe_partials, (size_t)r->cfg.yres * 6 * sizeof(double)));
+    if (!r->fe_log) HIPCHK(hipMalloc(&r->fe_log, (size_t)VSPG_FILM_ERROR_LOG_RECORDS * sizeof(VspgFilmError)));
+    if (!r->fe_event) HIPCHK(hipEventCreateWithFlags(&r->fe_event, hipEventDisableTiming));
+    std::vector<float4> padded(r->npix);
+    for (size_t i = 0; i < r->npix; ++i) padded[i] = make_float4(host_rgb[3 * i], host_rgb[3 * i + 1], host_rgb[3 * i + 2], 0.f);
+    HIPCHK(hipMemcpyAsync(r->fe_ref, padded.data(), r->npix * sizeof(float4), hipMemcpyHostToDevice, s));
+    HIPCHK(hipStreamSynchronize(s));
+    r->fe_ref_set = true;
+    return 0;
+}
+int vspg_film_error_enqueue(VspgRenderer *r, int x0, int y0, int x1, int y1, int tag, void *stream) {
+    if (!r) return fail(VSPG_EINVAL, "null renderer");
+    if (x0 < 0 || y0 < 0 || x1 <= x0 || y1 <= y0 || x1 > r->cfg.xres || y1 > r->cfg.yres)
+        return fail(VSPG_EINVAL, "pixel window [" + std::to_string(x0) + "," + std::to_string(x1) + ") x [" + std::to_string(y0) + "," + std::to_string(y1) +
+                                     ") is empty or not inside the " + std::to_string(r->cfg.xres) + " x " + std::to_string(r->cfg.yres) + " film");
+    if (!r->fe_ref_set) return fail(VSPG_EINVAL, "vspg_film_error_enqueue: no reference image (vspg_renderer_set_reference_image)");
+    if (r->fe_count >= (size_t)VSPG_FILM_ERROR_LOG_RECORDS)
+        return fail(VSPG_EINVAL, "vspg_film_error_enqueue: the log holds " + std::to_string(VSPG_FILM_ERROR_LOG_RECORDS) +
+                                     " records and is full (vspg_film_error_read empties it)");
+    HIPCHK(hipSetDevice(r->cfg.device));
+    hipStream_t s = (hipStream_t)stream;
+    if (const int rc = flush_parked_samples(r, s)) return rc;  // (the record is of the complete film)
+    if (r->fe_inflight && s != r->fe_stream) HIPCHK(hipStreamWaitEvent(s, r->fe_event, 0));
+    const PixelWindow win = {x0, y0, x1, y1};
+    hipLaunchKernelGGL(k_film_error_rows, dim3((unsigned)(y1 - y0)), dim3(kFilmErrorBlock), 0, s, r->cfg.xres, win, r->film, r->fe_ref, r->fe_partials);
+    HIPCHK(hipGetLastError());
+    hipLaunchKernelGGL(k_film_error_finish, dim3(1), dim3(kFilmErrorBlock), 0, s, win, tag, r->fe_partials, r->fe_log + r->fe_count);
+    HIPCHK(hipGetLastError());
+    ++r->fe_count;
+    HIPCHK(hipEventRecord(r->fe_event, s));
+    r->fe_stream = s;
+    r->fe_inflight = true;
+    return 0;
+}
+int vspg_film_error_read(VspgRenderer *r, VspgFilmError *out, size_t max_records, size_t *n_out, void *stream) {
+    if (!r || !out) return fail(VSPG_EINVAL, "null argument");
+    if (max_records < r->fe_count)
+        return fail(VSPG_EINVAL, "vspg_film_error_read: the log holds " + std::to_string(r->fe_count) + " records, room for " + std::to_string(max_records));
+    if (n_out) *n_out = 0;
+    if (r->fe_count == 0) return 0;
+    HIPCHK(hipSetDevice(r->cfg.device));
+    hipStream_t s = (hipStream_t)stream;
+    HIPCHK(hipStreamSynchronize(s));
+    if (const int rc = film_error_wait(r)) return rc;  // (enqueues that went to another stream)
+    HIPCHK(hipMemcpyAsync(out, r->fe_log, r->fe_count * sizeof(VspgFilmError), hipMemcpyDeviceToHost, s));
+    HIPCHK(hipStreamSynchronize(s));
+    int khz = 0;
+    HIPCHK(hipDeviceGetAttribute(&khz, hipDeviceAttributeWallClockRate, r->cfg.device));
+    for (size_t i = 0; i < r->fe_count; ++i) out[i].tick_khz = (uint32_t)khz;
+    if (n_out) *n_out = r->fe_count;
+    r->fe_count = 0;
     return 0;
 }
 int vspg_vsp_buffer_device_ptr(VspgRenderer *r, float **dev_ptr, size_t *n_floats) {

@@ -647,28 +647,87 @@ GuidingCache GuidingCache::Read(const std::string &filename) {
     return gc;
 }
 
+std::vector<float> LoadMseReferenceImage(const std::string &filename, int xres, int yres, int x0, int y0, int x1, int y1) {
+    const TrBuffer img = TrBuffer::Load(filename);
+    const int bw = x1 - x0, bh = y1 - y0;
+    if (img.xres == xres && img.yres == yres) return img.rgb;
+    if (img.xres != bw || img.yres != bh)
+        throw Error(filename + ": the MSE reference image is " + std::to_string(img.xres) + " x " + std::to_string(img.yres) + ", it must have the size of the frame (" +
+                    std::to_string(xres) + " x " + std::to_string(yres) + ") or of the pixel bounds (" + std::to_string(bw) + " x " + std::to_string(bh) + ")");
+    std::vector<float> frame((size_t)xres * yres * 3, 0.f);
+    for (int y = 0; y < bh; ++y)
+        std::memcpy(&frame[((size_t)(y0 + y) * xres + x0) * 3], &img.rgb[(size_t)y * bw * 3], (size_t)bw * 3 * sizeof(float));
+    return frame;
+}
+void CheckMseReferenceOptions(const std::string &image, const std::string &out) {
+    if (!image.empty() && out.empty()) throw Error("Must provide MSE reference output filename via --mse-reference-out");
+    if (!out.empty() && image.empty()) throw Error("Must provide MSE reference image via --mse-reference-image");
+}
+float FilmErrorAverage(const VspgFilmError &rec, const double sums[3]) {
+    const float n = float(rec.x1 - rec.x0) * float(rec.y1 - rec.y0);
+    float sum = 0;
+    for (int c = 0; c < 3; ++c) {
+        const float mean = float(sums[c] / n);  // (double / Float, stored as Float: image.cpp:605)
+        sum += mean;
+    }
+    return sum / 3;
+}
+void GuidedVolPathVSPGIntegrator::SetMseReference(const std::vector<float> &frameImage, std::FILE *out) {
+    if (frameImage.size() != (size_t)cfg.xres * cfg.yres * 3) throw Error("the MSE reference image does not have the size of the frame");
+    if (vspg_renderer_set_reference_image(renderer, frameImage.data(), nullptr) != 0) throw Error(vspg_last_error());
+    mseOut = out;
+}
+
 void GuidedVolPathVSPGIntegrator::Render() {
     // ImageTileIntegrator::Render (integrators.cpp:123-239): waves of 1 spp, PostProcessWave each
     int waveStart = 0, waveEnd = 1, nextWaveSize = 1;
     VspgCounters before;
     std::memset(&before, 0, sizeof before);
+    // the film's error against the reference image, one record per wave (:243-257), kept on the device until the log is drained
+    std::vector<VspgFilmError> errors;
+    size_t logged = 0;
+    auto drainErrors = [&]() {
+        if (logged == 0) return;
+        const size_t at = errors.size();
+        errors.resize(at + logged);
+        size_t n = 0;
+        if (vspg_film_error_read(renderer, errors.data() + at, logged, &n, nullptr) != 0) throw Error(vspg_last_error());
+        errors.resize(at + n);
+        logged = 0;
+    };
     while (waveStart < spp) {
         const auto t0 = std::chrono::steady_clock::now();
         const std::string kernel = waveLog ? vspg_renderer_kernel_name(renderer) : "";
         if (vspg_render_window(renderer, bounds[0], bounds[1], bounds[2], bounds[3], waveStart, waveEnd, nullptr) != 0) throw Error(vspg_last_error());
         PostProcessWave();
+        if (mseOut) {  // (tag: the samples per pixel so far, the reference's waveStart at :254)
+            if (vspg_film_error_enqueue(renderer, bounds[0], bounds[1], bounds[2], bounds[3], waveEnd, nullptr) != 0) throw Error(vspg_last_error());
+            if (++logged == VSPG_FILM_ERROR_LOG_RECORDS) drainErrors();
+        }
         if (waveLog) {  // one JSON line per wave: the counter read synchronises the stream, so `ms` is the wave's wall time
             VspgCounters c;
             if (vspg_get_counters(renderer, &c, nullptr) != 0) throw Error(vspg_last_error());
             const double ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
-            std::fprintf(waveLog, "{\"wave\": %d, \"ms\": %.4f, \"paths\": %llu, \"segments\": %llu, \"density_queries\": %llu, \"kernel\": \"%s\"}\n", waveStart, ms,
+            std::fprintf(waveLog, "{\"wave\": %d, \"ms\": %.4f, \"paths\": %llu, \"segments\": %llu, \"density_queries\": %llu, \"kernel\": \"%s\"", waveStart, ms,
                          (unsigned long long)(c.paths - before.paths), (unsigned long long)(c.segments - before.segments),
                          (unsigned long long)(c.density_queries - before.density_queries), kernel.c_str());
+            if (mseOut) {  // (the stream is synchronised already: the wave's record is there)
+                drainErrors();
+                const VspgFilmError &e = errors.back(), &e0 = errors.front();
+                std::fprintf(waveLog, ", \"mse\": %.9g, \"mrse\": %.9g, \"device_ms\": %.6f", FilmErrorAverage(e, e.sum_se), FilmErrorAverage(e, e.sum_rse),
+                             e.tick_khz ? double(e.device_ticks - e0.device_ticks) / double(e.tick_khz) : 0.);
+            }
+            std::fprintf(waveLog, "}\n");
             std::fflush(waveLog);
             before = c;
         }
         waveStart = waveEnd;
         waveEnd = std::min(spp, waveEnd + nextWaveSize);
+    }
+    if (mseOut) {
+        drainErrors();
+        for (const VspgFilmError &e : errors) std::fprintf(mseOut, "%d, %.9g\n", e.tag, FilmErrorAverage(e, e.sum_se));  // :254
+        std::fflush(mseOut);
     }
 }
 void GuidedVolPathVSPGIntegrator::PostProcessWave() {

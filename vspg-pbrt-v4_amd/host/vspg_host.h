@@ -143,6 +143,18 @@ struct TrBufferSettings {  // "storeTrBuffer" / "loadTrBuffer" / "trBufferFileNa
     std::string fileName;
 };
 
+// --mse-reference-image (cmd/pbrt.cpp:60-61, ImageTileIntegrator::Render, cpu/integrators.cpp:129-158): the image the film is
+// compared with after every wave.  Read with TrBuffer's PFM reader (EXR is out of scope: OpenEXR is absent).  It has the size of
+// the frame -- then the pixel bounds select the part compared (:136-153) -- or exactly the size of the pixel bounds; anything else
+// is an Error that names both sizes.  Returned as a frame-sized image (W*H*3, top row first), what vspg_renderer_set_reference_image
+// takes; outside the pixel bounds nothing is ever compared.
+std::vector<float> LoadMseReferenceImage(const std::string &filename, int xres, int yres, int x0, int y0, int x1, int y1);
+// cmd/pbrt.cpp:244-248: each of --mse-reference-image / --mse-reference-out needs the other (throws Error with the reference's words)
+void CheckMseReferenceOptions(const std::string &image, const std::string &out);
+// The reference's last step on a record's sums (util/image.cpp:603-606 and ImageChannelValues::Average, util/image.h:205-210):
+// per channel Float(sum / (Float(width) * Float(height))), then the three averaged in Float.
+float FilmErrorAverage(const VspgFilmError &rec, const double sums[3]);
+
 class Integrator {
   public:
     virtual ~Integrator() = default;
@@ -179,10 +191,18 @@ class GuidedVolPathVSPGIntegrator : public Integrator {
     VspBuffer GetVspBuffer();            // the image-space VSP estimate as it stands
     const VspgIntegratorParams &Params() const { return params; }
     // one JSON line per wave while rendering: {wave, ms, paths, segments, density_queries, kernel} (not owned; NULL = off)
+    // With an MSE reference image the lines gain "mse", "mrse" and "device_ms" (device clock since the run's first record).
     void SetWaveLog(std::FILE *f) { waveLog = f; }
+    // Options->mseReferenceImage / mseReferenceOutput (integrators.cpp:129-158, :243-262): `frameImage` as LoadMseReferenceImage
+    // returns it; Render() then records the film's error over the pixel bounds after every wave ON THE DEVICE (vspg_film_error_enqueue:
+    // no film read-back, no host synchronisation per wave) and writes one line "spp, mse.Average()" per wave ("%d, %.9g\n", :254) to
+    // `out` (not owned) when it ends.  Recording completes the film after every wave, so the carry of in-flight paths between
+    // one-sample waves is given up.  Not covered: EXR reference images, --write-partial-images, vspg_pbrt_sharded.
+    void SetMseReference(const std::vector<float> &frameImage, std::FILE *out);
 
   private:
     std::FILE *waveLog = nullptr;
+    std::FILE *mseOut = nullptr;
     VspgIntegratorParams params;
     VspgRenderConfig cfg;
     VspgRenderer *renderer = nullptr;

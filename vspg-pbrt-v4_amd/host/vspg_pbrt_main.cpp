@@ -1,12 +1,16 @@
 // vspg_pbrt -- render a pbrt-v4 scene file (the subset of vspg_scenefile.h) with the MI355X-native GuidedVolPathVSPG path.
 //   vspg_pbrt scene.pbrt [--spp N] [--outfile image.pfm] [--seed S] [--device D] [--wave-log waves.jsonl] [--parse-only]
 //             [--cropwindow x0,x1,y0,y1] [--pixelbounds x0,x1,y0,y1]   (cmd/pbrt.cpp:132-153; they override the file's Film parameters)
+//             [--mse-reference-image ref.pfm --mse-reference-out file]  (cmd/pbrt.cpp:60-61, :244-248: after every wave the MSE of the
+//              film against the image is appended to the file as "spp, mse", cpu/integrators.cpp:243-257; reduced on the device.
+//              PFM only -- no EXR --, and neither --write-partial-images nor vspg_pbrt_sharded are covered.)
 // The counterpart of `pbrt scene.pbrt` for this integrator (cmd/pbrt.cpp -> RenderCPU, cpu/render.cpp:56-57); the image is
 // written as PFM (RGBFilm::WriteImage's EXR needs OpenEXR, an absent submodule).
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
 #include <string>
+#include <vector>
 
 #include "vspg_scenefile.h"
 
@@ -17,6 +21,7 @@ int main(int argc, char **argv) {
     bool parseOnly = false;
     vspg::FilmOverrides film;
     std::string cropArg, boundsArg;
+    std::string mseImagePath, mseOutPath;
     for (int i = 1; i < argc; ++i) {
         const std::string a = argv[i];
         auto next = [&]() -> const char * { if (i + 1 >= argc) { std::fprintf(stderr, "%s needs a value\n", a.c_str()); std::exit(2); } return argv[++i]; };
@@ -28,11 +33,14 @@ int main(int argc, char **argv) {
         else if (a == "--parse-only") parseOnly = true;
         else if (a == "--cropwindow") cropArg = next();
         else if (a == "--pixelbounds") boundsArg = next();
+        else if (a == "--mse-reference-image") mseImagePath = next();
+        else if (a == "--mse-reference-out") mseOutPath = next();
         else if (!a.empty() && a[0] == '-') { std::fprintf(stderr, "unknown option %s\n", a.c_str()); return 2; }
         else scene = a;
     }
-    if (scene.empty()) { std::fprintf(stderr, "usage: vspg_pbrt scene.pbrt [--spp N] [--outfile image.pfm] [--seed S] [--device D] [--wave-log waves.jsonl] [--parse-only] [--cropwindow x0,x1,y0,y1] [--pixelbounds x0,x1,y0,y1]\n"); return 2; }
+    if (scene.empty()) { std::fprintf(stderr, "usage: vspg_pbrt scene.pbrt [--spp N] [--outfile image.pfm] [--seed S] [--device D] [--wave-log waves.jsonl] [--parse-only] [--cropwindow x0,x1,y0,y1] [--pixelbounds x0,x1,y0,y1] [--mse-reference-image ref.pfm --mse-reference-out file]\n"); return 2; }
     try {
+        vspg::CheckMseReferenceOptions(mseImagePath, mseOutPath);
         if (!cropArg.empty()) vspg::ParseCropWindowArg(cropArg, &film);
         if (!boundsArg.empty()) vspg::ParsePixelBoundsArg(boundsArg, &film);
         auto sd = vspg::ParseSceneFile(scene);
@@ -57,6 +65,11 @@ int main(int argc, char **argv) {
         if (sd->scene.medium.temperature) std::printf("; temperature grid (blackbody emission under \"vspsamplingmethod\" \"nds\")");
         std::printf("\n");
         std::printf("pixel bounds: [ (%d, %d) - (%d, %d) ]\n", sd->boundsX0, sd->boundsY0, sd->boundsX1, sd->boundsY1);
+        std::vector<float> mseImage;
+        if (!mseImagePath.empty()) {
+            mseImage = vspg::LoadMseReferenceImage(mseImagePath, sd->xres, sd->yres, sd->boundsX0, sd->boundsY0, sd->boundsX1, sd->boundsY1);
+            std::printf("MSE reference image: %s\n", mseImagePath.c_str());
+        }
         if (parseOnly) return 0;
         auto integrator = vspg::CreateIntegrator(*sd, device);
         std::printf("%s\n", integrator->ToString().c_str());
@@ -67,8 +80,15 @@ int main(int argc, char **argv) {
             if (!wl) throw vspg::Error("cannot open " + waveLogPath);
             vi->SetWaveLog(wl);
         }
+        std::FILE *mseOut = nullptr;
+        if (!mseImagePath.empty()) {
+            mseOut = std::fopen(mseOutPath.c_str(), "w");  // (integrators.cpp:155-157)
+            if (!mseOut) throw vspg::Error(mseOutPath + ": cannot open for writing");
+            vi->SetMseReference(mseImage, mseOut);
+        }
         integrator->Render();
         if (wl) { vi->SetWaveLog(nullptr); std::fclose(wl); }
+        if (mseOut) std::fclose(mseOut);
         vspg::Film film = vi->GetFilm();
         film.WritePFM(sd->filmFilename);
         VspgCounters c = vi->Counters();

@@ -51,6 +51,35 @@ class BandShard:
         if self.y1 > self.y0:
             self.r.render_window(0, self.y0, self.xres, self.y1, w0, w1, stream)
 
+    def film_error_enqueue(self, tag=0, stream=None):
+        """one film-error record of the band (Renderer.film_error_enqueue); a rank whose band is empty records nothing.  The
+        ranks' records of one tag go through combine_film_errors -- or, as seven doubles per rank, through sum_over_ranks."""
+        if self.y1 > self.y0:
+            self.r.film_error_enqueue((0, self.y0, self.xres, self.y1), tag, stream)
+
+
+def combine_film_errors(records):
+    """Film-error records of DISJOINT windows -> one record of their union: the six sums added in the order given, in double, and
+    the pixel counts added.  Sums add over windows, means do not, which is why a record carries sums (include/vspg.h,
+    VspgFilmError).  The result keeps the first record's tag and clock rate, the bounding box of the windows and the latest
+    device_ticks; its mse() / mrse() divide by n_pixels."""
+    import copy
+    records = list(records)
+    if not records:
+        raise ValueError("combine_film_errors: no records")
+    out = copy.copy(records[0])
+    out.sum_se, out.sum_rse = [0.0, 0.0, 0.0], [0.0, 0.0, 0.0]
+    out.n_pixels = 0
+    for r in records:
+        for c in range(3):
+            out.sum_se[c] += float(r.sum_se[c])
+            out.sum_rse[c] += float(r.sum_rse[c])
+        out.n_pixels += int(r.n_pixels)
+    out.x0, out.y0 = min(r.x0 for r in records), min(r.y0 for r in records)
+    out.x1, out.y1 = max(r.x1 for r in records), max(r.y1 for r in records)
+    out.device_ticks = max(r.device_ticks for r in records)
+    return out
+
 
 def ordered_after(torch, device, stream, fn):
     """Run fn() -- work torch issues on ITS current stream (torch.distributed's collectives) -- ordered after what `stream`
