@@ -565,6 +565,25 @@ int vspg_ray_batch(VspgRenderer *r, int n, const VspgRayQuery *q, VspgRayResult 
 int vspg_sample_tmaj_batch(VspgRenderer *r, int variant, int n, const VspgTmajQuery *q,
                            VspgTmajResult *out, void *stream);
 
+/* Read-back of a grid / NanoVDB-semantics medium's device storage (test + diagnostics): the "octet bricks" the kernels read.
+ * The grid is cut into bnx x bny x bnz bricks of 8 x 8 x 8 octets (bn = (n + 8) / 8 per axis; brick number = (bz * bny + by) * bnx +
+ * bx; brick b holds the octets of base voxels 8b - 1 .. 8b + 6 per axis, i.e. raw voxels 8b - 1 .. 8b + 7, zero outside the grid).
+ * An octet is the eight raw values {(x,y,z), (x+1,y,z), (x,y+1,z), (x+1,y+1,z), then the same four at z+1} of its base voxel;
+ * a brick stores its 512 octets x fastest.  `indexed` = 1: only bricks that hold a non-zero value are stored, in increasing
+ * brick number, behind an index (slot, or -1 = all zero); 0: every brick is stored and a brick's slot is its number.
+ * VSPG_EINVAL for a renderer whose medium is not a grid. */
+typedef struct VspgBrickInfo {
+    int32_t bnx, bny, bnz;
+    int32_t indexed;
+    uint64_t n_stored;      /* stored bricks (dense: bnx * bny * bnz) */
+    uint64_t index_bytes;   /* device bytes held by the index (0 when dense) */
+    uint64_t octet_bytes;   /* device bytes held by the octets (one placeholder brick when n_stored == 0) */
+} VspgBrickInfo;
+int vspg_brick_info(VspgRenderer *r, VspgBrickInfo *out);
+/* index: bnx * bny * bnz slots (dense: the identity, the slot the kernels compute); octets: n_stored * 512 * 8 floats.  HOST
+ * arrays, either may be NULL. */
+int vspg_brick_read(VspgRenderer *r, int32_t *index, float *octets, void *stream);
+
 /* Primitive batch (bit-exact layer): for each i computes on device
  *   hash[i]   = Hash(f[i])                      (src/pbrt/util/hash.h:100)
  *   rng_u32[i]= RNG(Hash(f[i]),Hash(g[i])).Uniform<uint32_t>()  (util/rng.h:82-88,119-125)

@@ -1353,6 +1353,59 @@ def test_nvdb_paths_and_film_vs_oracle(nvdb_pair):
 
 
 # ---------------------------------------------------------------------------------------------
+# the same fixtures and the same assertions on the indexed (sparse) brick layout, which these 24^3 grids never take by
+# themselves (VSPG_DENSE_BRICKS=0 is read by vspg_renderer_create; tests/test_brick_storage_gpu.py has the sparse fixtures)
+# ---------------------------------------------------------------------------------------------
+def _indexed_pair(P, scene):
+    W, H = 64, 48
+    prm = P.app_f_params()
+    with pytest.MonkeyPatch.context() as mp:
+        mp.setenv("VSPG_DENSE_BRICKS", "0")
+        g = P.Renderer(scene, prm, W, H, seed=3)
+    assert g.brick_info()["indexed"] == 1
+    return g, oracle_lib.OracleRenderer(scene, prm, W, H, seed=3)
+
+
+@pytest.fixture(scope="module")
+def cloud_pair_indexed(gpu_pkg):
+    from scenes import cloud_density, grid_scene
+    scene = grid_scene(cloud_density(24), (24, 24, 24), (0.05, 0.08, 0.1), (3.0, 2.6, 2.2), g=0.5, bmin=(-0.8, -0.8, -0.5), bmax=(0.8, 0.7, 0.9), W=64, H=48)
+    g, c = _indexed_pair(gpu_pkg, scene)
+    yield gpu_pkg, g, c
+    g.close()
+    c.close()
+
+
+@pytest.fixture(scope="module")
+def nvdb_pair_indexed(gpu_pkg):
+    from scenes import cloud_density, nvdb_scene
+    scene = nvdb_scene(cloud_density(24), (24, 24, 24), (0.05, 0.08, 0.1), (3.0, 2.6, 2.2), g=0.5, index_min=(-3, 2, 0), voxel=(0.066, 0.0625, 0.058),
+                       origin=(-0.6, -0.93, -0.5), density_offset=0.02, majorant_scale=1.25, W=64, H=48)
+    g, c = _indexed_pair(gpu_pkg, scene)
+    yield gpu_pkg, g, c
+    g.close()
+    c.close()
+
+
+@pytest.mark.parametrize("variant", [0, 1, 2])
+def test_grid_free_flight_vs_oracle_indexed_bricks(cloud_pair_indexed, variant):
+    test_grid_free_flight_vs_oracle(cloud_pair_indexed, variant)
+
+
+def test_grid_paths_and_film_vs_oracle_indexed_bricks(cloud_pair_indexed):
+    test_grid_paths_and_film_vs_oracle(cloud_pair_indexed)
+
+
+@pytest.mark.parametrize("variant", [0, 1, 2])
+def test_nvdb_free_flight_vs_oracle_indexed_bricks(nvdb_pair_indexed, variant):
+    test_nvdb_free_flight_vs_oracle(nvdb_pair_indexed, variant)
+
+
+def test_nvdb_paths_and_film_vs_oracle_indexed_bricks(nvdb_pair_indexed):
+    test_nvdb_paths_and_film_vs_oracle(nvdb_pair_indexed)
+
+
+# ---------------------------------------------------------------------------------------------
 # non-identity renderFromMedium (media.h:322, :354; util/transform.h:387-429, transform.cpp:263-303)
 # ---------------------------------------------------------------------------------------------
 def _placed(P, scene, kind):

@@ -227,6 +227,11 @@ class VspgTmajResult(C.Structure):
                 ("vrc", C.c_float), ("majorant_scale", C.c_float)]
 
 
+class VspgBrickInfo(C.Structure):
+    _fields_ = [("bnx", C.c_int32), ("bny", C.c_int32), ("bnz", C.c_int32), ("indexed", C.c_int32),
+                ("n_stored", C.c_uint64), ("index_bytes", C.c_uint64), ("octet_bytes", C.c_uint64)]
+
+
 # every symbol include/vspg.h declares: (name, restype, argtypes)
 _P = C.POINTER
 _vp = C.c_void_p
@@ -265,6 +270,8 @@ SYMBOLS = [
     ("vspg_reset_counters", C.c_int, [_vp, _vp]),
     ("vspg_trace_paths", C.c_int, [_vp, C.c_int, _P(C.c_int32), _P(C.c_int32), _P(C.c_float), _P(C.c_int32), _vp]),
     ("vspg_sample_tmaj_batch", C.c_int, [_vp, C.c_int, C.c_int, _P(VspgTmajQuery), _P(VspgTmajResult), _vp]),
+    ("vspg_brick_info", C.c_int, [_vp, _P(VspgBrickInfo)]),
+    ("vspg_brick_read", C.c_int, [_vp, _P(C.c_int32), _P(C.c_float), _vp]),
     ("vspg_primitives_batch", C.c_int, [_vp, C.c_int, _P(C.c_float), _P(C.c_float), _P(C.c_uint64), _P(C.c_uint32), _P(C.c_float), _vp]),
     ("vspg_renderer_training_stats", C.c_int, [_vp, _P(VspgTrainStats), _vp]),
     ("vspg_train_samples_read", C.c_int, [_vp, _P(VspgTrainSample), C.c_size_t, _P(C.c_size_t), _vp]),
@@ -719,6 +726,24 @@ class Renderer:
         out = (VspgTmajResult * n)()
         _check(self.lib, self.lib.vspg_sample_tmaj_batch(self.h, variant, n, q, out, _vp(0)))
         return list(out)
+
+    def brick_info(self):
+        """The device layout of a grid medium's density (vspg_brick_info): dict with bnx, bny, bnz, indexed, n_stored,
+        index_bytes, octet_bytes."""
+        bi = VspgBrickInfo()
+        _check(self.lib, self.lib.vspg_brick_info(self.h, C.byref(bi)))
+        return {k: int(getattr(bi, k)) for k, _ in VspgBrickInfo._fields_}
+
+    def brick_storage(self, index=True, octets=True):
+        """(index [bnz, bny, bnx] int32 -- slot or -1, the identity when every brick is stored --, octets
+        [n_stored, 8, 8, 8, 8] float32 -- brick, z, y, x in the brick, corner) as the kernels read them (vspg_brick_read)."""
+        import numpy as np
+        bi = self.brick_info()
+        idx = np.empty((bi["bnz"], bi["bny"], bi["bnx"]), dtype=np.int32) if index else None
+        octs = np.empty((bi["n_stored"], 8, 8, 8, 8), dtype=np.float32) if octets else None
+        _check(self.lib, self.lib.vspg_brick_read(self.h, idx.ctypes.data_as(_P(C.c_int32)) if index else None,
+                                                 octs.ctypes.data_as(_P(C.c_float)) if octets else None, _vp(0)))
+        return idx, octs
 
     def primitives_batch(self, f, g):
         import numpy as np

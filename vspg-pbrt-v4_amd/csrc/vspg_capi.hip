@@ -2874,7 +2874,8 @@ int vspg_renderer_create(const VspgScene *scene, const VspgIntegratorParams *par
             CK(hipMalloc(&dflags, nb * sizeof(int32_t)));
             hipLaunchKernelGGL(k_brick_flags, dim3((unsigned)nb), dim3(kBlock), 0, 0, r->density, nx, ny, nz, bnx, bny, dflags);
             std::vector<int32_t> flags(nb), index(nb), active;
-            hipError_t ef = hipMemcpy(flags.data(), dflags, nb * sizeof(int32_t), hipMemcpyDeviceToHost);
+            hipError_t ef = hipGetLastError();  // a launch that failed would leave the flags uninitialised
+            if (ef == hipSuccess) ef = hipMemcpy(flags.data(), dflags, nb * sizeof(int32_t), hipMemcpyDeviceToHost);
             (void)hipFree(dflags);
             CK(ef);
             // Dense bricks: when storing EVERY brick fits the budget (16 KB per 8^3 voxels: 0.5 GB for 256^3, 4.3 GB for 512^3 of this
@@ -2900,7 +2901,8 @@ int vspg_renderer_create(const VspgScene *scene, const VspgIntegratorParams *par
                 hipError_t ea = hipMemcpy(dactive, active.data(), r->n_bricks * sizeof(int32_t), hipMemcpyHostToDevice);
                 if (ea == hipSuccess) {
                     hipLaunchKernelGGL(k_brick_fill, dim3((unsigned)r->n_bricks), dim3(512), 0, 0, r->density, nx, ny, nz, bnx, bny, dactive, r->octets);
-                    ea = hipDeviceSynchronize();
+                    ea = hipGetLastError();
+                    if (ea == hipSuccess) ea = hipDeviceSynchronize();
                 }
                 (void)hipFree(dactive);
                 CK(ea);
@@ -4034,6 +4036,37 @@ int vspg_primitives_batch(VspgRenderer *r, int n, const float *f, const float *g
     HIPCHK(hipMemcpyAsync(hash, dh.p, (size_t)n * 8, hipMemcpyDeviceToHost, s));
     HIPCHK(hipMemcpyAsync(rng_u32, du.p, (size_t)n * 4, hipMemcpyDeviceToHost, s));
     HIPCHK(hipMemcpyAsync(fastexp, de.p, (size_t)n * 4, hipMemcpyDeviceToHost, s));
+    HIPCHK(hipStreamSynchronize(s));
+    return 0;
+}
+
+static bool has_bricks(const VspgRenderer *r) {
+    return r->scene.medium.type == VSPG_MEDIUM_GRID || r->scene.medium.type == VSPG_MEDIUM_NANOVDB;
+}
+
+int vspg_brick_info(VspgRenderer *r, VspgBrickInfo *out) {
+    if (!r || !out) return fail(VSPG_EINVAL, "null argument");
+    if (!has_bricks(r)) return fail(VSPG_EINVAL, "renderer has no grid medium");
+    const size_t nb = (size_t)r->hscene.bnx * r->hscene.bny * r->hscene.bnz;
+    out->bnx = r->hscene.bnx; out->bny = r->hscene.bny; out->bnz = r->hscene.bnz;
+    out->indexed = r->brick_index ? 1 : 0;
+    out->n_stored = r->n_bricks;
+    out->index_bytes = r->brick_index ? nb * sizeof(int32_t) : 0;
+    out->octet_bytes = (r->n_bricks ? r->n_bricks : 1) * 512 * 2 * sizeof(float4);
+    return 0;
+}
+
+int vspg_brick_read(VspgRenderer *r, int32_t *index, float *octets, void *stream) {
+    if (!r) return fail(VSPG_EINVAL, "null renderer");
+    if (!has_bricks(r)) return fail(VSPG_EINVAL, "renderer has no grid medium");
+    HIPCHK(hipSetDevice(r->cfg.device));
+    hipStream_t s = (hipStream_t)stream;
+    const size_t nb = (size_t)r->hscene.bnx * r->hscene.bny * r->hscene.bnz;
+    if (index) {
+        if (r->brick_index) HIPCHK(hipMemcpyAsync(index, r->brick_index, nb * sizeof(int32_t), hipMemcpyDeviceToHost, s));
+        else for (size_t b = 0; b < nb; ++b) index[b] = (int32_t)b;   // dense: GridMediumT::octet uses the cell number as the slot
+    }
+    if (octets && r->n_bricks) HIPCHK(hipMemcpyAsync(octets, r->octets, r->n_bricks * 512 * 2 * sizeof(float4), hipMemcpyDeviceToHost, s));
     HIPCHK(hipStreamSynchronize(s));
     return 0;
 }

@@ -1441,9 +1441,10 @@ struct GridMediumT {
             const int cell = ((oz >> 3) * bny + (oy >> 3)) * bnx + (ox >> 3);
             int b = cell;
             if (brick_index) b = *(const int VSPG_GLOBAL_AS *)(brick_index + cell);
-            VSPG_DBG_CHECK(b < 1 << 20 || !brick_index, 1);
+            // a slot is below the stored count, which is at most the number of bricks (an indexed grid may store more than 2^20)
+            VSPG_DBG_CHECK(b < bnx * bny * ((nz + 8) >> 3), 1);
 #ifdef VSPG_WF_DEBUG
-            if (brick_index && b >= 1 << 20) return o;
+            if (b >= bnx * bny * ((nz + 8) >> 3)) return o;
 #endif
             if (b >= 0) {
                 typedef float v4f_ __attribute__((ext_vector_type(4)));
