@@ -2948,7 +2948,7 @@ def test_temperature_grid_emission_vs_oracle(gpu_pkg, kind, options):
         films.append(fg)
         g.close(); cc.close()
     # ("wg": the workgroup kernel's pool record has no room for the wavelength sample -- a medium with a temperature grid is routed
-    #  to the per-lane kernel instead, vspg_capi.hip: uses_wg_kernel; round 4 ran k_render_wave_wg with an uninitialised sample)
+    #  to the per-lane kernel instead, vspg_kernel_choice.h: choose_kernel; round 4 ran k_render_wave_wg with an uninitialised sample)
     for kernel in (None, "lane", "wg"):
         if kernel:
             os.environ["VSPG_KERNEL"] = kernel

@@ -22,6 +22,7 @@
 #include "vspg_wavefront.h"
 #include "vspg_wf_launch.h"
 #include "vspg_film_error.h"
+#include "vspg_kernel_choice.h"
 #ifdef VSPG_SINGLE_TU  // diagnostic builds that read device-side globals of the pipeline kernels (VSPG_WF_STATS, VSPG_PROFILE, VSPG_WF_DEBUG)
 #include "vspg_wf_grid.hip"
 #include "vspg_wf_nvdb.hip"
@@ -29,6 +30,7 @@
 #endif
 
 using namespace vspg;
+using namespace vspg_choice;
 
 // =======================================================================================
 // kernels
@@ -1655,7 +1657,7 @@ struct VspgRenderer {
     VspgIntegratorParams prm;
     VspgRenderConfig cfg;
     int arith = VSPG_ARITH_EXACT;   // vspg_renderer_set_arithmetic (vspg_arith.h): which instantiations the path kernels are launched from
-    std::string kernel_name_buf, kernel_name_buf2;
+    std::string kernel_name_buf;
     DScene hscene;
     DScene *dscene = nullptr;
     float4 *film = nullptr;
@@ -2561,12 +2563,8 @@ static int validate(const VspgScene *scene, const VspgIntegratorParams *p, const
 // One pass of the wavefront pipeline: sample index `sample` of every pixel.  The pipeline's kernels are instantiated in their own
 // translation units (vspg_wf_grid.hip / vspg_wf_nvdb.hip: wf_dispatch_*, vspg_wf_launch.h), which `make -j` builds beside this one;
 // here the pass is prepared -- buffers, grids, streams -- and handed over as a plain WfLaunch.
-static bool wf_merged_walks(const VspgRenderer *r, bool guided) {
-    bool merged = r->hscene.has_boundaries != 0 || guided;
-    if (const char *e = getenv("VSPG_WF_MERGED")) { if (e[0] == '0') merged = false; else if (e[0] == '1') merged = true; }
-    return merged;
-}
-static int wf_render_pass(VspgRenderer *r, const PixelWindow &win, int sample, hipStream_t s, bool nvdb, bool guided, bool train, bool grey) {
+static int wf_render_pass(VspgRenderer *r, const KernelChoice &c, const PixelWindow &win, int sample, hipStream_t s) {
+    const bool nvdb = r->scene.medium.type == VSPG_MEDIUM_NANOVDB, guided = c.guided, train = c.train, grey = r->medium_grey;
     const int tilesX = win_tiles_x(win), tilesY = win_tiles_y(win);  // the pass's slots: the pixels of the window's tiles
     const size_t items = (size_t)tilesX * tilesY * 64;
     // Path-loop iterations of a pass.  Without medium boundaries every iteration ends at a vertex and raises the depth: maxdepth + 1
@@ -2652,8 +2650,8 @@ static int wf_render_pass(VspgRenderer *r, const PixelWindow &win, int sample, h
     }
     // both walks of an iteration as ONE kernel where the job lists are short or a third kernel sits in the chain (boundary scenes,
     // guided pipelines); side by side on two streams for dense unguided clouds (k_wf_walk, vspg_wavefront.h: measured both ways).
-    // VSPG_WF_MERGED=0|1 overrides (read per pass: tests and A/Bs flip it).
-    L.merged = wf_merged_walks(r, guided);
+    // VSPG_WF_MERGED=0|1 overrides (choose_kernel; decided per call: tests and A/Bs flip it).
+    L.merged = c.wf_merged;
     // job cursors of the merged walk kernel's stream: boundary scenes' short lists are dealt out to kWfSegs of them (wf_claim_refill;
     // VSPG_WF_SEGS=1|8 overrides, read per pass)
     L.segs = bnd ? kWfSegs : 1;
@@ -2708,6 +2706,16 @@ struct RoctxRange {
     explicit RoctxRange(const char *name) { if (g_roctx.push) g_roctx.push(name); }
     ~RoctxRange() { if (g_roctx.pop) g_roctx.pop(); }
 };
+// A kernel instantiation as a value: what vspg_render_window's launch lambdas are handed.  Only the tuples named there are built -- each
+// further one costs minutes of compile time.
+template <class M, bool G = false, bool T = false, int NP = 0, int BLK = 0, int WV = 0>
+struct KernelInst {
+    using Medium = M;
+    static constexpr bool guided = G, train = T;
+    static constexpr int pool = NP, block = BLK, waves = WV;
+};
+template <class M, int NP> using WgHomogInst = KernelInst<M, false, false, NP, kWgBlockHomog, kWgWavesHomog>;
+template <class M, int NP, bool T = false> using WgGuidedInst = KernelInst<M, true, T, NP, kWgBlockGuided, kWgWavesGuided>;
 }  // namespace
 
 extern "C" {
@@ -3134,107 +3142,19 @@ int vspg_renderer_destroy(VspgRenderer *r) {
     return 0;
 }
 
-// scheduler: "wg" = workgroup-level wavefront kernel, "lane" = per-lane persistent kernel.  Default: wg for
-// homogeneous media (dense, equally long phases); lane for grid media, whose tracking walks have very
-// different lengths per path -- a phase lasts as long as its longest walk, while the per-lane kernel
-// refills a lane the moment its path ends (measured on the 256^3 cloud stand-in: 30.5 vs 38.6 ms per wave)
-// -- and for guided builds.  VSPG_KERNEL=wg|lane overrides (unguided builds only).
-// guided renders on the workgroup kernel (VSPG_KERNEL=wg): a trained (or loaded) field being QUERIED over a homogeneous medium
-// -- training launches record path segments and guided Russian roulette carries per-pixel state, both on the per-lane kernel.
-// Opt-in, not the default: measured on MI355X (1080p fog box, reference-default options) the per-lane kernel
-// runs a guided wave in 2.33 ms, this one in 2.58 ms (384-path pool, kd nodes in L2) / 2.93 ms (320-path pool + the upper kd
-// levels in LDS): it issues 18 % fewer vector instructions at 68 % instead of 54 % lane utilisation, but the guided vertex code
-// needs ~240 registers either way (2 waves per SIMD) and at that occupancy the phase barriers cost more than the compaction saves.
-// VSPG_KERNEL=wg|lane|wf picks a path kernel where several serve a configuration (tests, A/B runs); empty == unset
-static const char *kernel_env() {
-    const char *e = getenv("VSPG_KERNEL");
-    return e && *e ? e : nullptr;
-}
-// Medium boundaries, interface materials and spheres are served by the full-scene code paths (per-lane kernel, pipeline)
-static bool has_boundaries_or_spheres(const VspgRenderer *r) { return r->hscene.has_boundaries != 0 || r->hscene.n_spheres > 0; }
-static bool uses_wg_guided(const VspgRenderer *r) {
-    // round 3: the workgroup kernel's guided vertex (vspg_guided_wg.h, four waves per SIMD) is the DEFAULT for a trained or
-    // loaded field over a homogeneous medium in a rectangle scene; VSPG_KERNEL=lane selects the per-lane kernel (tests compare
-    // the two).  Guided Russian roulette, triangles / infinite lights and non-uniform light samplers stay per-lane.
-    const char *kenv = kernel_env();
-    if (kenv && strcmp(kenv, "wg") != 0) return false;
-    if (has_boundaries_or_spheres(r)) return false;
-    return wants_guiding(r->prm) && !r->prm.rrguiding && r->scene.medium.type == VSPG_MEDIUM_HOMOGENEOUS &&
-           r->hscene.n_tris == 0 && r->hscene.n_inf == 0 && r->hscene.lsamp.mode == VSPG_LIGHTSAMPLER_UNIFORM;
-}
-// guided renders over a homogeneous medium: the grey / zero-null-coefficient / rectangle-scene instantiation of the per-lane
-// kernel (the segment half of the loop sheds the same per-channel work as the headline kernel's instantiation)
-static bool guided_grey_simple(const VspgRenderer *r) {
-    return r->scene.medium.type == VSPG_MEDIUM_HOMOGENEOUS && r->medium_grey && r->surfaces_grey && r->null_zero && r->hscene.n_tris == 0 &&
-           r->hscene.n_inf == 0 && r->hscene.lsamp.mode == VSPG_LIGHTSAMPLER_UNIFORM && !has_boundaries_or_spheres(r) && !getenv("VSPG_NO_GREY_GUIDED");
-}
-// a scene of rectangles and area lights only, one medium filling it: what the workgroup kernel's specialised instantiations are built for
-static bool scene_is_simple(const VspgRenderer *r) {
-    return r->hscene.n_tris == 0 && r->hscene.n_inf == 0 && r->hscene.lsamp.mode == VSPG_LIGHTSAMPLER_UNIFORM && !has_boundaries_or_spheres(r);
-}
-// Round 4: everything else over a homogeneous medium, unguided -- triangles (BVH), spheres, infinite lights, power / BVH light samplers,
-// medium boundaries -- runs the workgroup kernel's FULL-scene instantiation (k_render_wave_wg2<HomogeneousMedium>) instead of the
-// per-lane kernel; VSPG_KERNEL=lane keeps the per-lane kernel (tests compare the two).
-static bool uses_wg_full(const VspgRenderer *r) {
-    const char *kenv = kernel_env();
-    if (kenv && strcmp(kenv, "wg") != 0) return false;
-    return r->scene.medium.type == VSPG_MEDIUM_HOMOGENEOUS && !wants_guiding(r->prm) && !scene_is_simple(r);
-}
-static bool uses_wg_kernel(const VspgRenderer *r) {
-    const bool grid = r->scene.medium.type == VSPG_MEDIUM_GRID;
-    const bool nvdb = r->scene.medium.type == VSPG_MEDIUM_NANOVDB;
-    const bool guided = wants_guiding(r->prm);
-    if (uses_wg_guided(r)) return true;
-    if (uses_wg_full(r)) return true;
-    const char *kenv = kernel_env();
-    const bool want_wg = kenv ? strcmp(kenv, "wg") == 0 : !grid;
-    // (the TrBuffer's running mean needs a pixel's samples in order: the per-lane kernel owns a pixel per launch)
-    // triangle hits carry a per-hit error bound the LDS pool record has no room for, and the kernel's homogeneous instantiations
-    // are built for rectangle scenes with area lights only (HomogeneousMediumT::kSimpleScene)
-    if (r->hscene.n_tris > 0 || r->hscene.n_inf > 0 || has_boundaries_or_spheres(r)) return false;
-    if (r->hscene.lsamp.mode != VSPG_LIGHTSAMPLER_UNIFORM) return false;  // power / BVH picks of a multi-light scene: the full-scene kernels
-    // (a temperature grid's blackbody emission needs the path's wavelength sample, which k_render_wave_wg's pool record does not carry)
-    if (grid && r->hscene.temperature) return false;
-    return !guided && !nvdb && want_wg && !(kenv && strcmp(kenv, "lane") == 0) && !(r->hscene.tr_calc && grid);
-}
-// "wf" = the multi-kernel wavefront pipeline (vspg_wavefront.h): heterogeneous media whose every segment runs the
-// resampling routine (the reference's default vspsamplingmethod), unguided.  Default for those; VSPG_KERNEL=lane|wg
-// selects the single-kernel schedulers instead (kept for the guided / NDS configurations and as cross-checks).
-static bool uses_wf_pipeline(const VspgRenderer *r) {
-    const bool het = r->scene.medium.type == VSPG_MEDIUM_GRID || r->scene.medium.type == VSPG_MEDIUM_NANOVDB;
-    const char *kenv = kernel_env();
-    if (kenv && strcmp(kenv, "wf") != 0) return false;
-    // guided builds too, training passes included (segment recording in the dense kernels), guided Russian roulette (round 3:
-    // the vertex kernel reads the pixel's contribution estimate) and, in its own shape, NDS / NDS+ (k_wf_segment_vertex)
-    return het;
-}
-// Which scheduler of the workgroup kernel: k_render_wave_wg2 (tiles from a global head, samples parked and
-// resolved by the next launch, two barriers) serves every homogeneous configuration since round 3 -- with the shared tile head it
-// beat k_render_wave_wg (film flush between the phases, three barriers) on the unguided workload too (0.776 against 0.808 ms);
-// VSPG_WG_SCHED=1 selects k_render_wave_wg for the unguided instantiations (tests compare the two), grid media under
-// VSPG_KERNEL=wg stay on it.
-static bool uses_wg2(const VspgRenderer *r) {
-    if (!uses_wg_kernel(r) || r->scene.medium.type == VSPG_MEDIUM_GRID) return false;
-    if (uses_wg_guided(r) || uses_wg_full(r)) return true;
-    const char *e = getenv("VSPG_WG_SCHED");
-    return !(e && e[0] == '1');
-}
-// Round 5: the barrier-free scheduler (k_render_wave_wg3, vspg_wg3.h: ring queues in LDS, every wavefront its own scheduler) serves
-// whatever k_render_wave_wg2 served; VSPG_WG_SCHED=2 keeps k_render_wave_wg2 (tests compare the three schedulers).
-// It lives on the pool's slack over the workgroup's lanes (HISTORY round 5), which the larger records do not leave: the guided /
-// training instantiations (544 / 448 paths for 512 lanes: reference-default trained wave 1.45 ms against 1.42) and the full-scene one
-// (512) stay on k_render_wave_wg2.
-static bool uses_wg3(const VspgRenderer *r) {
-    if (!uses_wg2(r) || uses_wg_guided(r) || uses_wg_full(r)) return false;
-    const char *e = getenv("VSPG_WG_SCHED");
-    return !(e && e[0] == '2');
-}
-static bool arith_covered(const VspgRenderer *r) {
-    if (kernel_env() || getenv("VSPG_WG_SCHED")) return false;  // (the cross-check kernels exist in exact arithmetic only)
-    if (wants_guiding(r->prm) || r->hscene.tr_calc) return false;
-    if (uses_wf_pipeline(r))
-        return r->scene.medium.type == VSPG_MEDIUM_GRID && r->prm.vspsamplingmethod == VSPG_VSP_RESAMPLING && r->hscene.temperature == nullptr;
-    return uses_wg3(r) && !uses_wg_guided(r) && !uses_wg_full(r);
+// Which path kernel serves a renderer: choose_kernel (vspg_kernel_choice.h) decides from these facts and the process environment, afresh at
+// every entry point; what a renderer reports and what it launches come from that one record.  Nothing else reads the renderer for it.
+static ChoiceFacts choice_facts(const VspgRenderer *r) {
+    ChoiceFacts f;
+    f.medium_type = r->scene.medium.type;
+    f.n_tris = r->hscene.n_tris, f.n_inf = r->hscene.n_inf, f.n_spheres = r->hscene.n_spheres;
+    f.has_boundaries = r->hscene.has_boundaries != 0;
+    f.lightsampler = r->hscene.lsamp.mode;
+    f.medium_grey = r->medium_grey, f.surfaces_grey = r->surfaces_grey, f.null_zero = r->null_zero;
+    f.guided = wants_guiding(r->prm), f.rrguiding = r->prm.rrguiding != 0, f.training = r->training;
+    f.tr_calc = r->hscene.tr_calc != 0, f.has_temperature = r->hscene.temperature != nullptr;
+    f.resampling = r->prm.vspsamplingmethod == VSPG_VSP_RESAMPLING;
+    return f;
 }
 // The samples a one-sample wg2 launch parked are resolved by the next such launch; anything else that reads or writes the film or
 // the image-space statistics calls this first (VSPG_WG2_DEFER=0: every launch resolves its own samples at once).
@@ -3290,22 +3210,22 @@ static int flush_parked_samples(VspgRenderer *r, hipStream_t s) {
     r->ws_parked = false;
     return 0;
 }
-static const char *kernel_name_exact(VspgRenderer *r);
 const char *vspg_renderer_kernel_name(VspgRenderer *r) {
     if (!r) return "";
-    if (r->arith == VSPG_ARITH_EXACT) return kernel_name_exact(r);
-    r->kernel_name_buf = std::string(r->arith == VSPG_ARITH_FAST_WEIGHTS ? "fastw::" : "fast::") + kernel_name_exact(r);  // (the inline namespace of vspg_fast.hip's symbols)
+    // (the tolerance modes: the inline namespace of vspg_fast.hip's symbols)
+    r->kernel_name_buf = std::string(r->arith == VSPG_ARITH_EXACT ? "" : r->arith == VSPG_ARITH_FAST_WEIGHTS ? "fastw::" : "fast::") +
+                         kernel_name(choose_kernel(choice_facts(r), read_choice_env()));
     return r->kernel_name_buf.c_str();
 }
 // Which instantiations a renderer's path kernels are launched from (vspg_arith.h).  The tolerance modes exist for the unguided
 // rectangle-scene workgroup kernel and the unguided resampling pipeline over GridMedium; anything else is refused by name.
-static bool arith_covered(const VspgRenderer *r);
 int vspg_renderer_set_arithmetic(VspgRenderer *r, int mode) {
     if (!r) return fail(VSPG_EINVAL, "null renderer");
     if (mode != VSPG_ARITH_EXACT && mode != VSPG_ARITH_FAST_WEIGHTS && mode != VSPG_ARITH_FAST) return fail(VSPG_EINVAL, "unknown arithmetic mode");
-    if (mode != VSPG_ARITH_EXACT && !arith_covered(r))
+    const KernelChoice c = choose_kernel(choice_facts(r), read_choice_env());
+    if (mode != VSPG_ARITH_EXACT && !c.arith_covered)
         return fail(VSPG_ESCOPE, "the tolerance-mode instantiations cover unguided renders of rectangle scenes over a homogeneous medium and unguided "
-                                 "\"resampling\" renders over a uniformgrid medium (this renderer runs " + std::string(kernel_name_exact(r)) + ")");
+                                 "\"resampling\" renders over a uniformgrid medium (this renderer runs " + kernel_name(c) + ")");
     if (mode != r->arith && r->carry_pending) {  // (paths in flight end in the arithmetic they started in)
         HIPCHK(hipSetDevice(r->cfg.device));
         if (const int rc = drain_carried_paths(r, r->ws_stream)) return rc;
@@ -3314,53 +3234,6 @@ int vspg_renderer_set_arithmetic(VspgRenderer *r, int mode) {
     return 0;
 }
 int vspg_renderer_get_arithmetic(VspgRenderer *r) { return r ? r->arith : VSPG_EINVAL; }
-static const char *kernel_name_exact(VspgRenderer *r) {
-    const bool grid = r->scene.medium.type == VSPG_MEDIUM_GRID, nvdb = r->scene.medium.type == VSPG_MEDIUM_NANOVDB;
-    const bool guided = wants_guiding(r->prm);
-    if (uses_wf_pipeline(r) && r->prm.vspsamplingmethod != VSPG_VSP_RESAMPLING) {
-        if (guided && r->training) return nvdb ? "k_wf_segment_vertex<NanoDenseMedium,guided,train>" : "k_wf_segment_vertex<GridMedium,guided,train>";
-        if (guided) return nvdb ? "k_wf_segment_vertex<NanoDenseMedium,guided>" : "k_wf_segment_vertex<GridMedium,guided>";
-        return nvdb ? (r->medium_grey ? "k_wf_segment_vertex<NanoDenseMediumGrey>" : "k_wf_segment_vertex<NanoDenseMedium>")
-                    : (r->medium_grey ? "k_wf_segment_vertex<GridMediumGrey>" : "k_wf_segment_vertex<GridMedium>");
-    }
-    if (uses_wf_pipeline(r)) {
-        // the pipeline is named by its walk kernel: k_wf_dist_walk (beside k_wf_shadow_walk), or k_wf_walk where one kernel runs both
-        const char *n = guided && r->training ? (nvdb ? "k_wf_dist_walk<NanoDenseMedium,guided,train>" : "k_wf_dist_walk<GridMedium,guided,train>")
-                        : guided ? (nvdb ? "k_wf_dist_walk<NanoDenseMedium,guided>" : "k_wf_dist_walk<GridMedium,guided>")
-                        : nvdb ? (r->medium_grey ? "k_wf_dist_walk<NanoDenseMediumGrey>" : "k_wf_dist_walk<NanoDenseMedium>")
-                               : (r->medium_grey ? "k_wf_dist_walk<GridMediumGrey>" : "k_wf_dist_walk<GridMedium>");
-        if (!wf_merged_walks(r, guided)) return n;
-        r->kernel_name_buf2 = std::string("k_wf_walk") + (n + sizeof("k_wf_dist_walk") - 1);
-        return r->kernel_name_buf2.c_str();
-    }
-    const bool w3 = uses_wg3(r);
-    if (uses_wg_guided(r)) {
-        if (r->training) return guided_grey_simple(r) ? (w3 ? "k_render_wave_wg3<HomogeneousMediumT<2,true>,guided,train>" : "k_render_wave_wg2<HomogeneousMediumT<2,true>,guided,train>")
-                                                      : (w3 ? "k_render_wave_wg3<HomogeneousMedium,guided,train>" : "k_render_wave_wg2<HomogeneousMedium,guided,train>");
-        return guided_grey_simple(r) ? (w3 ? "k_render_wave_wg3<HomogeneousMediumT<2,true>,guided>" : "k_render_wave_wg2<HomogeneousMediumT<2,true>,guided>")
-                                     : (w3 ? "k_render_wave_wg3<HomogeneousMedium,guided>" : "k_render_wave_wg2<HomogeneousMedium,guided>");
-    }
-    if (uses_wg_full(r)) return w3 ? "k_render_wave_wg3<HomogeneousMedium>" : "k_render_wave_wg2<HomogeneousMedium>";
-    if (uses_wg_kernel(r) && uses_wg2(r)) {
-        if (r->medium_grey && r->surfaces_grey && r->null_zero) return w3 ? "k_render_wave_wg3<HomogeneousMediumT<2,true>>" : "k_render_wave_wg2<HomogeneousMediumT<2,true>>";
-        if (r->medium_grey && r->surfaces_grey) return w3 ? "k_render_wave_wg3<HomogeneousMediumT<2,false>>" : "k_render_wave_wg2<HomogeneousMediumT<2,false>>";
-        if (r->medium_grey) return w3 ? "k_render_wave_wg3<HomogeneousMediumT<1,false>>" : "k_render_wave_wg2<HomogeneousMediumT<1,false>>";
-        return w3 ? "k_render_wave_wg3<HomogeneousMediumT<0,false>>" : "k_render_wave_wg2<HomogeneousMediumT<0,false>>";
-    }
-    if (uses_wg_kernel(r)) {
-        if (grid) return "k_render_wave_wg<GridMedium>";
-        if (r->medium_grey && r->surfaces_grey && r->null_zero) return "k_render_wave_wg<HomogeneousMediumT<2,true>>";
-        if (r->medium_grey && r->surfaces_grey) return "k_render_wave_wg<HomogeneousMediumT<2,false>>";
-        if (r->medium_grey) return "k_render_wave_wg<HomogeneousMediumT<1,false>>";
-        return "k_render_wave_wg<HomogeneousMediumT<0,false>>";
-    }
-    const bool train = guided && r->training;
-    if (nvdb) return guided ? (train ? "k_render_wave<NanoDenseMedium,guided,train>" : "k_render_wave<NanoDenseMedium,guided>") : "k_render_wave<NanoDenseMedium>";
-    if (grid) return guided ? (train ? "k_render_wave<GridMedium,guided,train>" : "k_render_wave<GridMedium,guided>")
-                            : (r->medium_grey ? "k_render_wave<GridMediumGrey>" : "k_render_wave<GridMedium>");
-    if (guided && guided_grey_simple(r)) return train ? "k_render_wave<HomogeneousMediumT<2,true>,guided,train>" : "k_render_wave<HomogeneousMediumT<2,true>,guided>";
-    return guided ? (train ? "k_render_wave<HomogeneousMedium,guided,train>" : "k_render_wave<HomogeneousMedium,guided>") : "k_render_wave<HomogeneousMedium>";
-}
 
 int vspg_render_wave(VspgRenderer *r, int wave_start, int wave_end, void *stream) {
     const RoctxRange range("vspg_render_wave");  // (around the window call's own range: traces keep the name they filter on)
@@ -3378,6 +3251,7 @@ int vspg_render_window(VspgRenderer *r, int x0, int y0, int x1, int y1, int wave
                                      ") is empty or not inside the " + std::to_string(r->cfg.xres) + " x " + std::to_string(r->cfg.yres) + " film");
     if (wave_end < wave_start || wave_start < 0) return fail(VSPG_EINVAL, "bad wave range");
     if (wave_end == wave_start) return 0;
+    const KernelChoice c = choose_kernel(choice_facts(r), read_choice_env());  // what this call launches, decided once
     HIPCHK(hipSetDevice(r->cfg.device));
     const PixelWindow win = {x0, y0, x1, y1};
     const bool whole = x0 == 0 && y0 == 0 && x1 == r->cfg.xres && y1 == r->cfg.yres;
@@ -3400,21 +3274,21 @@ int vspg_render_window(VspgRenderer *r, int x0, int y0, int x1, int y1, int wave
     if (first >= wave_end) return 0;  // nothing for this shard in the range
     const int n_samples = (wave_end - 1 - first) / sc + 1;
     const PcgJump jump = pcg_jump((unsigned long long)first * 65536ull);
-    const bool grid = r->scene.medium.type == VSPG_MEDIUM_GRID;
-    const bool nvdb = r->scene.medium.type == VSPG_MEDIUM_NANOVDB;
-    const bool guided = wants_guiding(r->prm);
-    if (guided && !r->field_set) return fail(VSPG_ESCOPE, "guiding enabled but the renderer holds no guiding field");
+    const int single = n_samples == 1 ? 1 : 0;
+    const bool wf = c.family == Family::WfWalk || c.family == Family::WfSegmentVertex;
+    const bool parks = c.family == Family::Wg2 || c.family == Family::Wg3;  // (a launch of these parks its samples, below)
+    if (c.guided && !r->field_set) return fail(VSPG_ESCOPE, "guiding enabled but the renderer holds no guiding field");
     // a one-sample launch of k_render_wave_wg2 resolves the samples its predecessor parked; every other launch adds to the film
     // itself, so the parked samples go in first
     // (a launch resolves parked samples pixel by pixel as it starts them: those of ANOTHER window go in through k_film_resolve first)
-    const bool defer = !uses_wf_pipeline(r) && uses_wg2(r) && n_samples == 1 && wg2_defer_enabled();
+    const bool defer = parks && single && wg2_defer_enabled();
     const bool same_win = r->ws_win.x0 == x0 && r->ws_win.y0 == y0 && r->ws_win.x1 == x1 && r->ws_win.y1 == y1;
     if (!defer || !same_win) { const int rc = flush_parked_samples(r, (hipStream_t)stream); if (rc) return rc; }
     // ... and a k_render_wave_wg3 launch of that kind also takes over the paths its predecessor left in flight (below); any other drains them
     // (not where the paths themselves keep a per-pixel running mean, the TrBuffer's: two samples of a pixel would be in flight at once)
-    const bool carry = defer && uses_wg3(r) && !r->hscene.tr_calc && wg3_carry_enabled();
+    const bool carry = defer && c.family == Family::Wg3 && !r->hscene.tr_calc && wg3_carry_enabled();
     if (r->carry_pending && !carry) { const int rc = drain_carried_paths(r, (hipStream_t)stream); if (rc) return rc; }
-    if (uses_wf_pipeline(r)) {  // one pass per sample index of this shard, in order
+    if (wf) {  // one pass per sample index of this shard, in order
 #ifdef VSPG_WF_DEBUG
         auto checksum = [&](const void *dptr, size_t bytes) -> unsigned long long {
             if (!dptr || !bytes) return 0ull;
@@ -3433,8 +3307,7 @@ int vspg_render_window(VspgRenderer *r, int x0, int y0, int x1, int y1, int wave
         for (int k = 0; k < 6; ++k) before[k] = checksum(bufs[k], sizes[k]);
 #endif
         for (int w = first; w < wave_end; w += sc > 1 ? sc : 1) {
-            const hipStream_t hs = (hipStream_t)stream;
-            const int rc = wf_render_pass(r, win, w, hs, nvdb, guided, guided && r->training, r->medium_grey);
+            const int rc = wf_render_pass(r, c, win, w, (hipStream_t)stream);
             if (rc) return rc;
         }
 #ifdef VSPG_WF_DEBUG
@@ -3449,7 +3322,7 @@ int vspg_render_window(VspgRenderer *r, int x0, int y0, int x1, int y1, int wave
         return 0;
     }
     // a18: while the field trains, the guided kernels record path segments and emit radiance samples
-    const bool train = guided && r->training;
+    const bool train = c.train;
     TrainArgs targs = {nullptr, nullptr, nullptr, nullptr, 0, 0};
     if (train) {
         if (n_samples > 1) {  // a training launch covers one sample per pixel (the record buffer is sized for that): split
@@ -3465,132 +3338,152 @@ int vspg_render_window(VspgRenderer *r, int x0, int y0, int x1, int y1, int wave
     // exactly one path-kernel launch follows: it uses the counter the previous launch zeroed and zeroes the other one
     unsigned int *const work_head = r->work_head + (r->head_parity & 1u);
     r->head_parity ^= 1u;
-#define VSPG_LAUNCH_RENDER(M, G)                                                                                          \
-    do {                                                                                                                  \
-        if (G && train)                                                                                                   \
-            hipLaunchKernelGGL((k_render_wave<M, G, G>), dim3((unsigned)blocks), dim3(kBlock), 0, (hipStream_t)stream,    \
-                               r->dscene, r->film, r->isg_stats, r->vsp, r->vsp_ready, wave_start, wave_end, first,        \
-                               n_samples == 1 ? 1 : 0, jump, static_per_wave, dyn_base, work_head, r->counters, targs, win); \
-        else                                                                                                              \
-            hipLaunchKernelGGL((k_render_wave<M, G, false>), dim3((unsigned)blocks), dim3(kBlock), 0, (hipStream_t)stream, \
-                               r->dscene, r->film, r->isg_stats, r->vsp, r->vsp_ready, wave_start, wave_end, first,        \
-                               n_samples == 1 ? 1 : 0, jump, static_per_wave, dyn_base, work_head, r->counters, targs, win); \
-    } while (0)
-    const bool use_wg = uses_wg_kernel(r);
-    if (use_wg) {
-        const unsigned tiles_magic = tilesX > 1 ? (unsigned)((0x100000000ull + (unsigned)tilesX - 1) / (unsigned)tilesX) : 0u;
-        const bool gwg = uses_wg_guided(r);
-        const int wwaves = gwg ? kWgWavesGuided : grid ? kWgWavesGrid : kWgWavesHomog, wblock = gwg ? kWgBlockGuided : grid ? kWgBlockGrid : kWgBlockHomog;
-        long long wblocks = (long long)r->num_cus * (wwaves * 4 / (wblock / 64));
-        const long long wmax = (items + kWgChunk - 1) / kWgChunk;
-        if (wblocks > wmax) wblocks = wmax;
-        const int single = n_samples == 1 ? 1 : 0;
-        const long long n_tiles_all = (long long)tilesX * tilesY;
-        // Two schedulers (uses_wg2): k_render_wave_wg2 (tiles from a global head, parked samples, two barriers) by default,
-        // k_render_wave_wg (film flush between the phases, three barriers) for grid media and under VSPG_WG_SCHED=1.
-        const bool sched2 = uses_wg2(r);
-        if (sched2) {
-            for (int k = 0; k < 2; ++k)
-                if (!r->wave_samples[k]) HIPCHK(hipMalloc(&r->wave_samples[k], r->npix * sizeof(float4)));
-            // CARRY (vspg_wg3.h): the pending image is resumed by a launch of the shape that wrote it, whose sample index differs from
-            // the suspended paths' (that is how the kernel tells them apart); otherwise it is drained first
-            const int wg3_grey = r->medium_grey ? (r->surfaces_grey ? 2 : 1) : 0, wg3_null_zero = r->medium_grey && r->surfaces_grey && r->null_zero ? 1 : 0;
-            if (carry && wblocks > n_tiles_all) wblocks = n_tiles_all;
-            if (r->carry_pending) {
-                const Wg3Launch &P = r->carry_shape;
-                const bool same_shape = carry && P.grey == wg3_grey && P.null_zero == wg3_null_zero && P.blocks == (unsigned)wblocks && P.windowed == (whole ? 0 : 1) &&
-                                        r->carry_arith == r->arith && P.first_sample != first && P.dscene == r->dscene;
-                if (!same_shape) { const int rc = drain_carried_paths(r, (hipStream_t)stream); if (rc) return rc; }
-            }
-            float4 *const ws_out = r->wave_samples[r->ws_cur];
-            const float4 *const ws_prev = defer && r->ws_parked ? r->wave_samples[r->ws_cur ^ 1] : nullptr;
-            if (ws_prev) { const int rc = order_after_parking(r, (hipStream_t)stream); if (rc) return rc; }
-            const long long n_tiles = n_tiles_all;
-            if (wblocks > n_tiles) wblocks = n_tiles;
-            // the share of the frame handed out from the global head, in 64ths (VSPG_WG2_TAIL; the rest is dealt to the workgroups
-            // up front, interleaved).  Measured on the reference-default guided workload / the unguided one (ms per 1080p wave):
-            // 0: 1.59 / 0.887, 8: 1.50 / 0.829, 16: 1.46 / 0.800, 32: 1.47 / 0.790, 64 (all of it): 1.454 / 0.775.
-            const int tail64 = [] { const char *e = getenv("VSPG_WG2_TAIL"); const int v = e ? atoi(e) : 64; return v < 0 ? 0 : (v > 64 ? 64 : v); }();  // (per launch: a test varies it)
-            const unsigned static_tiles = (unsigned)((n_tiles * (64 - tail64) / 64) / wblocks * wblocks);
-#define VSPG_LAUNCH_WG2(M, G, NPOOL, BLK, WV)                                                                                         \
-    hipLaunchKernelGGL((k_render_wave_wg2<M, G, NPOOL, BLK, WV>), dim3((unsigned)wblocks), dim3(BLK), 0, (hipStream_t)stream, r->dscene, \
-                       r->film, r->isg_stats, r->vsp, r->vsp_ready, wave_end, first, single, jump, tiles_magic, static_tiles, work_head, ws_prev, ws_out, r->counters, targs, win)
-            if (uses_wg3(r)) {
-                {  // the unguided rectangle-scene instantiations (the headline workload): also built in the tolerance modes
-                    static_assert(kWgBlockHomog == VSPG_WG_BLOCK && kWgWavesHomog == VSPG_WG_WAVES, "wg3_launch_unguided's launch shape");
-                    // (its tile cursors: a pair of sets of its own, alternating like the counter pair of the other kernels -- which this launch leaves alone)
-                    unsigned int *const head8 = r->work_head8 + (r->head8_parity & 1u) * (unsigned)(kWg3HeadSetBytes / 4);
-                    r->head8_parity ^= 1u;
-                    r->head_parity ^= 1u;  // (undo the toggle above: no launch used that pair)
-                    Wg3Launch L3{r->dscene, r->film, r->isg_stats, r->vsp, r->vsp_ready, wave_end, first, single, jump, tiles_magic, head8, ws_prev, ws_out,
-                                 r->counters, (unsigned)wblocks, (hipStream_t)stream, wg3_grey, wg3_null_zero, whole ? 0 : 1, win, 0, nullptr, nullptr};
-                    if (carry) {
-                        // (an image per workgroup of the largest grid a launch of this renderer can have, at the largest instantiation's size)
-                        const size_t img_bytes = (size_t)r->num_cus * (size_t)(kWgWavesHomog * 4 / (kWgBlockHomog / 64)) * (size_t)kWg3ImageStrideMax * sizeof(unsigned int);
-                        for (int k = 0; k < 2; ++k)
-                            if (!r->carry_img[k]) HIPCHK(hipMalloc(&r->carry_img[k], img_bytes));
-                        L3.carry = 1;
-                        L3.resume = r->carry_pending ? r->carry_img[r->carry_cur ^ 1] : nullptr;
-                        L3.suspend = r->carry_img[r->carry_cur];
-                    }
-                    const int lrc = wg3_launch_any(r->arith, L3);
-                    if (lrc != 0) return fail(VSPG_EHIP, std::string("k_render_wave_wg3: ") + hipGetErrorName((hipError_t)lrc));
-                    if (carry) {
-                        if (r->carry_pending) r->carry_resumes++;
-                        r->carry_cur ^= 1;
-                        r->carry_pending = true;
-                        r->carry_shape = L3;
-                        r->carry_arith = r->arith;
-                    }
-                }
-            } else
-            if (gwg && train && guided_grey_simple(r))
-                hipLaunchKernelGGL((k_render_wave_wg2<HomogeneousMediumGreySceneNullZero, true, kWg2PoolTrainT<2>, kWgBlockGuided, kWgWavesGuided, true>), dim3((unsigned)wblocks),
-                                   dim3(kWgBlockGuided), 0, (hipStream_t)stream, r->dscene, r->film, r->isg_stats, r->vsp, r->vsp_ready, wave_end, first, single, jump,
-                                   tiles_magic, static_tiles, work_head, ws_prev, ws_out, r->counters, targs, win);
-            else if (gwg && train)
-                hipLaunchKernelGGL((k_render_wave_wg2<HomogeneousMediumSimple, true, kWg2PoolTrainT<0>, kWgBlockGuided, kWgWavesGuided, true>), dim3((unsigned)wblocks),
-                                   dim3(kWgBlockGuided), 0, (hipStream_t)stream, r->dscene, r->film, r->isg_stats, r->vsp, r->vsp_ready, wave_end, first, single, jump,
-                                   tiles_magic, static_tiles, work_head, ws_prev, ws_out, r->counters, targs, win);
-            else if (gwg && guided_grey_simple(r)) VSPG_LAUNCH_WG2(HomogeneousMediumGreySceneNullZero, true, kWg2PoolGuidedT<2>, kWgBlockGuided, kWgWavesGuided);
-            else if (gwg) VSPG_LAUNCH_WG2(HomogeneousMediumSimple, true, kWg2PoolGuidedT<0>, kWgBlockGuided, kWgWavesGuided);
-            else if (uses_wg_full(r)) VSPG_LAUNCH_WG2(HomogeneousMedium, false, kWg2PoolFull, kWgBlockHomog, kWgWavesHomog);
-            else if (r->medium_grey && r->surfaces_grey && r->null_zero) VSPG_LAUNCH_WG2(HomogeneousMediumGreySceneNullZero, false, kWg2PoolHomogT<2>, kWgBlockHomog, kWgWavesHomog);
-            else if (r->medium_grey && r->surfaces_grey) VSPG_LAUNCH_WG2(HomogeneousMediumGreyScene, false, kWg2PoolHomogT<2>, kWgBlockHomog, kWgWavesHomog);
-            else if (r->medium_grey) VSPG_LAUNCH_WG2(HomogeneousMediumGrey, false, kWg2PoolHomogT<1>, kWgBlockHomog, kWgWavesHomog);
-            else VSPG_LAUNCH_WG2(HomogeneousMediumSimple, false, kWg2PoolHomogT<0>, kWgBlockHomog, kWgWavesHomog);
-#undef VSPG_LAUNCH_WG2
-            HIPCHK(hipGetLastError());
-            if (single) {  // this launch's samples are parked in ws_out (its predecessor's, if any were, have just been resolved)
-                r->ws_cur ^= 1;
-                r->ws_parked = true;
-                r->ws_win = win;
-                r->ws_stream = (hipStream_t)stream;
-                if (!r->ws_event) HIPCHK(hipEventCreateWithFlags(&r->ws_event, hipEventDisableTiming));
-                HIPCHK(hipEventRecord(r->ws_event, (hipStream_t)stream));
-                if (!defer) { const int rc = flush_parked_samples(r, (hipStream_t)stream); if (rc) return rc; }
-            }
-        } else {
-#define VSPG_LAUNCH_WG(M, NPOOL, BLK, WV)                                                                                            \
-    hipLaunchKernelGGL((k_render_wave_wg<M, false, NPOOL, BLK, WV>), dim3((unsigned)wblocks), dim3(BLK), 0, (hipStream_t)stream, r->dscene, \
-                       r->film, r->isg_stats, r->vsp, r->vsp_ready, wave_end, first, single, jump, tiles_magic, work_head, r->counters, win)
-            if (grid) VSPG_LAUNCH_WG(GridMedium, kWgPoolGrid, kWgBlockGrid, kWgWavesGrid);
-            else if (r->medium_grey && r->surfaces_grey && r->null_zero) VSPG_LAUNCH_WG(HomogeneousMediumGreySceneNullZero, kWgPoolHomogT<2>, kWgBlockHomog, kWgWavesHomog);  // ... and the null-collision coefficient is exactly 0
-            else if (r->medium_grey && r->surfaces_grey) VSPG_LAUNCH_WG(HomogeneousMediumGreyScene, kWgPoolHomogT<2>, kWgBlockHomog, kWgWavesHomog);  // ... and every Kd bitwise grey: beta is grey by construction too
-            else if (r->medium_grey) VSPG_LAUNCH_WG(HomogeneousMediumGrey, kWgPoolHomogT<1>, kWgBlockHomog, kWgWavesHomog);  // sigma_a, sigma_s, Le bitwise grey: the broadcast-spectrum instantiation
-            else VSPG_LAUNCH_WG(HomogeneousMediumSimple, kWgPoolHomogT<0>, kWgBlockHomog, kWgWavesHomog);
-#undef VSPG_LAUNCH_WG
+    // the workgroup kernels' grid (k_render_wave_wg / _wg2 / _wg3)
+    const unsigned tiles_magic = tilesX > 1 ? (unsigned)((0x100000000ull + (unsigned)tilesX - 1) / (unsigned)tilesX) : 0u;
+    const bool wgrid = c.medium == MediumInst::Grid;
+    const int wwaves = c.wg_guided ? kWgWavesGuided : wgrid ? kWgWavesGrid : kWgWavesHomog, wblock = c.wg_guided ? kWgBlockGuided : wgrid ? kWgBlockGrid : kWgBlockHomog;
+    long long wblocks = (long long)r->num_cus * (wwaves * 4 / (wblock / 64));
+    const long long wmax = (items + kWgChunk - 1) / kWgChunk;
+    if (wblocks > wmax) wblocks = wmax;
+    // Two schedulers park their samples (k_render_wave_wg2: tiles from a global head, two barriers; k_render_wave_wg3: barrier-free):
+    // a launch writes its samples to ws_out and resolves those its predecessor left in ws_prev
+    float4 *ws_out = nullptr;
+    const float4 *ws_prev = nullptr;
+    const int wg3_grey = r->medium_grey ? (r->surfaces_grey ? 2 : 1) : 0, wg3_null_zero = r->medium_grey && r->surfaces_grey && r->null_zero ? 1 : 0;
+    if (parks) {
+        for (int k = 0; k < 2; ++k)
+            if (!r->wave_samples[k]) HIPCHK(hipMalloc(&r->wave_samples[k], r->npix * sizeof(float4)));
+        const long long n_tiles = (long long)tilesX * tilesY;
+        if (wblocks > n_tiles) wblocks = n_tiles;
+        // CARRY (vspg_wg3.h): the pending image is resumed by a launch of the shape that wrote it, whose sample index differs from
+        // the suspended paths' (that is how the kernel tells them apart); otherwise it is drained first
+        if (r->carry_pending) {
+            const Wg3Launch &P = r->carry_shape;
+            const bool same_shape = carry && P.grey == wg3_grey && P.null_zero == wg3_null_zero && P.blocks == (unsigned)wblocks && P.windowed == (whole ? 0 : 1) &&
+                                    r->carry_arith == r->arith && P.first_sample != first && P.dscene == r->dscene;
+            if (!same_shape) { const int rc = drain_carried_paths(r, (hipStream_t)stream); if (rc) return rc; }
         }
-    } else if (nvdb && guided) VSPG_LAUNCH_RENDER(NanoDenseMedium, true);
-    else if (nvdb) VSPG_LAUNCH_RENDER(NanoDenseMedium, false);
-    else if (grid && guided) VSPG_LAUNCH_RENDER(GridMedium, true);
-    else if (grid && r->medium_grey) VSPG_LAUNCH_RENDER(GridMediumGrey, false);
-    else if (grid) VSPG_LAUNCH_RENDER(GridMedium, false);
-    else if (guided && guided_grey_simple(r)) VSPG_LAUNCH_RENDER(HomogeneousMediumGreySceneNullZero, true);
-    else if (guided) VSPG_LAUNCH_RENDER(HomogeneousMedium, true);
-    else VSPG_LAUNCH_RENDER(HomogeneousMedium, false);
-#undef VSPG_LAUNCH_RENDER
+        ws_out = r->wave_samples[r->ws_cur];
+        ws_prev = defer && r->ws_parked ? r->wave_samples[r->ws_cur ^ 1] : nullptr;
+        if (ws_prev) { const int rc = order_after_parking(r, (hipStream_t)stream); if (rc) return rc; }
+    }
+    using NullZero = HomogeneousMediumGreySceneNullZero;
+    const auto not_built = [&] { return fail(VSPG_ESCOPE, "internal: no instantiation " + kernel_name(c) + " is built"); };
+    switch (c.family) {
+    case Family::Lane: {
+        const auto launch = [&](auto inst) {
+            using I = decltype(inst);
+            hipLaunchKernelGGL((k_render_wave<typename I::Medium, I::guided, I::train>), dim3((unsigned)blocks), dim3(kBlock), 0, (hipStream_t)stream, r->dscene,
+                               r->film, r->isg_stats, r->vsp, r->vsp_ready, wave_start, wave_end, first, single, jump, static_per_wave, dyn_base, work_head,
+                               r->counters, targs, win);
+        };
+        // (a medium's unguided, guided and guided + training builds)
+        const auto launch_guided_or_not = [&](auto inst) {
+            using M = typename decltype(inst)::Medium;
+            if (c.train) launch(KernelInst<M, true, true>{});
+            else if (c.guided) launch(KernelInst<M, true>{});
+            else launch(KernelInst<M>{});
+        };
+        switch (c.medium) {
+        case MediumInst::NanoDense: launch_guided_or_not(KernelInst<NanoDenseMedium>{}); break;
+        case MediumInst::Grid: launch_guided_or_not(KernelInst<GridMedium>{}); break;
+        case MediumInst::GridGrey: launch(KernelInst<GridMediumGrey>{}); break;
+        case MediumInst::Homogeneous: launch_guided_or_not(KernelInst<HomogeneousMedium>{}); break;
+        case MediumInst::HomogeneousGreySceneNullZero:  // (guided renders only)
+            if (c.train) launch(KernelInst<NullZero, true, true>{});
+            else launch(KernelInst<NullZero, true>{});
+            break;
+        default: return not_built();
+        }
+        break;
+    }
+    case Family::Wg: {  // (film flush between the phases, three barriers: grid media under VSPG_KERNEL=wg, and VSPG_WG_SCHED=1)
+        const auto launch = [&](auto inst) {
+            using I = decltype(inst);
+            hipLaunchKernelGGL((k_render_wave_wg<typename I::Medium, false, I::pool, I::block, I::waves>), dim3((unsigned)wblocks), dim3(I::block), 0,
+                               (hipStream_t)stream, r->dscene, r->film, r->isg_stats, r->vsp, r->vsp_ready, wave_end, first, single, jump, tiles_magic, work_head,
+                               r->counters, win);
+        };
+        switch (c.medium) {
+        case MediumInst::Grid: launch(KernelInst<GridMedium, false, false, kWgPoolGrid, kWgBlockGrid, kWgWavesGrid>{}); break;
+        case MediumInst::HomogeneousGreySceneNullZero: launch(WgHomogInst<NullZero, kWgPoolHomogT<2>>{}); break;
+        case MediumInst::HomogeneousGreyScene: launch(WgHomogInst<HomogeneousMediumGreyScene, kWgPoolHomogT<2>>{}); break;
+        case MediumInst::HomogeneousGrey: launch(WgHomogInst<HomogeneousMediumGrey, kWgPoolHomogT<1>>{}); break;
+        case MediumInst::HomogeneousSimple: launch(WgHomogInst<HomogeneousMediumSimple, kWgPoolHomogT<0>>{}); break;
+        default: return not_built();
+        }
+        break;
+    }
+    case Family::Wg2: {
+        // the share of the frame handed out from the global head, in 64ths (VSPG_WG2_TAIL; the rest is dealt to the workgroups
+        // up front, interleaved).  Measured on the reference-default guided workload / the unguided one (ms per 1080p wave):
+        // 0: 1.59 / 0.887, 8: 1.50 / 0.829, 16: 1.46 / 0.800, 32: 1.47 / 0.790, 64 (all of it): 1.454 / 0.775.
+        const int tail64 = [] { const char *e = getenv("VSPG_WG2_TAIL"); const int v = e ? atoi(e) : 64; return v < 0 ? 0 : (v > 64 ? 64 : v); }();  // (per launch: a test varies it)
+        const unsigned static_tiles = (unsigned)(((long long)tilesX * tilesY * (64 - tail64) / 64) / wblocks * wblocks);
+        const auto launch = [&](auto inst) {
+            using I = decltype(inst);
+            hipLaunchKernelGGL((k_render_wave_wg2<typename I::Medium, I::guided, I::pool, I::block, I::waves, I::train>), dim3((unsigned)wblocks), dim3(I::block), 0,
+                               (hipStream_t)stream, r->dscene, r->film, r->isg_stats, r->vsp, r->vsp_ready, wave_end, first, single, jump, tiles_magic, static_tiles,
+                               work_head, ws_prev, ws_out, r->counters, targs, win);
+        };
+        switch (c.medium) {
+        case MediumInst::HomogeneousGreySceneNullZero:
+            if (c.train) launch(WgGuidedInst<NullZero, kWg2PoolTrainT<2>, true>{});
+            else if (c.guided) launch(WgGuidedInst<NullZero, kWg2PoolGuidedT<2>>{});
+            else launch(WgHomogInst<NullZero, kWg2PoolHomogT<2>>{});
+            break;
+        case MediumInst::HomogeneousSimple:
+            if (c.train) launch(WgGuidedInst<HomogeneousMediumSimple, kWg2PoolTrainT<0>, true>{});
+            else if (c.guided) launch(WgGuidedInst<HomogeneousMediumSimple, kWg2PoolGuidedT<0>>{});
+            else launch(WgHomogInst<HomogeneousMediumSimple, kWg2PoolHomogT<0>>{});
+            break;
+        case MediumInst::HomogeneousGreyScene: launch(WgHomogInst<HomogeneousMediumGreyScene, kWg2PoolHomogT<2>>{}); break;
+        case MediumInst::HomogeneousGrey: launch(WgHomogInst<HomogeneousMediumGrey, kWg2PoolHomogT<1>>{}); break;
+        case MediumInst::Homogeneous: launch(WgHomogInst<HomogeneousMedium, kWg2PoolFull>{}); break;  // (the full-scene instantiation)
+        default: return not_built();
+        }
+        break;
+    }
+    case Family::Wg3: {  // the unguided rectangle-scene instantiations (the headline workload): also built in the tolerance modes
+        static_assert(kWgBlockHomog == VSPG_WG_BLOCK && kWgWavesHomog == VSPG_WG_WAVES, "wg3_launch_unguided's launch shape");
+        // (its tile cursors: a pair of sets of its own, alternating like the counter pair of the other kernels -- which this launch leaves alone)
+        unsigned int *const head8 = r->work_head8 + (r->head8_parity & 1u) * (unsigned)(kWg3HeadSetBytes / 4);
+        r->head8_parity ^= 1u;
+        r->head_parity ^= 1u;  // (undo the toggle above: no launch used that pair)
+        Wg3Launch L3{r->dscene, r->film, r->isg_stats, r->vsp, r->vsp_ready, wave_end, first, single, jump, tiles_magic, head8, ws_prev, ws_out,
+                     r->counters, (unsigned)wblocks, (hipStream_t)stream, wg3_grey, wg3_null_zero, whole ? 0 : 1, win, 0, nullptr, nullptr};
+        if (carry) {
+            // (an image per workgroup of the largest grid a launch of this renderer can have, at the largest instantiation's size)
+            const size_t img_bytes = (size_t)r->num_cus * (size_t)(kWgWavesHomog * 4 / (kWgBlockHomog / 64)) * (size_t)kWg3ImageStrideMax * sizeof(unsigned int);
+            for (int k = 0; k < 2; ++k)
+                if (!r->carry_img[k]) HIPCHK(hipMalloc(&r->carry_img[k], img_bytes));
+            L3.carry = 1;
+            L3.resume = r->carry_pending ? r->carry_img[r->carry_cur ^ 1] : nullptr;
+            L3.suspend = r->carry_img[r->carry_cur];
+        }
+        const int lrc = wg3_launch_any(r->arith, L3);  // (wg3_launch_unguided picks the grey / null-zero instantiation, vspg_wg3.h)
+        if (lrc != 0) return fail(VSPG_EHIP, std::string("k_render_wave_wg3: ") + hipGetErrorName((hipError_t)lrc));
+        if (carry) {
+            if (r->carry_pending) r->carry_resumes++;
+            r->carry_cur ^= 1;
+            r->carry_pending = true;
+            r->carry_shape = L3;
+            r->carry_arith = r->arith;
+        }
+        break;
+    }
+    default: return not_built();
+    }
     HIPCHK(hipGetLastError());
+    if (parks && single) {  // this launch's samples are parked in ws_out (its predecessor's, if any were, have just been resolved)
+        r->ws_cur ^= 1;
+        r->ws_parked = true;
+        r->ws_win = win;
+        r->ws_stream = (hipStream_t)stream;
+        if (!r->ws_event) HIPCHK(hipEventCreateWithFlags(&r->ws_event, hipEventDisableTiming));
+        HIPCHK(hipEventRecord(r->ws_event, (hipStream_t)stream));
+        if (!defer) { const int rc = flush_parked_samples(r, (hipStream_t)stream); if (rc) return rc; }
+    }
     if (train) {
         hipLaunchKernelGGL(k_propagate, dim3((unsigned)((items + kBlock - 1) / kBlock)), dim3(kBlock), 0, (hipStream_t)stream, targs,
                            train_rec_capacity(r->prm.maxdepth));
