@@ -433,9 +433,9 @@ int vspg_renderer_get_arithmetic(VspgRenderer *r);
  * vspg_reset_counters, vspg_renderer_set_arithmetic, the buffer setters, the due update of vspg_post_process_step -- finish them
  * first (one short launch on the call's stream); vspg_renderer_destroy drops them.  VSPG_WG3_CARRY=0 in the environment (read
  * per wave) makes every wave finish its own paths.
- * vspg_film_error_enqueue (below) reads the film and belongs to this list: it finishes parked samples and suspended paths first, on
- * its stream, so its record is of the COMPLETE film -- a host that records after every wave therefore gives up the carry of
- * in-flight paths between waves (every wave is followed by the short drain launch). */
+ * vspg_film_error_enqueue and vspg_film_resolve (below) read the film and belong to this list: each finishes parked samples and
+ * suspended paths first, on its stream, so its record or image is of the COMPLETE film -- a host that records or writes an image after
+ * every wave therefore gives up the carry of in-flight paths between waves (every wave is followed by the short drain launch). */
 int vspg_flush(VspgRenderer *r, void *stream);
 int vspg_film_device_ptr(VspgRenderer *r, float **dev_ptr, size_t *n_floats);
 int vspg_film_read(VspgRenderer *r, float *host_rgbw /* W*H*4 */, void *stream);
@@ -477,6 +477,25 @@ int vspg_film_error_enqueue(VspgRenderer *r, int x0, int y0, int x1, int y1, int
 /* Synchronises `stream`, copies the records in enqueue order and empties the log.  max_records smaller than the log's content:
  * VSPG_EINVAL, log untouched. */
 int vspg_film_error_read(VspgRenderer *r, VspgFilmError *out, size_t max_records, size_t *n_out, void *stream);
+
+/* The film resolved to pixel values on the device: what RGBFilm::GetImage hands RGBFilm::WriteImage (src/pbrt/film.cpp:531-569), over
+ * the window [x0,x1) x [y0,y1) (vspg_render_window's rules: strict, VSPG_EINVAL otherwise).  Per pixel and channel
+ *   v_c = w != 0 ? sum_c / w : sum_c      (RGBFilm::GetPixelRGB, film.h:269-287: one float division, no colour transform).
+ * VSPG_RESOLVE_F32 stores v_c unchanged; *n_clamped is 0.  VSPG_RESOLVE_F16 stores Half(v_c) (util/float.h:417-463: round to nearest
+ * even, subnormal halves, >= 65520 to +-inf, any NaN to 0x7e00 | sign) after the clamp of film.cpp:544-556: with m = r; if (m < g) m = g;
+ * if (m < b) m = b; -- std::max({r,g,b}), NaN behaviour included -- iff m > 65504 every channel > 65504 becomes 65504 and the pixel
+ * counts once in *n_clamped ("%d pixel values clamped to maximum fp16 value.").  Negative overflow is not clamped: -inf.
+ * out_bytes must be (x1-x0)*(y1-y0)*3*(2|4), else VSPG_EINVAL with nothing written.  It belongs to the calls that finish parked
+ * samples and suspended paths first (above), on `stream`, and synchronises `stream` like vspg_film_read.  The first call allocates a
+ * staging buffer of xres*yres*12 bytes and a 4-byte counter, freed at destroy; a renderer that never calls it allocates and launches
+ * nothing.  6 (or 12) bytes per pixel cross to the host instead of vspg_film_read's 16, and in the scan-line layout they are an
+ * OpenEXR scan-line block's payload as they stand (channels sorted by name: B, G, R). */
+#define VSPG_RESOLVE_F32 0
+#define VSPG_RESOLVE_F16 1
+#define VSPG_RESOLVE_RGB 0           /* interleaved R,G,B per pixel, rows top first: pbrt's Image memory layout */
+#define VSPG_RESOLVE_SCANLINE_BGR 1  /* per row: the row's B values, then its G values, then its R values: an EXR scan line of channels B,G,R */
+int vspg_film_resolve(VspgRenderer *r, int x0, int y0, int x1, int y1, int format, int layout,
+                      void *host_out, size_t out_bytes, uint64_t *n_clamped /* or NULL */, void *stream);
 
 /* Image-space VSP buffer (stands in for openpgl ImageSpaceGuidingBuffer,
  * guidedvolpathvspgintegrator.cpp:161-178, 1098-1112). */

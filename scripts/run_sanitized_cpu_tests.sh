@@ -7,6 +7,8 @@ make -C oracle asan
 make -C vspg-pbrt-v4_amd/host asan
 echo "== host_selftest under ASan/UBSan"
 ASAN_OPTIONS=detect_leaks=1 ./vspg-pbrt-v4_amd/host/host_selftest_asan
+echo "== the image codec (host/vspg_image.cpp) under ASan/UBSan: tests/test_exr_host.py through vspg_imgtool_asan"
+VSPG_IMGTOOL=$PWD/vspg-pbrt-v4_amd/host/vspg_imgtool_asan ASAN_OPTIONS=detect_leaks=1 python -m pytest tests/test_exr_host.py -x -q -p no:cacheprovider
 echo "== pytest -m 'not gpu' with liboracle_asan.so"
 LIBASAN=$(gcc -print-file-name=libasan.so)
 # python itself is not instrumented: preload the runtime, leak checking off (the interpreter never frees everything)

@@ -232,6 +232,9 @@ class VspgBrickInfo(C.Structure):
                 ("n_stored", C.c_uint64), ("index_bytes", C.c_uint64), ("octet_bytes", C.c_uint64)]
 
 
+RESOLVE_F32, RESOLVE_F16 = 0, 1           # VSPG_RESOLVE_*: the format ...
+RESOLVE_RGB, RESOLVE_SCANLINE_BGR = 0, 1  # ... and the layout of vspg_film_resolve
+
 # every symbol include/vspg.h declares: (name, restype, argtypes)
 _P = C.POINTER
 _vp = C.c_void_p
@@ -262,6 +265,7 @@ SYMBOLS = [
     ("vspg_renderer_set_reference_image", C.c_int, [_vp, _P(C.c_float), _vp]),
     ("vspg_film_error_enqueue", C.c_int, [_vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _vp]),
     ("vspg_film_error_read", C.c_int, [_vp, _P(VspgFilmError), C.c_size_t, _P(C.c_size_t), _vp]),
+    ("vspg_film_resolve", C.c_int, [_vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _vp, C.c_size_t, _P(C.c_uint64), _vp]),
     ("vspg_vsp_buffer_device_ptr", C.c_int, [_vp, _P(_vp), _P(C.c_size_t)]),
     ("vspg_vsp_buffer_read", C.c_int, [_vp, _P(C.c_float), _P(C.c_int), _vp]),
     ("vspg_vsp_buffer_load", C.c_int, [_vp, _P(C.c_float), _vp]),
@@ -639,6 +643,23 @@ class Renderer:
         n = C.c_size_t()
         _check(self.lib, self.lib.vspg_film_error_read(self.h, buf, FILM_ERROR_LOG_RECORDS, C.byref(n), _vp(stream or 0)))
         return [FilmError.from_c(buf[i]) for i in range(n.value)]
+
+    def film_resolve(self, window=None, half=True, layout="rgb", stream=None):
+        """The film's pixel values over window = (x0, y0, x1, y1) (default: the frame), resolved on the device (vspg_film_resolve):
+        sum / weight per channel, for half=True clamped to the largest finite half and converted like the reference's Half(float).
+        Returns (array, n_clamped): the array is float16 or float32, (h, w, 3) in R,G,B order for layout "rgb", (h, 3, w) in
+        B,G,R order for layout "scanline" -- the payload of an OpenEXR scan-line block, row by row."""
+        import numpy as np
+        x0, y0, x1, y1 = (int(v) for v in (window if window is not None else (0, 0, self.xres, self.yres)))
+        if layout not in ("rgb", "scanline"):
+            raise ValueError("layout is %r: 'rgb' or 'scanline'" % (layout,))
+        h, w = max(y1 - y0, 0), max(x1 - x0, 0)
+        out = np.empty((h, w, 3) if layout == "rgb" else (h, 3, w), dtype=np.float16 if half else np.float32)
+        n = C.c_uint64()
+        _check(self.lib, self.lib.vspg_film_resolve(self.h, x0, y0, x1, y1, RESOLVE_F16 if half else RESOLVE_F32,
+                                                    RESOLVE_RGB if layout == "rgb" else RESOLVE_SCANLINE_BGR,
+                                                    out.ctypes.data_as(_vp), out.nbytes, C.byref(n), _vp(stream or 0)))
+        return out, int(n.value)
 
     def vsp_buffer(self, stream=None):
         import numpy as np

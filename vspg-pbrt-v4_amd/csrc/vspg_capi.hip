@@ -22,6 +22,7 @@
 #include "vspg_wavefront.h"
 #include "vspg_wf_launch.h"
 #include "vspg_film_error.h"
+#include "vspg_film_resolve.h"
 #include "vspg_kernel_choice.h"
 #ifdef VSPG_SINGLE_TU  // diagnostic builds that read device-side globals of the pipeline kernels (VSPG_WF_STATS, VSPG_PROFILE, VSPG_WF_DEBUG)
 #include "vspg_wf_grid.hip"
@@ -1745,6 +1746,9 @@ struct VspgRenderer {
     hipStream_t fe_stream = nullptr;     // the stream of the last enqueue ...
     hipEvent_t fe_event = nullptr;       // ... and an event behind it: the partial sums are shared, an enqueue on another stream waits
     bool fe_inflight = false;
+    // the resolved film (vspg_film_resolve.h): allocated by the first vspg_film_resolve
+    void *rs_stage = nullptr;            // the window's pixel values on their way to the host: at most npix * 12 bytes
+    unsigned int *rs_clamped = nullptr;  // pixels the fp16 clamp touched in the last resolve
 };
 
 // ---- host float helpers for scene preprocessing (same formulas as the kernels use) ----
@@ -3138,6 +3142,8 @@ int vspg_renderer_destroy(VspgRenderer *r) {
     if (r->fe_partials) (void)hipFree(r->fe_partials);
     if (r->fe_log) (void)hipFree(r->fe_log);
     if (r->fe_event) (void)hipEventDestroy(r->fe_event);
+    if (r->rs_stage) (void)hipFree(r->rs_stage);
+    if (r->rs_clamped) (void)hipFree(r->rs_clamped);
     delete r;
     return 0;
 }
@@ -3659,6 +3665,40 @@ int vspg_film_clear(VspgRenderer *r, void *stream) {
     HIPCHK(hipSetDevice(r->cfg.device));
     if (const int rc = flush_parked_samples(r, (hipStream_t)stream)) return rc;  // (their statistics stay; the film is cleared after)
     HIPCHK(hipMemsetAsync(r->film, 0, r->npix * sizeof(float4), (hipStream_t)stream));
+    return 0;
+}
+// ---- the film resolved to pixel values (include/vspg.h, vspg_film_resolve.h) ----
+int vspg_film_resolve(VspgRenderer *r, int x0, int y0, int x1, int y1, int format, int layout, void *host_out, size_t out_bytes,
+                      uint64_t *n_clamped, void *stream) {
+    if (!r || !host_out) return fail(VSPG_EINVAL, "null argument");
+    if (x0 < 0 || y0 < 0 || x1 <= x0 || y1 <= y0 || x1 > r->cfg.xres || y1 > r->cfg.yres)
+        return fail(VSPG_EINVAL, "pixel window [" + std::to_string(x0) + "," + std::to_string(x1) + ") x [" + std::to_string(y0) + "," + std::to_string(y1) +
+                                     ") is empty or not inside the " + std::to_string(r->cfg.xres) + " x " + std::to_string(r->cfg.yres) + " film");
+    if (format != VSPG_RESOLVE_F32 && format != VSPG_RESOLVE_F16) return fail(VSPG_EINVAL, "vspg_film_resolve: format " + std::to_string(format) + " is neither VSPG_RESOLVE_F32 nor VSPG_RESOLVE_F16");
+    if (layout != VSPG_RESOLVE_RGB && layout != VSPG_RESOLVE_SCANLINE_BGR) return fail(VSPG_EINVAL, "vspg_film_resolve: layout " + std::to_string(layout) + " is neither VSPG_RESOLVE_RGB nor VSPG_RESOLVE_SCANLINE_BGR");
+    const size_t want = (size_t)(x1 - x0) * (size_t)(y1 - y0) * 3 * (format == VSPG_RESOLVE_F16 ? 2 : 4);
+    if (out_bytes != want)
+        return fail(VSPG_EINVAL, "vspg_film_resolve: the window's pixels take " + std::to_string(want) + " bytes, out_bytes is " + std::to_string(out_bytes));
+    HIPCHK(hipSetDevice(r->cfg.device));
+    hipStream_t s = (hipStream_t)stream;
+    if (!r->rs_stage) HIPCHK(hipMalloc(&r->rs_stage, r->npix * 3 * sizeof(float)));
+    if (!r->rs_clamped) HIPCHK(hipMalloc(&r->rs_clamped, sizeof(unsigned int)));
+    if (const int rc = flush_parked_samples(r, s)) return rc;  // (the values are of the complete film)
+    const PixelWindow win = {x0, y0, x1, y1};
+    unsigned int clamped = 0;
+    if (format == VSPG_RESOLVE_F16) {
+        hipLaunchKernelGGL(k_film_pixels_zero, dim3(1), dim3(1), 0, s, r->rs_clamped);
+        HIPCHK(hipGetLastError());
+        film_resolve_launch<unsigned short>(r->cfg.xres, win, layout, r->film, r->rs_stage, r->rs_clamped, s);
+        HIPCHK(hipGetLastError());
+        HIPCHK(hipMemcpyAsync(&clamped, r->rs_clamped, sizeof(clamped), hipMemcpyDeviceToHost, s));
+    } else {
+        film_resolve_launch<float>(r->cfg.xres, win, layout, r->film, r->rs_stage, r->rs_clamped, s);
+        HIPCHK(hipGetLastError());
+    }
+    HIPCHK(hipMemcpyAsync(host_out, r->rs_stage, want, hipMemcpyDeviceToHost, s));
+    HIPCHK(hipStreamSynchronize(s));
+    if (n_clamped) *n_clamped = clamped;
     return 0;
 }
 // ---- film error against a reference image (include/vspg.h, vspg_film_error.h) ----

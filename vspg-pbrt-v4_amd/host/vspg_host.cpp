@@ -1,4 +1,5 @@
 #include "vspg_host.h"
+#include "vspg_image.h"
 #include "vspg_nanovdb.h"
 
 #include <algorithm>
@@ -459,7 +460,9 @@ GuidedVolPathVSPGIntegrator::GuidedVolPathVSPGIntegrator(const VspgIntegratorPar
             std::fclose(probe);
             std::string msg;
             try {
-                TrBuffer tb = TrBuffer::Load(trSettings.fileName);
+                // (format by extension, as pbrt's Image::Read: the reference's EXR with its channel names, or this adapter's PFM)
+                TrBuffer tb = HasExtension(trSettings.fileName, ".exr") ? TrBuffer::FromImage(ReadImage(trSettings.fileName), trSettings.fileName)
+                                                                          : TrBuffer::Load(trSettings.fileName);
                 if (tb.xres != xres || tb.yres != yres) msg = "resolution differs from the film's";
                 else if (vspg_renderer_set_tr_buffer(renderer, tb.rgb.data(), nullptr) != 0) msg = vspg_last_error();
             } catch (const Error &e) {
@@ -482,7 +485,8 @@ GuidedVolPathVSPGIntegrator::~GuidedVolPathVSPGIntegrator() {
     }
     if (trSettings.store) {  // :219-221
         try {
-            GetTrBuffer().Store(trSettings.fileName);
+            if (HasExtension(trSettings.fileName, ".exr")) vspg::WriteImage(GetTrBuffer().ToImage(), trSettings.fileName);  // (trbuffer.h:52-71)
+            else GetTrBuffer().Store(trSettings.fileName);
         } catch (const Error &e) {
             std::fprintf(stderr, "GuidedVolPathVSPGIntegrator: storing the transmittance buffer failed: %s\n", e.what());
         }
@@ -524,73 +528,54 @@ static bool has_pfm_extension(const std::string &fn) {
     for (char &c : e) c = (char)std::tolower((unsigned char)c);
     return e == ".pfm";
 }
+// The PFM raster itself is the Image layer's (vspg_image.cpp); these four keep their PFM-only contract and their types.
 void VspBuffer::Store(const std::string &filename) const {
     if (!has_pfm_extension(filename)) throw Error(filename + ": only the .pfm format is supported for the image-space guiding buffer");
-    std::FILE *f = std::fopen(filename.c_str(), "wb");
-    if (!f) throw Error(filename + ": cannot open for writing");
-    std::fprintf(f, "Pf\n%d %d\n-1.000000\n", xres, yres);
-    bool ok = true;
-    for (int y = yres - 1; y >= 0 && ok; --y) ok = std::fwrite(&vsp[(size_t)y * xres], sizeof(float), (size_t)xres, f) == (size_t)xres;
-    ok = std::fclose(f) == 0 && ok;
-    if (!ok) throw Error(filename + ": write failed");
+    Image img;
+    img.xres = xres; img.yres = yres;
+    img.channels = {"Y"};
+    img.data = vsp;
+    vspg::WriteImage(img, filename);
 }
 VspBuffer VspBuffer::Load(const std::string &filename) {
     if (!has_pfm_extension(filename)) throw Error(filename + ": only the .pfm format is supported for the image-space guiding buffer");
-    std::FILE *f = std::fopen(filename.c_str(), "rb");
-    if (!f) throw Error(filename + ": cannot open");
+    Image img = ReadImage(filename);
+    if (img.NChannels() != 1) throw Error(filename + ": not a single-channel PFM image");
     VspBuffer vb;
-    char magic[3] = {0, 0, 0};
-    float scale = 0;
-    bool ok = std::fscanf(f, "%2s %d %d %f", magic, &vb.xres, &vb.yres, &scale) == 4 && std::string(magic) == "Pf" && vb.xres > 0 &&
-              vb.yres > 0 && vb.xres <= 32768 && vb.yres <= 32768 && scale < 0;  // little endian only
-    if (ok) ok = std::fgetc(f) != EOF;
-    if (ok) {
-        vb.vsp.resize((size_t)vb.xres * vb.yres);
-        for (int y = vb.yres - 1; y >= 0 && ok; --y)
-            ok = std::fread(&vb.vsp[(size_t)y * vb.xres], sizeof(float), (size_t)vb.xres, f) == (size_t)vb.xres;
-    }
-    std::fclose(f);
-    if (!ok) throw Error(filename + ": not a little-endian single-channel PFM image");
+    vb.xres = img.xres; vb.yres = img.yres;
+    vb.vsp = std::move(img.data);
     vb.ready = true;
     return vb;
 }
 void TrBuffer::Store(const std::string &filename) const {
-    if (!has_pfm_extension(filename)) throw Error(filename + ": only the .pfm format of pbrt's Image class is supported (OpenEXR is absent)");
-    std::FILE *f = std::fopen(filename.c_str(), "wb");
-    if (!f) throw Error(filename + ": cannot open for writing");
-    std::fprintf(f, "PF\n%d %d\n-1.000000\n", xres, yres);
-    bool ok = true;
-    for (int y = yres - 1; y >= 0 && ok; --y)  // bottom scanline first
-        ok = std::fwrite(&rgb[(size_t)y * xres * 3], sizeof(float), (size_t)xres * 3, f) == (size_t)xres * 3;
-    ok = std::fclose(f) == 0 && ok;
-    if (!ok) throw Error(filename + ": write failed");
+    if (!has_pfm_extension(filename)) throw Error(filename + ": only the .pfm format of pbrt's Image class is supported here (ToImage + WriteImage write OpenEXR)");
+    Image img;
+    img.xres = xres; img.yres = yres;
+    img.channels = {"R", "G", "B"};
+    img.data = rgb;
+    vspg::WriteImage(img, filename);
 }
 TrBuffer TrBuffer::Load(const std::string &filename) {
-    if (!has_pfm_extension(filename)) throw Error(filename + ": only the .pfm format of pbrt's Image class is supported (OpenEXR is absent)");
-    std::FILE *f = std::fopen(filename.c_str(), "rb");
-    if (!f) throw Error(filename + ": cannot open");
+    if (!has_pfm_extension(filename)) throw Error(filename + ": only the .pfm format of pbrt's Image class is supported here (ReadImage + FromImage read OpenEXR)");
+    Image img = ReadImage(filename);
+    if (img.NChannels() != 3) throw Error(filename + ": not a 3-channel PFM image");
     TrBuffer tb;
-    char magic[3] = {0, 0, 0};
-    float scale = 0;
-    bool ok = std::fscanf(f, "%2s %d %d %f", magic, &tb.xres, &tb.yres, &scale) == 4 && std::string(magic) == "PF" && tb.xres > 0 &&
-              tb.yres > 0 && tb.xres <= 32768 && tb.yres <= 32768 && scale != 0;
-    if (ok) ok = std::fgetc(f) != EOF;  // the single whitespace byte after the header
-    if (ok) {
-        tb.rgb.resize((size_t)tb.xres * tb.yres * 3);
-        for (int y = tb.yres - 1; y >= 0 && ok; --y)
-            ok = std::fread(&tb.rgb[(size_t)y * tb.xres * 3], sizeof(float), (size_t)tb.xres * 3, f) == (size_t)tb.xres * 3;
-    }
-    std::fclose(f);
-    if (!ok) throw Error(filename + ": not a 3-channel PFM image");
-    if (scale > 0)  // big-endian file
-        for (float &v : tb.rgb) {
-            unsigned char *b = reinterpret_cast<unsigned char *>(&v);
-            std::swap(b[0], b[3]);
-            std::swap(b[1], b[2]);
-        }
-    const float mag = scale < 0 ? -scale : scale;
-    if (mag != 1.f)
-        for (float &v : tb.rgb) v *= mag;
+    tb.xres = img.xres; tb.yres = img.yres;
+    tb.rgb = std::move(img.data);  // (a "PF" file's channels are R, G, B in that order)
+    return tb;
+}
+Image TrBuffer::ToImage() const {
+    Image img;
+    img.xres = xres; img.yres = yres;
+    img.half = false;
+    img.channels = {"Transmittance.R", "Transmittance.G", "Transmittance.B"};
+    img.data = rgb;
+    return img;
+}
+TrBuffer TrBuffer::FromImage(const Image &image, const std::string &name) {
+    TrBuffer tb;
+    tb.xres = image.xres; tb.yres = image.yres;
+    tb.rgb = image.Gather({"Transmittance.R", "Transmittance.G", "Transmittance.B"}, name + ": the image");
     return tb;
 }
 GuidingCache GuidedVolPathVSPGIntegrator::GetGuidingCache() {
@@ -648,7 +633,12 @@ GuidingCache GuidingCache::Read(const std::string &filename) {
 }
 
 std::vector<float> LoadMseReferenceImage(const std::string &filename, int xres, int yres, int x0, int y0, int x1, int y1) {
-    const TrBuffer img = TrBuffer::Load(filename);
+    TrBuffer img;
+    {   // Image::Read by extension; the channels R, G, B by name (integrators.cpp:131-135)
+        const Image file = ReadImage(filename);
+        img.xres = file.xres; img.yres = file.yres;
+        img.rgb = file.Gather({"R", "G", "B"}, filename + ": the MSE reference image");
+    }
     const int bw = x1 - x0, bh = y1 - y0;
     if (img.xres == xres && img.yres == yres) return img.rgb;
     if (img.xres != bw || img.yres != bh)
@@ -681,6 +671,8 @@ void GuidedVolPathVSPGIntegrator::SetMseReference(const std::vector<float> &fram
 void GuidedVolPathVSPGIntegrator::Render() {
     // ImageTileIntegrator::Render (integrators.cpp:123-239): waves of 1 spp, PostProcessWave each
     int waveStart = 0, waveEnd = 1, nextWaveSize = 1;
+    const auto renderStart = std::chrono::steady_clock::now();
+    auto elapsed = [&]() { return std::chrono::duration<double>(std::chrono::steady_clock::now() - renderStart).count(); };
     VspgCounters before;
     std::memset(&before, 0, sizeof before);
     // the film's error against the reference image, one record per wave (:243-257), kept on the device until the log is drained
@@ -721,14 +713,57 @@ void GuidedVolPathVSPGIntegrator::Render() {
             std::fflush(waveLog);
             before = c;
         }
+        sppDone = waveEnd;
+        if (outPartial && !outFile.empty()) {  // --write-partial-images (:258-261): the image so far, with its metadata (:245-255)
+            renderSeconds = elapsed();
+            if (mseOut) {
+                drainErrors();
+                haveMse = true;
+                lastMse = FilmErrorAverage(errors.back(), errors.back().sum_se);
+            }
+            WriteImage();
+        }
         waveStart = waveEnd;
         waveEnd = std::min(spp, waveEnd + nextWaveSize);
     }
     if (mseOut) {
         drainErrors();
+        if (!errors.empty()) {
+            haveMse = true;
+            lastMse = FilmErrorAverage(errors.back(), errors.back().sum_se);
+        }
         for (const VspgFilmError &e : errors) std::fprintf(mseOut, "%d, %.9g\n", e.tag, FilmErrorAverage(e, e.sum_se));  // :254
         std::fflush(mseOut);
     }
+    renderSeconds = elapsed();
+}
+void GuidedVolPathVSPGIntegrator::SetOutput(const std::string &filename, bool fp16, bool writePartial) {
+    outFile = filename;
+    outFp16 = fp16;
+    outPartial = writePartial;
+}
+void GuidedVolPathVSPGIntegrator::WriteImage() {
+    if (outFile.empty()) throw Error("GuidedVolPathVSPGIntegrator::WriteImage: no output file (SetOutput)");
+    if (!HasExtension(outFile, ".exr")) {
+        GetFilm().WritePFM(outFile);
+        return;
+    }
+    Image meta;
+    meta.xres = bounds[2] - bounds[0]; meta.yres = bounds[3] - bounds[1];
+    meta.channels = {"B", "G", "R"};
+    meta.dataX0 = bounds[0]; meta.dataY0 = bounds[1];
+    meta.fullX = cfg.xres; meta.fullY = cfg.yres;
+    meta.samplesPerPixel = sppDone;
+    meta.renderTimeSeconds = (float)renderSeconds;
+    if (haveMse) meta.MSE = lastMse;
+    // the device hands over the scan-line payload itself: 6 (or 12) bytes per pixel, nothing rearranged on the host
+    std::vector<unsigned char> lines((size_t)meta.xres * meta.yres * 3 * (outFp16 ? 2 : 4));
+    uint64_t nClamped = 0;
+    if (vspg_film_resolve(renderer, bounds[0], bounds[1], bounds[2], bounds[3], outFp16 ? VSPG_RESOLVE_F16 : VSPG_RESOLVE_F32, VSPG_RESOLVE_SCANLINE_BGR,
+                          lines.data(), lines.size(), &nClamped, nullptr) != 0)
+        throw Error(vspg_last_error());
+    if (nClamped > 0) std::fprintf(stderr, "Warning: %d pixel values clamped to maximum fp16 value.\n", (int)nClamped);  // (film.cpp:558-559)
+    WriteExrScanlines(meta, outFp16, lines.data(), outFile);
 }
 void GuidedVolPathVSPGIntegrator::PostProcessWave() {
     if (vspg_post_process_wave(renderer, nullptr) != 0) throw Error(vspg_last_error());

@@ -82,6 +82,8 @@ VspgMedium CreateMedium(const std::string &name, const ParameterDictionary &para
                         std::vector<float> *densityStorage = nullptr, std::vector<float> *leScaleStorage = nullptr,
                         std::vector<float> *temperatureStorage = nullptr);
 
+struct Image;  // vspg_image.h: pbrt's Image by file extension (PFM, OpenEXR)
+
 struct Film {
     int xres = 0, yres = 0;   // the size of the film's pixelBounds: the window that was rendered (the whole frame by default)
     int x0 = 0, y0 = 0;       // ... and its origin in the frame; pixel (x, y) below is relative to it
@@ -112,16 +114,18 @@ struct GuidingCacheSettings {  // "storeGuidingCache" / "loadGuidingCache" / "gu
 };
 
 // TrBuffer (src/pbrt/cpu/trbuffer.h:17-104): the per-pixel transmittance estimates of the primary rays, kept between
-// runs for NDS+.  The reference stores it through pbrt's Image class (format by file extension, normally OpenEXR, an
-// absent submodule); this adapter reads and writes the PFM raster of that class (util/image.cpp:1756-1800 WritePFM:
-// "PF", width height, scale -1 = little endian, RGB float32, scanlines bottom to top).  PFM carries no channel
-// names ("Transmittance.R/G/B" in the reference's EXR), so the file is this adapter's own persistence, readable by
-// any PFM tool.  Other extensions are refused.
+// runs for NDS+.  The reference stores it through pbrt's Image class (format by file extension, normally OpenEXR).
+// Store / Load read and write the PFM raster of that class only (util/image.cpp:1756-1800 WritePFM: "PF", width height,
+// scale -1 = little endian, RGB float32, scanlines bottom to top) and refuse other extensions.  PFM carries no channel
+// names; the reference's EXR layout -- FLOAT channels "Transmittance.R/G/B" (trbuffer.h:52-71) -- goes through ToImage /
+// FromImage and vspg_image.h's WriteImage / ReadImage, which is what the integrator does for a "trBufferFileName" ending in .exr.
 struct TrBuffer {
     int xres = 0, yres = 0;
     std::vector<float> rgb;  // row-major, top row first, 3 floats per pixel
     void Store(const std::string &filename) const;
     static TrBuffer Load(const std::string &filename);
+    Image ToImage() const;                                              // FLOAT, channels Transmittance.R / .G / .B
+    static TrBuffer FromImage(const Image &image, const std::string &name);  // by those names; `name` is for the Error
 };
 // The image-space VSP buffer between runs ("storeISGBuffer" / "loadISGBuffer" / "isgBufferFileName",
 // guidedvolpathvspgintegrator.cpp:151-159, 214-216).  OpenPGL's own file format is not part of the reference tree; this
@@ -144,7 +148,8 @@ struct TrBufferSettings {  // "storeTrBuffer" / "loadTrBuffer" / "trBufferFileNa
 };
 
 // --mse-reference-image (cmd/pbrt.cpp:60-61, ImageTileIntegrator::Render, cpu/integrators.cpp:129-158): the image the film is
-// compared with after every wave.  Read with TrBuffer's PFM reader (EXR is out of scope: OpenEXR is absent).  It has the size of
+// compared with after every wave.  Read with ReadImage (vspg_image.h: PFM or OpenEXR; channels R, G, B by name, half files widened
+// exactly).  It has the size of
 // the frame -- then the pixel bounds select the part compared (:136-153) -- or exactly the size of the pixel bounds; anything else
 // is an Error that names both sizes.  Returned as a frame-sized image (W*H*3, top row first), what vspg_renderer_set_reference_image
 // takes; outside the pixel bounds nothing is ever compared.
@@ -197,8 +202,20 @@ class GuidedVolPathVSPGIntegrator : public Integrator {
     // returns it; Render() then records the film's error over the pixel bounds after every wave ON THE DEVICE (vspg_film_error_enqueue:
     // no film read-back, no host synchronisation per wave) and writes one line "spp, mse.Average()" per wave ("%d, %.9g\n", :254) to
     // `out` (not owned) when it ends.  Recording completes the film after every wave, so the carry of in-flight paths between
-    // one-sample waves is given up.  Not covered: EXR reference images, --write-partial-images, vspg_pbrt_sharded.
+    // one-sample waves is given up.  Not covered: vspg_pbrt_sharded.
     void SetMseReference(const std::vector<float> &frameImage, std::FILE *out);
+    // The film's file (RGBFilm::WriteImage, film.cpp:531-569), format by extension:
+    //   .exr  the pixel bounds resolved ON THE DEVICE (vspg_film_resolve, scan-line layout) and written as they arrive: HALF channels
+    //         B, G, R by default, FLOAT with fp16 = false (the Film's "savefp16"); dataWindow = the pixel bounds, displayWindow = the
+    //         frame; samplesPerPixel, renderTimeSeconds and -- with an MSE reference -- MSE (the last wave's average) attributes; the
+    //         reference's warning "%d pixel values clamped to maximum fp16 value." when the clamp touched any;
+    //   any other name (.pfm)  GetFilm().WritePFM(), byte for byte as ever.
+    // writePartial (--write-partial-images, cmd/pbrt.cpp:81, integrators.cpp:258-261): Render() rewrites the file after every wave with
+    // samplesPerPixel = the waves so far; that completes the film each wave, so the carry of in-flight paths is given up.
+    // Out of scope: vspg_pbrt_sharded (stays PFM), the Film's "maxcomponentvalue", the camera matrices in the metadata (worldToCamera,
+    // worldToNDC), PIZ and the other compressions, tiled EXR.
+    void SetOutput(const std::string &filename, bool fp16 = true, bool writePartial = false);
+    void WriteImage();            // the film as it stands to the file SetOutput named
 
   private:
     std::FILE *waveLog = nullptr;
@@ -208,6 +225,12 @@ class GuidedVolPathVSPGIntegrator : public Integrator {
     VspgRenderer *renderer = nullptr;
     int bounds[4] = {0, 0, 0, 0};  // x0, y0, x1, y1
     int spp;
+    std::string outFile;
+    bool outFp16 = true, outPartial = false;
+    int sppDone = 0;              // waves rendered so far (metadata.samplesPerPixel)
+    double renderSeconds = 0;     // (metadata.renderTimeSeconds)
+    bool haveMse = false;
+    float lastMse = 0;            // (metadata.MSE)
     GuidingCacheSettings cacheSettings;
     TrBufferSettings trSettings;
     IsgBufferSettings isgSettings;

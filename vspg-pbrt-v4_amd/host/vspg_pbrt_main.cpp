@@ -1,11 +1,13 @@
 // vspg_pbrt -- render a pbrt-v4 scene file (the subset of vspg_scenefile.h) with the MI355X-native GuidedVolPathVSPG path.
-//   vspg_pbrt scene.pbrt [--spp N] [--outfile image.pfm] [--seed S] [--device D] [--wave-log waves.jsonl] [--parse-only]
+//   vspg_pbrt scene.pbrt [--spp N] [--outfile image.exr|image.pfm] [--seed S] [--device D] [--wave-log waves.jsonl] [--parse-only]
 //             [--cropwindow x0,x1,y0,y1] [--pixelbounds x0,x1,y0,y1]   (cmd/pbrt.cpp:132-153; they override the file's Film parameters)
-//             [--mse-reference-image ref.pfm --mse-reference-out file]  (cmd/pbrt.cpp:60-61, :244-248: after every wave the MSE of the
-//              film against the image is appended to the file as "spp, mse", cpu/integrators.cpp:243-257; reduced on the device.
-//              PFM only -- no EXR --, and neither --write-partial-images nor vspg_pbrt_sharded are covered.)
-// The counterpart of `pbrt scene.pbrt` for this integrator (cmd/pbrt.cpp -> RenderCPU, cpu/render.cpp:56-57); the image is
-// written as PFM (RGBFilm::WriteImage's EXR needs OpenEXR, an absent submodule).
+//             [--mse-reference-image ref.exr|ref.pfm --mse-reference-out file]  (cmd/pbrt.cpp:60-61, :244-248: after every wave the MSE
+//              of the film against the image is appended to the file as "spp, mse", cpu/integrators.cpp:243-257; reduced on the device.
+//              vspg_pbrt_sharded does not cover it.)
+//             [--write-partial-images]   (cmd/pbrt.cpp:81, integrators.cpp:258-261: the image file is rewritten after every wave)
+// The counterpart of `pbrt scene.pbrt` for this integrator (cmd/pbrt.cpp -> RenderCPU, cpu/render.cpp:56-57); the image is written
+// by its extension (RGBFilm::WriteImage, film.cpp:531-569): OpenEXR -- resolved on the device, HALF unless the Film says
+// "bool savefp16" false -- or PFM.
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
@@ -18,7 +20,7 @@ int main(int argc, char **argv) {
     std::string scene, out;
     int spp = -1, seed = -1, device = 0;
     std::string waveLogPath;
-    bool parseOnly = false;
+    bool parseOnly = false, writePartial = false;
     vspg::FilmOverrides film;
     std::string cropArg, boundsArg;
     std::string mseImagePath, mseOutPath;
@@ -35,10 +37,11 @@ int main(int argc, char **argv) {
         else if (a == "--pixelbounds") boundsArg = next();
         else if (a == "--mse-reference-image") mseImagePath = next();
         else if (a == "--mse-reference-out") mseOutPath = next();
+        else if (a == "--write-partial-images") writePartial = true;
         else if (!a.empty() && a[0] == '-') { std::fprintf(stderr, "unknown option %s\n", a.c_str()); return 2; }
         else scene = a;
     }
-    if (scene.empty()) { std::fprintf(stderr, "usage: vspg_pbrt scene.pbrt [--spp N] [--outfile image.pfm] [--seed S] [--device D] [--wave-log waves.jsonl] [--parse-only] [--cropwindow x0,x1,y0,y1] [--pixelbounds x0,x1,y0,y1] [--mse-reference-image ref.pfm --mse-reference-out file]\n"); return 2; }
+    if (scene.empty()) { std::fprintf(stderr, "usage: vspg_pbrt scene.pbrt [--spp N] [--outfile image.exr|image.pfm] [--seed S] [--device D] [--wave-log waves.jsonl] [--parse-only] [--cropwindow x0,x1,y0,y1] [--pixelbounds x0,x1,y0,y1] [--mse-reference-image ref.exr|ref.pfm --mse-reference-out file] [--write-partial-images]\n"); return 2; }
     try {
         vspg::CheckMseReferenceOptions(mseImagePath, mseOutPath);
         if (!cropArg.empty()) vspg::ParseCropWindowArg(cropArg, &film);
@@ -86,11 +89,11 @@ int main(int argc, char **argv) {
             if (!mseOut) throw vspg::Error(mseOutPath + ": cannot open for writing");
             vi->SetMseReference(mseImage, mseOut);
         }
+        vi->SetOutput(sd->filmFilename, sd->saveFP16, writePartial);
         integrator->Render();
         if (wl) { vi->SetWaveLog(nullptr); std::fclose(wl); }
         if (mseOut) std::fclose(mseOut);
-        vspg::Film film = vi->GetFilm();
-        film.WritePFM(sd->filmFilename);
+        vi->WriteImage();
         VspgCounters c = vi->Counters();
         std::printf("paths %llu segments %llu -> %s\n", (unsigned long long)c.paths, (unsigned long long)c.segments, sd->filmFilename.c_str());
     } catch (const std::exception &e) {

@@ -235,6 +235,7 @@ class Parser {
             sd->xres = p.GetOneInt("xresolution", 1280);
             sd->yres = p.GetOneInt("yresolution", 720);
             sd->filmFilename = p.GetOneString("filename", "pbrt.pfm");
+            sd->saveFP16 = p.GetOneBool("savefp16", true);
             sd->cropWindow = p.GetFloatArray("cropwindow");
             sd->pixelBoundsParam = p.GetIntArray("pixelbounds");   // (resolved once the command line is known: ResolvePixelBounds)
             p.ReportUnused();

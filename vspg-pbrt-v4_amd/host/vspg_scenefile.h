@@ -8,7 +8,7 @@
 // unused-parameter error are the reference's.
 //
 // Directives: LookAt, Camera "perspective" (fov), Sampler (pixelsamples, seed), PixelFilter "box", Film "rgb"
-// (xresolution, yresolution, filename), Integrator, Option (ignored), ColorSpace (ignored), WorldBegin, AttributeBegin/End,
+// (xresolution, yresolution, filename, savefp16, cropwindow, pixelbounds), Integrator, Option (ignored), ColorSpace (ignored), WorldBegin, AttributeBegin/End,
 // Identity, Translate, Scale, Rotate, Transform, ConcatTransform, ReverseOrientation, Material "diffuse" (reflectance) / "interface",
 // MakeNamedMaterial / NamedMaterial ("diffuse", "interface"), AreaLightSource "diffuse" (L, scale, twosided), LightSource "infinite"
 // (L, scale; no image) / "distant" (L, scale, from, to), MakeNamedMedium ("homogeneous", "uniformgrid"), MediumInterface,
@@ -20,7 +20,8 @@
 // with the reference's boundaries (round 4): every shape carries its MediumInterface and its material -- an "interface" material
 // makes it a pure medium boundary (guidedvolpathvspgintegrator.cpp:399-404) -- and the camera starts in the "outside" medium of the
 // MediumInterface in effect at the Camera directive (scene.cpp:153-155); a second medium in the same scene is refused by name;
-// emission on rectangles only; the film is written as PFM (OpenEXR is an absent submodule).
+// emission on rectangles only; the film is written as OpenEXR or PFM by its file name's extension (host/vspg_image.h; "maxcomponentvalue"
+// is not read).
 #pragma once
 #include <memory>
 #include <string>
@@ -40,6 +41,7 @@ struct SceneDescription {
     int pixelSamples = 16;               // Sampler default
     int seed = 0;
     std::string filmFilename = "pbrt.pfm";
+    bool saveFP16 = true;                // Film "savefp16" (film.cpp:531-569): an .exr film is HALF, or FLOAT when false
     // Film "cropwindow" / "pixelbounds" as the file gives them (x0 x1 y0 y1; empty = not given), and the film's pixelBounds
     // [x0, x1) x [y0, y1) resolved from them by ResolvePixelBounds: all the render loop covers and the written image holds
     std::vector<float> cropWindow;
