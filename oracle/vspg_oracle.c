@@ -1875,6 +1875,14 @@ static v3 lobe_dir(const VspgFieldRegion *R, int k, v3 p) {
 }
 static float lobe_b(const VspgFieldRegion *R, int k) { return R->weight[k] * vmf_norm(kappa_clamp(R->kappa[k])); }
 /* {Surface,Volume}SamplingDistribution::Init + Apply*Product */
+/* test instrumentation: how often Init took the sum == 0 fallback [0] and met a cancelling product lobe [1] (any thread) */
+static long g_guiding_branches[2];
+void oracle_guiding_branch_counts(long out[2], int reset) {
+    for (int i = 0; i < 2; ++i) {
+        out[i] = __atomic_load_n(&g_guiding_branches[i], __ATOMIC_RELAXED);
+        if (reset) __atomic_store_n(&g_guiding_branches[i], 0, __ATOMIC_RELAXED);
+    }
+}
 static gdist_t gdist_init(const OracleRenderer *r, int f, v3 p, int have_product, v3 m2, float k2) {
     gdist_t d;
     memset(&d, 0, sizeof d);
@@ -1894,6 +1902,7 @@ static gdist_t gdist_init(const OracleRenderer *r, int f, v3 p, int have_product
         if (have_product) {
             v3 s = v_add(v_scale(d.raw[k], kr), v_scale(m2, k2));
             float kp = sqrtf(v_len2(s));
+            if (!(kp > 1e-6f)) __atomic_fetch_add(&g_guiding_branches[1], 1, __ATOMIC_RELAXED);
             float kpinv = kp > 1e-6f ? 1.0f / kp : 0.f; /* lobes cancel: c1 = c2 = 0, i.e. mu . w := 0 under kc = 0.01 -- nearly uniform */
             float kc = kappa_clamp(kp);
             float E = oracle_fast_exp(-2 * kc);
@@ -1909,6 +1918,7 @@ static gdist_t gdist_init(const OracleRenderer *r, int f, v3 p, int have_product
         d.isum = 1.0f / sum;
     } else { /* degenerate product: fall back to the incident-radiance mixture */
         d.isum = 1.f;
+        __atomic_fetch_add(&g_guiding_branches[0], 1, __ATOMIC_RELAXED);
         for (int k = 0; k < d.n; ++k) { d.a[k] = lobe_b(R, k); wo[k] = R->weight[k]; d.kc[k] = kappa_clamp(R->kappa[k]); d.c1[k] = 1.f; d.c2[k] = 0.f; }
     }
     for (int k = 0; k < d.n; ++k) d.wn[k] = wo[k] * d.isum;
@@ -1985,26 +1995,38 @@ static void free_field(OracleRenderer *r, int f) {
     r->rstats[f] = NULL;
     memset(&r->field[f], 0, sizeof r->field[f]);
 }
-static int copy_field(OracleRenderer *r, int f, const VspgField *src) {
-    free_field(r, f);
+/* what copy_field takes: absent / empty (the field is cleared), or children after their parent, leaves in range, 0..GK lobes */
+static int check_field(const VspgField *src) {
     if (!src || src->n_nodes <= 0 || src->n_regions <= 0) return 0;
+    if (!src->nodes || !src->regions) return VSPG_EINVAL;
     for (int i = 0; i < src->n_nodes; ++i) {
         uint32_t axis = src->nodes[i].packed & 3u, idx = src->nodes[i].packed >> 2;
         if (axis == 3u ? (int)idx >= src->n_regions : (int)idx + 1 >= src->n_nodes || (int)idx <= i) return VSPG_EINVAL;
     }
+    for (int i = 0; i < src->n_regions; ++i)
+        if (src->regions[i].n_lobes < 0 || src->regions[i].n_lobes > GK) return VSPG_EINVAL;
+    return 0;
+}
+static void copy_field(OracleRenderer *r, int f, const VspgField *src) { /* src has passed check_field */
+    free_field(r, f);
+    if (!src || src->n_nodes <= 0 || src->n_regions <= 0) return;
     r->field[f].n_nodes = src->n_nodes; r->field[f].n_regions = src->n_regions;
     r->field[f].nodes = (VspgKdNode *)malloc(sizeof(VspgKdNode) * src->n_nodes);
     r->field[f].regions = (VspgFieldRegion *)malloc(sizeof(VspgFieldRegion) * src->n_regions);
     memcpy(r->field[f].nodes, src->nodes, sizeof(VspgKdNode) * src->n_nodes);
     memcpy(r->field[f].regions, src->regions, sizeof(VspgFieldRegion) * src->n_regions);
-    return 0;
 }
 int oracle_renderer_set_guiding_field(OracleRenderer *r, const VspgField *surface_field, const VspgField *volume_field) {
+    /* all or nothing: a refused call leaves both fields and the training state as they were */
+    int rc = check_field(surface_field);
+    if (rc) return rc;
+    rc = check_field(volume_field);
+    if (rc) return rc;
     r->training = 0; /* a loaded cache is not trained further (:117-122) */
     r->field_uploaded = 1;
-    int rc = copy_field(r, 0, surface_field);
-    if (rc) return rc;
-    return copy_field(r, 1, volume_field);
+    copy_field(r, 0, surface_field);
+    copy_field(r, 1, volume_field);
+    return 0;
 }
 int oracle_guiding_query_batch(OracleRenderer *r, int is_volume, float g, int n, const float *p, const float *n_or_wo,
                                const float *wi, const float *u, int32_t *out_ok, float *out_pdf, float *out_incoming_pdf,

@@ -109,6 +109,8 @@ int oracle_guiding_query_batch(OracleRenderer *r, int is_volume, float g, int n,
                                const float *n_or_wo, const float *wi, const float *u, int32_t *out_ok,
                                float *out_pdf, float *out_incoming_pdf, float *out_vsp, float *out_ws,
                                float *out_pdf_s);
+/* test instrumentation: Init calls that took the sum == 0 fallback [0] / met a cancelling product lobe [1], all renderers */
+void oracle_guiding_branch_counts(long out[2], int reset);
 
 /* guiding-cache training (a18; the OpenPGL side -- PropagateSamples, Field::Update -- is this build's
  * own design, PARITY UNPINNED; the recording hooks follow src/pbrt/cpu/guiding.h:682-832) */

@@ -73,6 +73,7 @@ def load():
         "oracle_guiding_query_batch": (C.c_int, [vp, C.c_int, C.c_float, C.c_int, p(C.c_float), p(C.c_float), p(C.c_float),
                                                  p(C.c_float), p(C.c_int32), p(C.c_float), p(C.c_float), p(C.c_float),
                                                  p(C.c_float), p(C.c_float)]),
+        "oracle_guiding_branch_counts": (None, [C.c_long * 2, C.c_int]),
         "oracle_renderer_training_stats": (C.c_int, [vp, p(P.VspgTrainStats)]),
         "oracle_train_samples_read": (C.c_int, [vp, p(P.VspgTrainSample), C.c_size_t, p(C.c_size_t)]),
         "oracle_renderer_get_guiding_field": (C.c_int, [vp, C.c_int, p(P.VspgKdNode), p(P.VspgFieldRegion), p(C.c_int32),
@@ -291,3 +292,10 @@ def guiding_query(fn, handle, is_volume, g, p, n_or_wo, wi, u, stream):
     rc = fn(*args)
     assert rc == 0, rc
     return dict(ok=ok, pdf=pdf, incoming_pdf=inc, vsp=vsp, ws=ws, pdf_s=pdfs)
+
+
+def guiding_branch_counts(reset=False):
+    """(sum == 0 fallbacks, cancelling product lobes) the oracle's Init has taken since the last reset, over all renderers"""
+    out = (C.c_long * 2)()
+    load().oracle_guiding_branch_counts(out, int(reset))
+    return out[0], out[1]

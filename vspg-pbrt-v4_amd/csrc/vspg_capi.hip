@@ -4004,12 +4004,9 @@ int vspg_brick_read(VspgRenderer *r, int32_t *index, float *octets, void *stream
     return 0;
 }
 
-static int upload_field(VspgRenderer *r, int f, const VspgField *src, hipStream_t s) {
-    if (r->fnodes[f]) { (void)hipFree(r->fnodes[f]); r->fnodes[f] = nullptr; }
-    if (r->fregions[f]) { (void)hipFree(r->fregions[f]); r->fregions[f] = nullptr; }
-    if (r->faux[f]) { (void)hipFree(r->faux[f]); r->faux[f] = nullptr; }
-    if (r->flobes[f]) { (void)hipFree(r->flobes[f]); r->flobes[f] = nullptr; }
-    r->hscene.field[f] = DField{0, 0, nullptr, nullptr, nullptr, nullptr};
+// A field that upload_field can take: absent / empty (the field is cleared), or arrays with children after their parent,
+// leaves in range and 0..GK lobes per region.  Checked for BOTH fields before anything of the renderer changes.
+static int validate_field(const VspgField *src) {
     if (!src || src->n_nodes <= 0 || src->n_regions <= 0) return 0;
     if (!src->nodes || !src->regions) return fail(VSPG_EINVAL, "guiding field without node / region arrays");
     for (int i = 0; i < src->n_nodes; ++i) {  // structural check: children after their parent, leaves in range
@@ -4020,6 +4017,16 @@ static int upload_field(VspgRenderer *r, int f, const VspgField *src, hipStream_
     for (int i = 0; i < src->n_regions; ++i)
         if (src->regions[i].n_lobes < 0 || src->regions[i].n_lobes > VSPG_FIELD_LOBES)
             return fail(VSPG_EINVAL, "guiding-field region with an invalid lobe count");
+    return 0;
+}
+// (src has passed validate_field)
+static int upload_field(VspgRenderer *r, int f, const VspgField *src, hipStream_t s) {
+    if (r->fnodes[f]) { (void)hipFree(r->fnodes[f]); r->fnodes[f] = nullptr; }
+    if (r->fregions[f]) { (void)hipFree(r->fregions[f]); r->fregions[f] = nullptr; }
+    if (r->faux[f]) { (void)hipFree(r->faux[f]); r->faux[f] = nullptr; }
+    if (r->flobes[f]) { (void)hipFree(r->flobes[f]); r->flobes[f] = nullptr; }
+    r->hscene.field[f] = DField{0, 0, nullptr, nullptr, nullptr, nullptr};
+    if (!src || src->n_nodes <= 0 || src->n_regions <= 0) return 0;
     HIPCHK(hipMalloc(&r->fnodes[f], sizeof(VspgKdNode) * src->n_nodes));
     HIPCHK(hipMalloc(&r->fregions[f], sizeof(VspgFieldRegion) * src->n_regions));
     HIPCHK(hipMemcpyAsync(r->fnodes[f], src->nodes, sizeof(VspgKdNode) * src->n_nodes, hipMemcpyHostToDevice, s));
@@ -4033,16 +4040,24 @@ static int upload_field(VspgRenderer *r, int f, const VspgField *src, hipStream_
 int vspg_renderer_set_guiding_field(VspgRenderer *r, const VspgField *surface_field, const VspgField *volume_field,
                                     void *stream) {
     if (!r) return fail(VSPG_EINVAL, "null renderer");
+    // a call refused by validation leaves the renderer exactly as it was: fields, training state, parked samples.  (A HIP
+    // failure further down does not: training is off and the fields may be cleared by then -- but the device's scene record
+    // is re-copied from the host's, so it never keeps a freed pointer.)
+    if (const int vrc = validate_field(surface_field)) return vrc;
+    if (const int vrc = validate_field(volume_field)) return vrc;
     HIPCHK(hipSetDevice(r->cfg.device));
     hipStream_t s = (hipStream_t)stream;
     if (const int frc = flush_parked_samples(r, s)) return frc;  // (paths in flight end under the scene record they started with)
     HIPCHK(hipStreamSynchronize(s));  // no launch may still read the old field
     r->training = false;                // a loaded cache is not trained further (:117-122)
     int rc = upload_field(r, 0, surface_field, s);
-    if (rc) return rc;
-    rc = upload_field(r, 1, volume_field, s);
-    if (rc) return rc;
+    if (!rc) rc = upload_field(r, 1, volume_field, s);
+    // the device's scene record follows the host's whatever happened above: it never keeps a pointer that was freed
     HIPCHK(hipMemcpyAsync(r->dscene, &r->hscene, sizeof(DScene), hipMemcpyHostToDevice, s));
+    if (rc) {
+        HIPCHK(hipStreamSynchronize(s));
+        return rc;
+    }
     for (int f = 0; f < 2; ++f)
         if (r->faux[f])
             hipLaunchKernelGGL(k_field_aux, dim3((r->hscene.field[f].n_regions * GK + kBlock - 1) / kBlock), dim3(kBlock), 0, s, r->dscene,

@@ -331,7 +331,11 @@ VDEV float gdist_vsp(const DField *fields, int f, int region, const GDistT<ST> &
 VDEV V3 vmf_sample_dir(float u0, float u1, float acc, float wk, float kap, V3 mz) {
     float uw = wk > 0 ? (u0 - acc) / wk : 0.f;
     uw = uw < 0 ? 0 : (uw > kOneMinusEps ? kOneMinusEps : uw);
-    float W = 1 + logf_(uw + (1 - uw) * fast_exp(-2 * kap)) / kap;
+    // la == 0 when uw == 0 under a kappa whose e^{-2 kappa} FastExp flushes to zero (kappa > 43.6): the host's logf gives -inf and
+    // W clamps to -1, the antipode; logf_ is scoped to positive normal floats (vspg_libm.h: NaN outside them).  (A NaN la -- NaN
+    // kappa or weight in a SET lobe -- also lands on W = -1 here, where the host carries the NaN into its clamp: no parity claimed.)
+    const float la = uw + (1 - uw) * fast_exp(-2 * kap);
+    float W = la > 0 ? 1 + logf_(la) / kap : -1.f;
     W = clampf(W, -1, 1);
     float sinT = safe_sqrt(1 - W * W);
     float phi = kTwoPi * u1;
