@@ -3479,6 +3479,43 @@ static v3 reaim(const VspgFieldRegion *R, v3 p, v3 w, float dist) {
     if (!(l2 > 0)) return w;
     return v_normalize(t);
 }
+/* The E step's terms of ONE sample in region R, as floats in the order of region_stats: S, R0, R1, R2, D, V, Qv, Qs, each
+ * VSPG_FIELD_LOBES wide (a statistic the sample does not feed -- D without a hit distance, V / Qv or Qs by the kind of the
+ * next event, a lobe slot k >= n_lobes -- is 0).  Returns 0, with every term 0, when the sample contributes nothing: a
+ * region without lobes, or a mixture density that is not positive and finite. */
+#define TRAIN_ESTEP_TERMS (8 * VSPG_FIELD_LOBES)
+static int train_estep_terms(const VspgFieldRegion *R, const VspgTrainSample *sm, float wmax, float *t) {
+    const int K = VSPG_FIELD_LOBES;
+    for (int k = 0; k < TRAIN_ESTEP_TERMS; ++k) t[k] = 0.f;
+    if (R->n_lobes <= 0) return 0;
+    float w = sm->weight < wmax ? sm->weight : wmax;
+    v3 om = reaim(R, v3_from(sm->p), v3_from(sm->dir), sm->distance);
+    float g[VSPG_FIELD_LOBES], gs = 0;
+    for (int k = 0; k < R->n_lobes; ++k) {
+        g[k] = R->weight[k] * vmf_eval(V3(R->mu[0][k], R->mu[1][k], R->mu[2][k]), kappa_clamp(R->kappa[k]), om);
+        gs += g[k];
+    }
+    if (!(gs > 0) || isinf(gs)) return 0;
+    int nextvol = (sm->flags & VSPG_SAMPLE_NEXT_VOLUME) != 0;
+    for (int k = 0; k < R->n_lobes; ++k) {
+        float wg = w * (g[k] / gs);
+        t[0 * K + k] = wg;
+        t[1 * K + k] = wg * om.x; t[2 * K + k] = wg * om.y; t[3 * K + k] = wg * om.z;
+        if (sm->distance > 0 && !isinf(sm->distance)) t[4 * K + k] = wg / sm->distance;
+        if (nextvol) { t[5 * K + k] = wg; t[6 * K + k] = wg * w; } else t[7 * K + k] = wg * w;
+    }
+    return 1;
+}
+/* test export: the terms of n samples that all lie in region R (out: n x 8 * VSPG_FIELD_LOBES floats; valid: n flags or NULL) */
+int oracle_train_estep_terms(const VspgFieldRegion *R, const VspgTrainSample *samples, size_t n, float wmax, float *out,
+                             int32_t *valid) {
+    if (!R || (!samples && n) || (!out && n)) return VSPG_EINVAL;
+    for (size_t i = 0; i < n; ++i) {
+        int ok = train_estep_terms(R, &samples[i], wmax, out + i * TRAIN_ESTEP_TERMS);
+        if (valid) valid[i] = ok;
+    }
+    return 0;
+}
 static void field_update_one(OracleRenderer *r, int f, float mean_w) {
     int want_vol = f == 1;
     VspgKdNode *nodes = r->field[f].nodes;
@@ -3555,23 +3592,14 @@ static void field_update_one(OracleRenderer *r, int f, float mean_w) {
         v3 p = v3_from(sm->p);
         int reg = field_lookup(r, f, p);
         if (reg < 0) continue;
-        const VspgFieldRegion *R = &regs[reg];
-        if (R->n_lobes <= 0) continue;
-        float w = sm->weight < wmax ? sm->weight : wmax;
-        v3 om = reaim(R, p, v3_from(sm->dir), sm->distance);
-        float g[VSPG_FIELD_LOBES], gs = 0;
-        for (int k = 0; k < R->n_lobes; ++k) {
-            g[k] = R->weight[k] * vmf_eval(V3(R->mu[0][k], R->mu[1][k], R->mu[2][k]), kappa_clamp(R->kappa[k]), om);
-            gs += g[k];
-        }
-        if (!(gs > 0) || isinf(gs)) continue;
-        int nextvol = (sm->flags & VSPG_SAMPLE_NEXT_VOLUME) != 0;
-        for (int k = 0; k < R->n_lobes; ++k) {
-            float wg = w * (g[k] / gs);
-            acc[reg].S[k] += wg;
-            acc[reg].R[0][k] += wg * om.x; acc[reg].R[1][k] += wg * om.y; acc[reg].R[2][k] += wg * om.z;
-            if (sm->distance > 0 && !isinf(sm->distance)) acc[reg].D[k] += wg / sm->distance;
-            if (nextvol) { acc[reg].V[k] += wg; acc[reg].Qv[k] += wg * w; } else acc[reg].Qs[k] += wg * w;
+        float t[TRAIN_ESTEP_TERMS];
+        if (!train_estep_terms(&regs[reg], sm, wmax, t)) continue;
+        for (int k = 0; k < regs[reg].n_lobes; ++k) {
+            const int K = VSPG_FIELD_LOBES;
+            acc[reg].S[k] += t[0 * K + k];
+            acc[reg].R[0][k] += t[1 * K + k]; acc[reg].R[1][k] += t[2 * K + k]; acc[reg].R[2][k] += t[3 * K + k];
+            acc[reg].D[k] += t[4 * K + k]; acc[reg].V[k] += t[5 * K + k];
+            acc[reg].Qv[k] += t[6 * K + k]; acc[reg].Qs[k] += t[7 * K + k];
         }
     }
     /* 5. M step */

@@ -116,6 +116,11 @@ void oracle_guiding_branch_counts(long out[2], int reset);
  * own design, PARITY UNPINNED; the recording hooks follow src/pbrt/cpu/guiding.h:682-832) */
 int oracle_renderer_training_stats(OracleRenderer *r, VspgTrainStats *out);
 int oracle_train_samples_read(OracleRenderer *r, VspgTrainSample *out, size_t max_samples, size_t *n_out);
+/* Field::Update's E step, sample by sample: the float terms {S, R0, R1, R2, D, V, Qv, Qs} x VSPG_FIELD_LOBES that each of n samples
+ * lying in region R adds to the region's statistics under the weight clamp wmax (what field_update_one sums); valid[i] = 0 and
+ * zero terms for a sample that contributes nothing. */
+int oracle_train_estep_terms(const VspgFieldRegion *R, const VspgTrainSample *samples, size_t n, float wmax, float *out,
+                             int32_t *valid);
 int oracle_renderer_get_guiding_field(OracleRenderer *r, int volume_field, VspgKdNode *nodes,
                                       VspgFieldRegion *regions, int32_t *n_nodes, int32_t *n_regions);
 

@@ -76,6 +76,8 @@ def load():
         "oracle_guiding_branch_counts": (None, [C.c_long * 2, C.c_int]),
         "oracle_renderer_training_stats": (C.c_int, [vp, p(P.VspgTrainStats)]),
         "oracle_train_samples_read": (C.c_int, [vp, p(P.VspgTrainSample), C.c_size_t, p(C.c_size_t)]),
+        "oracle_train_estep_terms": (C.c_int, [p(P.VspgFieldRegion), p(P.VspgTrainSample), C.c_size_t, C.c_float, p(C.c_float),
+                                               p(C.c_int32)]),
         "oracle_renderer_get_guiding_field": (C.c_int, [vp, C.c_int, p(P.VspgKdNode), p(P.VspgFieldRegion), p(C.c_int32),
                                                         p(C.c_int32)]),
         "oracle_integrator_params_default": (None, [p(P.VspgIntegratorParams)]),
@@ -292,6 +294,23 @@ def guiding_query(fn, handle, is_volume, g, p, n_or_wo, wi, u, stream):
     rc = fn(*args)
     assert rc == 0, rc
     return dict(ok=ok, pdf=pdf, incoming_pdf=inc, vsp=vsp, ws=ws, pdf_s=pdfs)
+
+
+def train_estep_terms(region, samples, wmax):
+    """Field::Update's E step sample by sample (oracle_train_estep_terms): `region` one record of field_models.REGION_DTYPE,
+    `samples` (TRAIN_SAMPLE_DTYPE) all lying in it.  Returns (terms float32 [n, 8 * VSPG_FIELD_LOBES] in the order S, R0, R1,
+    R2, D, V, Qv, Qs; valid int32 [n])."""
+    P = load_package()
+    lib = load()
+    reg = P.VspgFieldRegion.from_buffer_copy(np.asarray(region).tobytes())
+    sm = np.ascontiguousarray(samples, dtype=P.TRAIN_SAMPLE_DTYPE)
+    n = len(sm)
+    out = np.zeros((n, 8 * P.VSPG_FIELD_LOBES), dtype=np.float32)
+    valid = np.zeros(n, dtype=np.int32)
+    rc = lib.oracle_train_estep_terms(C.byref(reg), sm.ctypes.data_as(C.POINTER(P.VspgTrainSample)), n, C.c_float(float(wmax)),
+                                      out.ctypes.data_as(C.POINTER(C.c_float)), valid.ctypes.data_as(C.POINTER(C.c_int32)))
+    assert rc == 0, rc
+    return out, valid
 
 
 def guiding_branch_counts(reset=False):
