@@ -603,6 +603,39 @@ int vspg_brick_info(VspgRenderer *r, VspgBrickInfo *out);
  * arrays, either may be NULL. */
 int vspg_brick_read(VspgRenderer *r, int32_t *index, float *octets, void *stream);
 
+/* In-place update of a grid / NanoVDB-semantics medium's values (a volume sequence's next frame, or a tensor another program has
+ * just written on the device): replaces the `nx * ny * nz` samples (x fastest, the layout the renderer was created with) of the
+ * density grid (VSPG_GRID_DENSITY) or of the temperature grid (VSPG_GRID_TEMPERATURE: a plain copy, accepted only on a renderer
+ * created WITH a temperature grid -- the kernel instantiation depends on whether there is one).  Bounds, transform, index_min,
+ * voxel_size, grid_origin, density_offset, majorant_scale and the sigma spectra stay.  Afterwards every launch and batch entry point
+ * behaves as if the renderer had been created with the new values: the majorant grid is rebuilt on the device (one workgroup per
+ * cell takes the maximum over the cell's voxel box; the per-axis box tables are the host's, those vspg_renderer_create uses) and so
+ * are the octet bricks, in the layout -- dense or indexed -- create chose (VSPG_DENSE_BRICKS is not read again; an indexed renderer
+ * stores the bricks the NEW values occupy).
+ *   memory = VSPG_MEM_HOST:   `values` is a host array.
+ *   memory = VSPG_MEM_DEVICE: `values` is a pointer on the renderer's device, readable on `stream` at the time of the call (a torch
+ *                             tensor's data_ptr(), say).  It never crosses to the host and is not copied on the device either: the
+ *                             builders read it in place.
+ * The call first finishes parked samples and suspended paths on `stream` (they end under the medium they started in), rebuilds,
+ * and synchronises `stream` before it returns, as vspg_renderer_create does: `values` may be reused at once.
+ * It touches nothing else: not the film (beyond resolving those parked samples), the image-space statistics, the VSP buffer and its
+ * ready flag, the TrBuffer, the guiding fields and the training state, the counters, the reference image or the error log.  A caller
+ * starting a new frame calls vspg_film_clear itself.
+ * NaN voxels are the caller's contract to avoid: the majorant of a box that holds one is unspecified (as create's is, where it
+ * depends on the order of a host loop).  For finite values the majorants equal create's (the sign of an all-zero box's zero apart).
+ * VSPG_EINVAL, with the renderer exactly as it was: a null argument, an unknown `which` or `memory`, n_floats != nx*ny*nz, a medium
+ * that is neither GRID nor NANOVDB, TEMPERATURE on a renderer created without a temperature grid. */
+#define VSPG_GRID_DENSITY     0
+#define VSPG_GRID_TEMPERATURE 1
+#define VSPG_MEM_HOST   0
+#define VSPG_MEM_DEVICE 1
+int vspg_renderer_update_grid(VspgRenderer *r, int which, const float *values, size_t n_floats, int memory, void *stream);
+/* Read-back of the majorant grid the kernels read (test + diagnostics), x fastest: res^3 floats with res = 16 for a GRID medium,
+ * 64 for NANOVDB semantics.  host_out: n_floats == res^3 floats (HOST array); res (may be NULL) receives the resolution.
+ * VSPG_EINVAL for other media or a wrong n_floats (res is still reported for a grid medium, so a caller can size its array).
+ * Synchronises `stream`. */
+int vspg_majorant_read(VspgRenderer *r, float *host_out, size_t n_floats, int32_t *res, void *stream);
+
 /* Primitive batch (bit-exact layer): for each i computes on device
  *   hash[i]   = Hash(f[i])                      (src/pbrt/util/hash.h:100)
  *   rng_u32[i]= RNG(Hash(f[i]),Hash(g[i])).Uniform<uint32_t>()  (util/rng.h:82-88,119-125)

@@ -27,6 +27,8 @@ TMAJ_PLAIN, TMAJ_OPTICAL_DEPTH, TMAJ_RESAMPLING = 0, 1, 2
 
 VSPG_OK, VSPG_EINVAL, VSPG_ENODEVICE, VSPG_EHIP, VSPG_ESCOPE = 0, -1, -2, -3, -4
 ARITH_EXACT, ARITH_FAST_WEIGHTS, ARITH_FAST = 0, 1, 2
+GRID_DENSITY, GRID_TEMPERATURE = 0, 1  # VSPG_GRID_*: which grid vspg_renderer_update_grid replaces ...
+MEM_HOST, MEM_DEVICE = 0, 1            # ... and VSPG_MEM_*: where its values live
 
 f3 = C.c_float * 3
 
@@ -276,6 +278,8 @@ SYMBOLS = [
     ("vspg_sample_tmaj_batch", C.c_int, [_vp, C.c_int, C.c_int, _P(VspgTmajQuery), _P(VspgTmajResult), _vp]),
     ("vspg_brick_info", C.c_int, [_vp, _P(VspgBrickInfo)]),
     ("vspg_brick_read", C.c_int, [_vp, _P(C.c_int32), _P(C.c_float), _vp]),
+    ("vspg_renderer_update_grid", C.c_int, [_vp, C.c_int, _vp, C.c_size_t, C.c_int, _vp]),
+    ("vspg_majorant_read", C.c_int, [_vp, _P(C.c_float), C.c_size_t, _P(C.c_int32), _vp]),
     ("vspg_primitives_batch", C.c_int, [_vp, C.c_int, _P(C.c_float), _P(C.c_float), _P(C.c_uint64), _P(C.c_uint32), _P(C.c_float), _vp]),
     ("vspg_renderer_training_stats", C.c_int, [_vp, _P(VspgTrainStats), _vp]),
     ("vspg_train_samples_read", C.c_int, [_vp, _P(VspgTrainSample), C.c_size_t, _P(C.c_size_t), _vp]),
@@ -524,6 +528,33 @@ def app_f_params():
     return p
 
 
+def grid_update_source(n_voxels, values, device):
+    """What vspg_renderer_update_grid is handed for `values`: (address, memory kind, stream or None).  A NumPy array is a host source
+    (float32, n_voxels elements, C-contiguous); a torch tensor is a device source (float32, n_voxels elements, contiguous, on
+    cuda:`device`) whose stream is torch's current one.  Anything else raises ValueError -- here, before the library is called."""
+    import numpy as np
+    if isinstance(values, np.ndarray):
+        if values.dtype != np.float32:
+            raise ValueError("grid values must be float32, not %s" % values.dtype)
+        if values.size != n_voxels:
+            raise ValueError("grid values must hold nx*ny*nz = %d elements, not %d" % (n_voxels, values.size))
+        if not values.flags["C_CONTIGUOUS"]:
+            raise ValueError("grid values must be C-contiguous (x fastest)")
+        return values.ctypes.data, MEM_HOST, None
+    if type(values).__module__.split(".")[0] == "torch" and hasattr(values, "data_ptr"):
+        import torch
+        if values.dtype != torch.float32:
+            raise ValueError("grid values must be float32, not %s" % values.dtype)
+        if values.numel() != n_voxels:
+            raise ValueError("grid values must hold nx*ny*nz = %d elements, not %d" % (n_voxels, values.numel()))
+        if values.device.type != "cuda" or (values.device.index or 0) != device:
+            raise ValueError("grid values must live on the renderer's device cuda:%d, not %s" % (device, values.device))
+        if not values.is_contiguous():
+            raise ValueError("grid values must be contiguous (x fastest)")
+        return values.data_ptr(), MEM_DEVICE, torch.cuda.current_stream(values.device).cuda_stream
+    raise ValueError("grid values must be a NumPy array or a torch tensor, not %s" % type(values).__name__)
+
+
 class Renderer:
     """Thin RAII wrapper over the vspg_renderer_* entry points."""
 
@@ -765,6 +796,34 @@ class Renderer:
         _check(self.lib, self.lib.vspg_brick_read(self.h, idx.ctypes.data_as(_P(C.c_int32)) if index else None,
                                                  octs.ctypes.data_as(_P(C.c_float)) if octets else None, _vp(0)))
         return idx, octs
+
+    def _update_grid(self, which, values, stream):
+        m = self.scene.medium
+        n = int(m.nx) * int(m.ny) * int(m.nz)
+        ptr, memory, cur = grid_update_source(n, values, int(self.cfg.device))
+        if stream is None:
+            stream = cur  # (a device source: torch's current stream, the one its producer ran on)
+        _check(self.lib, self.lib.vspg_renderer_update_grid(self.h, which, _vp(ptr), n, memory, _vp(stream or 0)))
+
+    def update_density(self, values, stream=None):
+        """Replace the density grid's values in place (vspg_renderer_update_grid): a float32 NumPy array (host path) or a float32
+        torch tensor on the renderer's device (device path, read where it lies), nx*ny*nz elements, x fastest.  Majorants and
+        bricks are rebuilt; film, statistics, VSP buffer, guiding fields and counters stay."""
+        self._update_grid(GRID_DENSITY, values, stream)
+
+    def update_temperature(self, values, stream=None):
+        """Replace the temperature grid's values (a renderer created with one), as update_density takes them."""
+        self._update_grid(GRID_TEMPERATURE, values, stream)
+
+    def majorant(self, stream=None):
+        """The majorant grid the kernels read (vspg_majorant_read): [R, R, R] float32 indexed z, y, x; R = 16 (GRID) or 64 (NANOVDB)."""
+        import numpy as np
+        R = 64 if self.scene.medium.type == MEDIUM_NANOVDB else 16
+        out = np.empty((R, R, R), dtype=np.float32)
+        res = C.c_int32(0)
+        _check(self.lib, self.lib.vspg_majorant_read(self.h, out.ctypes.data_as(_P(C.c_float)), out.size, C.byref(res), _vp(stream or 0)))
+        assert res.value == R
+        return out
 
     def primitives_batch(self, f, g):
         import numpy as np

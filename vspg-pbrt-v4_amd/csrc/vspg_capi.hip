@@ -1580,6 +1580,45 @@ __global__ __launch_bounds__(512) void k_brick_fill(const float *__restrict__ d,
     q[1] = hi;
 }
 
+// ---- majorant grid of a grid medium built on the device (vspg_renderer_update_grid) ------------------------------------
+// One workgroup per majorant cell: the cell's majorant is the maximum over its voxel box [lo, hi]^3.  The box separates per axis, and
+// the per-axis tables (ranges[axis * R + c] = {lo, hi} in array coordinates, clipped to the grid; hi < lo: empty) come from the host
+// (majorant_axis_ranges: the arithmetic create's builders use -- recomputed here, the NANOVDB lerp and the double division would have to
+// match the host's rounding).  A box holds a handful of voxels (a small grid under 64^3 cells) or several hundred thousand (1024^3
+// under 16^3 cells: 66^3): the threads stride over the flattened box, x fastest, so a wavefront reads runs of whole rows; then a
+// wavefront reduction through lane shuffles and one through LDS.  The maximum of finite floats does not depend on the order.
+// NVDB: the start value is 0 and the cell gets (max + density_offset) * majorant_scale; GRID: the start value is the voxel at lo.
+constexpr int kMajBlock = 256;
+template <bool NVDB>
+__global__ __launch_bounds__(kMajBlock) void k_majorant_build(const float *__restrict__ d, int nx, int ny, int R,
+                                                             const int2 *__restrict__ ranges, float density_offset, float majorant_scale,
+                                                             float *__restrict__ maj) {
+    const int c = blockIdx.x;
+    const int2 rx = ranges[c % R], ry = ranges[R + (c / R) % R], rz = ranges[2 * R + c / (R * R)];
+    const int bx = rx.y - rx.x + 1, by = ry.y - ry.x + 1, bz = rz.y - rz.x + 1;
+    // (a box lies inside the grid, and a grid holds at most 2^31 voxels: unsigned arithmetic holds the count and the strided index)
+    const unsigned n = (bx > 0 && by > 0 && bz > 0) ? (unsigned)bx * (unsigned)by * (unsigned)bz : 0u;
+    float mx = 0.f;
+    if (!NVDB && n > 0) mx = d[((size_t)rz.x * ny + ry.x) * nx + rx.x];
+    for (unsigned i = threadIdx.x; i < n; i += kMajBlock) {
+        const unsigned row = i / (unsigned)bx, zz = row / (unsigned)by;
+        const int x = rx.x + (int)(i - row * (unsigned)bx), y = ry.x + (int)(row - zz * (unsigned)by), z = rz.x + (int)zz;
+        const float v = d[((size_t)z * ny + y) * nx + x];
+        mx = mx < v ? v : mx;
+    }
+    for (int o = 32; o > 0; o >>= 1) {
+        const float v = __shfl_down(mx, o, 64);
+        mx = mx < v ? v : mx;
+    }
+    __shared__ float s_max[kMajBlock / 64];
+    if ((threadIdx.x & 63) == 0) s_max[threadIdx.x >> 6] = mx;
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        for (int w = 1; w < kMajBlock / 64; ++w) mx = mx < s_max[w] ? s_max[w] : mx;
+        maj[c] = NVDB ? (mx + density_offset) * majorant_scale : mx;
+    }
+}
+
 // ImageSpaceGuidingBuffer::Update stand-in: 5x5 box filter over the sufficient statistics,
 // then the contribution / variance criterion (own design, unpinned).
 constexpr int kIsgRadius = 2;
@@ -2256,12 +2295,47 @@ static void build_dscene(const VspgScene &sc, const VspgIntegratorParams &prm, c
     lsb::build(sc, prm, D);  // LightSampler::Create(prm.lightsampler, lights) (lightsamplers.cpp:49-64)
 }
 
+// The voxel box of a majorant cell separates per axis: ranges[axis * R + c] = {lo, hi} of cell coordinate c, in ARRAY coordinates
+// (the NANOVDB index range minus index_min), clipped to the grid; hi < lo is an empty range.  Both host builders below and the device
+// builder (k_majorant_build, vspg_renderer_update_grid) read these tables, so the three agree on every box.
+//   GRID:    SampledGrid::MaxValue(VoxelBounds(x,y,z)) (media.cpp:262-269, containers.h:838-854)
+//   NANOVDB: "Initialize majorantGrid" (media.cpp:600-671): the cell's world bounds to index space (float Lerp, double division),
+//            widened by one voxel (the trilinear filter slop), truncated, clipped to the index bounding box
+static int majorant_res(const VspgMedium &m) { return m.type == VSPG_MEDIUM_NANOVDB ? kMajResNvdb : kMajRes; }
+static std::vector<int2> majorant_axis_ranges(const VspgMedium &m) {
+    const int R = majorant_res(m);
+    const int n[3] = {m.nx, m.ny, m.nz};
+    std::vector<int2> ranges((size_t)3 * R);
+    auto lerp = [](float t, float a, float b) { return (1 - t) * a + t * b; };  // pbrt::Lerp (math.h)
+    for (int k = 0; k < 3; ++k)
+        for (int c = 0; c < R; ++c) {
+            int lo, hi;
+            if (m.type == VSPG_MEDIUM_NANOVDB) {
+                const int imin = m.index_min[k], imax = m.index_min[k] + n[k] - 1;
+                const float w0 = lerp((float)c / R, m.bounds_min[k], m.bounds_max[k]);
+                const float w1 = lerp((float)(c + 1) / R, m.bounds_min[k], m.bounds_max[k]);
+                const double i0 = ((double)w0 - (double)m.grid_origin[k]) / (double)m.voxel_size[k];  // worldToIndexF(Vec3R)
+                const double i1 = ((double)w1 - (double)m.grid_origin[k]) / (double)m.voxel_size[k];
+                const float delta = 1.f;
+                lo = std::max((int)(i0 - delta), imin) - imin;
+                hi = std::min((int)(i1 + delta), imax) - imin;
+            } else {
+                float p0 = (float)c / R, p1 = (float)(c + 1) / R;
+                int a = (int)std::floor(p0 * n[k] - .5f), b = (int)std::floor(p1 * n[k] - .5f) + 1;
+                lo = std::max(a, 0);
+                hi = std::min(b, n[k] - 1);
+            }
+            ranges[(size_t)k * R + c] = make_int2(lo, hi);
+        }
+    return ranges;
+}
+
 // GridMedium constructor: majorantGrid.Set(x,y,z, densityGrid.MaxValue(VoxelBounds(x,y,z)))
 // (src/pbrt/media.cpp:262-269; SampledGrid::MaxValue src/pbrt/util/containers.h:838-854)
 static std::vector<float> build_majorant_grid(const VspgMedium &m) {
-    const int R = 16;
+    const int R = kMajRes;
     std::vector<float> maj((size_t)R * R * R);
-    const int n[3] = {m.nx, m.ny, m.nz};
+    const std::vector<int2> ranges = majorant_axis_ranges(m);
     auto at = [&](int x, int y, int z) -> float {
         if (x < 0 || y < 0 || z < 0 || x >= m.nx || y >= m.ny || z >= m.nz) return 0.f;
         return m.density[((size_t)z * m.ny + y) * m.nx + x];
@@ -2269,18 +2343,11 @@ static std::vector<float> build_majorant_grid(const VspgMedium &m) {
     for (int z = 0; z < R; ++z)
         for (int y = 0; y < R; ++y)
             for (int x = 0; x < R; ++x) {
-                const int c[3] = {x, y, z};
-                int lo[3], hi[3];
-                for (int k = 0; k < 3; ++k) {
-                    float p0 = (float)c[k] / R, p1 = (float)(c[k] + 1) / R;
-                    int a = (int)std::floor(p0 * n[k] - .5f), b = (int)std::floor(p1 * n[k] - .5f) + 1;
-                    lo[k] = std::max(a, 0);
-                    hi[k] = std::min(b, n[k] - 1);
-                }
-                float mx = at(lo[0], lo[1], lo[2]);
-                for (int zz = lo[2]; zz <= hi[2]; ++zz)
-                    for (int yy = lo[1]; yy <= hi[1]; ++yy)
-                        for (int xx = lo[0]; xx <= hi[0]; ++xx) mx = std::max(mx, at(xx, yy, zz));
+                const int2 rx = ranges[x], ry = ranges[R + y], rz = ranges[2 * R + z];
+                float mx = at(rx.x, ry.x, rz.x);
+                for (int zz = rz.x; zz <= rz.y; ++zz)
+                    for (int yy = ry.x; yy <= ry.y; ++yy)
+                        for (int xx = rx.x; xx <= rx.y; ++xx) mx = std::max(mx, at(xx, yy, zz));
                 maj[x + R * (y + R * z)] = mx;
             }
     return maj;
@@ -2469,36 +2536,23 @@ static bool wants_training(const VspgIntegratorParams &p) {  // the field is que
 
 // NanoVDBMedium constructor, "Initialize majorantGrid" (media.cpp:600-671) over the dense copy: 64^3 cells; a
 // cell's majorant is the largest voxel value in the cell's index-space footprint widened by one voxel (the
-// trilinear filter slop), clipped to the index bounding box, then (max + densityOffset) * majorantScale.
+// trilinear filter slop), clipped to the index bounding box (majorant_axis_ranges), then (max + densityOffset) * majorantScale.
 static std::vector<float> build_majorant_grid_nvdb(const VspgMedium &m) {
     const int R = kMajResNvdb;
     std::vector<float> maj((size_t)R * R * R);
-    const int imin[3] = {m.index_min[0], m.index_min[1], m.index_min[2]};
-    const int imax[3] = {m.index_min[0] + m.nx - 1, m.index_min[1] + m.ny - 1, m.index_min[2] + m.nz - 1};
-    auto value = [&](int i, int j, int k) -> float {  // accessor.getValue: background outside the tree
-        const int x = i - imin[0], y = j - imin[1], z = k - imin[2];
+    const std::vector<int2> ranges = majorant_axis_ranges(m);
+    auto value = [&](int x, int y, int z) -> float {  // accessor.getValue: background outside the tree (array coordinates)
         if (x < 0 || y < 0 || z < 0 || x >= m.nx || y >= m.ny || z >= m.nz) return 0.f;
         return m.density[((size_t)z * m.ny + y) * m.nx + x];
     };
-    auto lerp = [](float t, float a, float b) { return (1 - t) * a + t * b; };  // pbrt::Lerp (math.h)
     for (int z = 0; z < R; ++z)
         for (int y = 0; y < R; ++y)
             for (int x = 0; x < R; ++x) {
-                const int c[3] = {x, y, z};
-                int lo[3], hi[3];
-                for (int k = 0; k < 3; ++k) {
-                    const float w0 = lerp((float)c[k] / R, m.bounds_min[k], m.bounds_max[k]);
-                    const float w1 = lerp((float)(c[k] + 1) / R, m.bounds_min[k], m.bounds_max[k]);
-                    const double i0 = ((double)w0 - (double)m.grid_origin[k]) / (double)m.voxel_size[k];  // worldToIndexF(Vec3R)
-                    const double i1 = ((double)w1 - (double)m.grid_origin[k]) / (double)m.voxel_size[k];
-                    const float delta = 1.f;
-                    lo[k] = std::max((int)(i0 - delta), imin[k]);
-                    hi[k] = std::min((int)(i1 + delta), imax[k]);
-                }
+                const int2 rx = ranges[x], ry = ranges[R + y], rz = ranges[2 * R + z];
                 float mx = 0;
-                for (int kk = lo[2]; kk <= hi[2]; ++kk)
-                    for (int jj = lo[1]; jj <= hi[1]; ++jj)
-                        for (int ii = lo[0]; ii <= hi[0]; ++ii) mx = std::max(mx, value(ii, jj, kk));
+                for (int kk = rz.x; kk <= rz.y; ++kk)
+                    for (int jj = ry.x; jj <= ry.y; ++jj)
+                        for (int ii = rx.x; ii <= rx.y; ++ii) mx = std::max(mx, value(ii, jj, kk));
                 maj[x + R * (y + R * z)] = (mx + m.density_offset) * m.majorant_scale;
             }
     return maj;
@@ -4002,6 +4056,130 @@ int vspg_brick_read(VspgRenderer *r, int32_t *index, float *octets, void *stream
     if (octets && r->n_bricks) HIPCHK(hipMemcpyAsync(octets, r->octets, r->n_bricks * 512 * 2 * sizeof(float4), hipMemcpyDeviceToHost, s));
     HIPCHK(hipStreamSynchronize(s));
     return 0;
+}
+
+int vspg_majorant_read(VspgRenderer *r, float *host_out, size_t n_floats, int32_t *res, void *stream) {
+    if (!r || !host_out) return fail(VSPG_EINVAL, "null argument");
+    if (!has_bricks(r)) return fail(VSPG_EINVAL, "renderer has no grid medium");
+    const int R = majorant_res(r->scene.medium);
+    if (res) *res = R;
+    if (n_floats != (size_t)R * R * R) return fail(VSPG_EINVAL, "n_floats is not the majorant grid's resolution cubed");
+    HIPCHK(hipSetDevice(r->cfg.device));
+    HIPCHK(hipMemcpyAsync(host_out, r->majorant, n_floats * sizeof(float), hipMemcpyDeviceToHost, (hipStream_t)stream));
+    HIPCHK(hipStreamSynchronize((hipStream_t)stream));
+    return 0;
+}
+
+// The density update's device work, behind the refusals and the flush: majorants into r->majorant (in place), then the bricks as create
+// builds them -- flags on the device, slot numbering on the host, fill on the device -- from `d`, the new samples ON THE DEVICE.
+// Temporaries are the caller's to free (`tmp`), whatever the outcome.
+static int rebuild_density_storage(VspgRenderer *r, const float *d, hipStream_t s, std::vector<void *> &tmp) {
+    const VspgMedium &m = r->scene.medium;
+    const int nx = m.nx, ny = m.ny, nz = m.nz;
+    const bool nvdb = m.type == VSPG_MEDIUM_NANOVDB;
+    auto dev_alloc = [&](void **p, size_t bytes) {
+        const hipError_t e = hipMalloc(p, bytes);
+        if (e == hipSuccess) tmp.push_back(*p);
+        return e;
+    };
+    {   // majorants: the three per-axis box tables are the host's (majorant_axis_ranges), the maxima the device's
+        const int R = majorant_res(m);
+        const std::vector<int2> ranges = majorant_axis_ranges(m);
+        const int n[3] = {nx, ny, nz};
+        for (int k = 0; k < 3; ++k)
+            for (int c = 0; c < R; ++c) {  // (what the kernel indexes with: inside the grid, or empty)
+                const int2 q = ranges[(size_t)k * R + c];
+                if (q.y >= q.x && (q.x < 0 || q.y > n[k] - 1)) return fail(VSPG_EINVAL, "majorant cell footprint outside the density grid");
+            }
+        int2 *dranges = nullptr;
+        HIPCHK(dev_alloc((void **)&dranges, ranges.size() * sizeof(int2)));
+        HIPCHK(hipMemcpyAsync(dranges, ranges.data(), ranges.size() * sizeof(int2), hipMemcpyHostToDevice, s));
+        HIPCHK(hipStreamSynchronize(s));  // (`ranges` is pageable and leaves scope)
+        if (nvdb) hipLaunchKernelGGL(k_majorant_build<true>, dim3((unsigned)(R * R * R)), dim3(kMajBlock), 0, s, d, nx, ny, R, dranges,
+                                     m.density_offset, m.majorant_scale, r->majorant);
+        else hipLaunchKernelGGL(k_majorant_build<false>, dim3((unsigned)(R * R * R)), dim3(kMajBlock), 0, s, d, nx, ny, R, dranges, 0.f, 1.f,
+                                r->majorant);
+        HIPCHK(hipGetLastError());
+    }
+    const int bnx = r->hscene.bnx, bny = r->hscene.bny, bnz = r->hscene.bnz;
+    const size_t nb = (size_t)bnx * bny * bnz;
+    const bool dense = r->brick_index == nullptr;  // the layout create chose
+    std::vector<int32_t> index(nb), active;
+    if (dense) {
+        for (size_t b = 0; b < nb; ++b) active.push_back((int32_t)b);
+    } else {
+        int32_t *dflags = nullptr;
+        HIPCHK(dev_alloc((void **)&dflags, nb * sizeof(int32_t)));
+        hipLaunchKernelGGL(k_brick_flags, dim3((unsigned)nb), dim3(kBlock), 0, s, d, nx, ny, nz, bnx, bny, dflags);
+        HIPCHK(hipGetLastError());
+        std::vector<int32_t> flags(nb);
+        HIPCHK(hipMemcpyAsync(flags.data(), dflags, nb * sizeof(int32_t), hipMemcpyDeviceToHost, s));
+        HIPCHK(hipStreamSynchronize(s));
+        for (size_t b = 0; b < nb; ++b) {
+            index[b] = flags[b] ? (int32_t)active.size() : -1;
+            if (flags[b]) active.push_back((int32_t)b);
+        }
+        // the set of stored bricks follows the new values: another count is another allocation (one placeholder brick when none)
+        if (active.size() != r->n_bricks) {
+            float4 *fresh = nullptr;
+            HIPCHK(hipMalloc(&fresh, (active.empty() ? 1 : active.size()) * 512 * 2 * sizeof(float4)));
+            (void)hipFree(r->octets);  // (the stream is idle: the caller synchronised it behind the flush, and again above)
+            r->octets = fresh;
+            r->hscene.octets = fresh;
+            HIPCHK(hipMemcpyAsync(reinterpret_cast<char *>(r->dscene) + offsetof(DScene, octets), &r->hscene.octets, sizeof r->hscene.octets,
+                                  hipMemcpyHostToDevice, s));
+        }
+        r->n_bricks = active.size();
+        HIPCHK(hipMemcpyAsync(r->brick_index, index.data(), nb * sizeof(int32_t), hipMemcpyHostToDevice, s));
+    }
+    if (!active.empty()) {
+        int32_t *dactive = nullptr;
+        HIPCHK(dev_alloc((void **)&dactive, active.size() * sizeof(int32_t)));
+        HIPCHK(hipMemcpyAsync(dactive, active.data(), active.size() * sizeof(int32_t), hipMemcpyHostToDevice, s));
+        hipLaunchKernelGGL(k_brick_fill, dim3((unsigned)active.size()), dim3(512), 0, s, d, nx, ny, nz, bnx, bny, dactive, r->octets);
+        HIPCHK(hipGetLastError());
+    }
+    HIPCHK(hipStreamSynchronize(s));  // as create: the storage is complete, and the host vectors above may go
+    return 0;
+}
+
+int vspg_renderer_update_grid(VspgRenderer *r, int which, const float *values, size_t n_floats, int memory, void *stream) {
+    // every refusal comes before anything of the renderer changes -- parked samples included
+    if (!r || !values) return fail(VSPG_EINVAL, "null argument");
+    if (which != VSPG_GRID_DENSITY && which != VSPG_GRID_TEMPERATURE) return fail(VSPG_EINVAL, "unknown grid (VSPG_GRID_DENSITY / VSPG_GRID_TEMPERATURE)");
+    if (memory != VSPG_MEM_HOST && memory != VSPG_MEM_DEVICE) return fail(VSPG_EINVAL, "unknown memory kind (VSPG_MEM_HOST / VSPG_MEM_DEVICE)");
+    if (!has_bricks(r)) return fail(VSPG_EINVAL, "renderer has no grid medium");
+    const size_t n = (size_t)r->scene.medium.nx * r->scene.medium.ny * r->scene.medium.nz;
+    if (n_floats != n) return fail(VSPG_EINVAL, "n_floats is not nx * ny * nz of the grid the renderer was created with");
+    if (which == VSPG_GRID_TEMPERATURE && !r->temperature)
+        return fail(VSPG_EINVAL, "the renderer was created without a temperature grid (its kernels do not read one)");
+    HIPCHK(hipSetDevice(r->cfg.device));
+    hipStream_t s = (hipStream_t)stream;
+    if (const int rc = flush_parked_samples(r, s)) return rc;  // (paths in flight end under the medium they started in)
+    HIPCHK(hipStreamSynchronize(s));  // no launch may still read the old grid
+    if (which == VSPG_GRID_TEMPERATURE) {
+        HIPCHK(hipMemcpyAsync(r->temperature, values, n * sizeof(float), memory == VSPG_MEM_HOST ? hipMemcpyHostToDevice : hipMemcpyDeviceToDevice, s));
+        HIPCHK(hipStreamSynchronize(s));
+        return 0;
+    }
+    // a host source is staged on the device for the builders, as create stages it; a device source is read where it lies
+    std::vector<void *> tmp;
+    int rc = 0;
+    const float *d = values;
+    if (memory == VSPG_MEM_HOST) {
+        float *staged = nullptr;
+        hipError_t e = hipMalloc(&staged, n * sizeof(float));
+        if (e == hipSuccess) {
+            tmp.push_back(staged);
+            e = hipMemcpyAsync(staged, values, n * sizeof(float), hipMemcpyHostToDevice, s);
+        }
+        if (e != hipSuccess) rc = fail(VSPG_EHIP, std::string("staging the density grid: ") + hipGetErrorName(e));
+        d = staged;
+    }
+    if (!rc) rc = rebuild_density_storage(r, d, s, tmp);
+    if (rc) (void)hipStreamSynchronize(s);
+    for (void *p : tmp) (void)hipFree(p);
+    return rc;
 }
 
 // A field that upload_field can take: absent / empty (the field is cleared), or arrays with children after their parent,

@@ -667,6 +667,16 @@ void GuidedVolPathVSPGIntegrator::SetMseReference(const std::vector<float> &fram
     if (vspg_renderer_set_reference_image(renderer, frameImage.data(), nullptr) != 0) throw Error(vspg_last_error());
     mseOut = out;
 }
+void GuidedVolPathVSPGIntegrator::SetMediumDensity(const std::vector<float> &values) {
+    if (vspg_renderer_update_grid(renderer, VSPG_GRID_DENSITY, values.data(), values.size(), VSPG_MEM_HOST, nullptr) != 0) throw Error(vspg_last_error());
+}
+void GuidedVolPathVSPGIntegrator::SetMediumTemperature(const std::vector<float> &values) {
+    if (vspg_renderer_update_grid(renderer, VSPG_GRID_TEMPERATURE, values.data(), values.size(), VSPG_MEM_HOST, nullptr) != 0) throw Error(vspg_last_error());
+}
+void GuidedVolPathVSPGIntegrator::ClearFilm() {
+    if (vspg_film_clear(renderer, nullptr) != 0) throw Error(vspg_last_error());
+    sppDone = 0;
+}
 
 void GuidedVolPathVSPGIntegrator::Render() {
     // ImageTileIntegrator::Render (integrators.cpp:123-239): waves of 1 spp, PostProcessWave each

@@ -204,6 +204,13 @@ class GuidedVolPathVSPGIntegrator : public Integrator {
     // `out` (not owned) when it ends.  Recording completes the film after every wave, so the carry of in-flight paths between
     // one-sample waves is given up.  Not covered: vspg_pbrt_sharded.
     void SetMseReference(const std::vector<float> &frameImage, std::FILE *out);
+    // The next frame of a volume sequence: replace the grid medium's density / temperature values in place (vspg_renderer_update_grid,
+    // host source; nx*ny*nz values in the layout the scene was created with).  Majorants and bricks are rebuilt on the device; the BVH,
+    // the light sampler, the guiding fields, the VSP buffer, the TrBuffer and the film stay -- ClearFilm() starts the new frame's film.
+    // Throw on refusal: a medium that is no grid, a wrong size, a temperature grid the scene never had.
+    void SetMediumDensity(const std::vector<float> &values);
+    void SetMediumTemperature(const std::vector<float> &values);
+    void ClearFilm();             // vspg_film_clear: the film to zero (statistics, VSP buffer and fields stay); Render() starts at wave 0 again
     // The film's file (RGBFilm::WriteImage, film.cpp:531-569), format by extension:
     //   .exr  the pixel bounds resolved ON THE DEVICE (vspg_film_resolve, scan-line layout) and written as they arrive: HALF channels
     //         B, G, R by default, FLOAT with fp16 = false (the Film's "savefp16"); dataWindow = the pixel bounds, displayWindow = the
