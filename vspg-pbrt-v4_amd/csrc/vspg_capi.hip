@@ -2127,6 +2127,7 @@ static void build_dscene(const VspgScene &sc, const VspgIntegratorParams &prm, c
     using namespace hostmath;
     memset(D, 0, sizeof *D);
     D->n_quads = sc.n_quads;
+    int frame = 0;   // the axis frame the rectangle tests are in after record i - 1 (IsectRec)
     for (int i = 0; i < sc.n_quads; ++i) {
         const VspgQuad &in = sc.quads[i];
         DQuad &q = D->quads[i];
@@ -2158,26 +2159,7 @@ static void build_dscene(const VspgScene &sc, const VspgIntegratorParams &prm, c
         q.is_light = light;
         q.has_lobes = lobes;
         q.flags = surf_flags_of(in.material, in.medium_interface);
-        // axis-aligned fast path: n, e1, e2 each have exactly one non-zero component
-        auto single_axis = [](const float *v) {
-            int nz = 0, ax = -1;
-            for (int k = 0; k < 3; ++k)
-                if (v[k] != 0) { nz++; ax = k; }
-            return nz == 1 ? ax : -1;
-        };
-        int an = single_axis(q.n), a1 = single_axis(q.e1), a2 = single_axis(q.e2);
-        IsectRec &rec = D->irec[i];
-        memset(&rec, 0, sizeof rec);
-        if (an >= 0 && a1 >= 0 && a2 >= 0 && an != a1 && an != a2 && a1 != a2 && std::fabs(q.n[an]) == 1.0f) {
-            rec.kind = 1;
-            rec.axes = an | (a1 << 2) | (a2 << 4);
-            rec.f[0] = q.n[an]; rec.f[1] = q.p00[an]; rec.f[2] = q.p00[a1]; rec.f[3] = q.p00[a2];
-            rec.f[4] = q.e1[a1]; rec.f[5] = q.e2[a2]; rec.f[6] = q.inv_l1; rec.f[7] = q.inv_l2;
-        } else {
-            rec.kind = 0;
-            for (int k = 0; k < 3; ++k) { rec.f[k] = q.n[k]; rec.f[3 + k] = q.p00[k]; rec.f[6 + k] = q.e1[k]; rec.f[9 + k] = q.e2[k]; }
-            rec.f[12] = q.inv_l1; rec.f[13] = q.inv_l2;
-        }
+        frame = isect_rec_build(&D->irec[i], q.n, q.p00, q.e1, q.e2, q.inv_l1, q.inv_l2, frame);
         if (light) D->light_quads[D->n_lights++] = i;
     }
     D->n_inf = sc.n_infinite_lights;

@@ -547,13 +547,53 @@ struct DQuad {
 // (MediumInterface with inside != outside), 0 for every other surface (the ray's medium carries on, interaction.h:218-229)
 enum { SURF_INTERFACE = 1, SURF_IFACE_SHIFT = 1 };
 // Packed per-rectangle intersection record: ONE 64-byte scalar load per test (s_load_dwordx16) with
-// no dependent address arithmetic.  kind 0: generic {n, p00, e1, e2, inv_l1, inv_l2}; kind 1: axis
-// aligned {nsign, pa = p00[axis], pu = p00[uaxis], pv = p00[vaxis], l1, l2, inv_l1, inv_l2}.
+// no dependent address arithmetic.  kind 0: generic {n, p00, e1, e2, inv_l1, inv_l2}, tested in the scene frame (frame axis 0).
+// kind 1: axis aligned, tested in the FRAME OF ITS AXIS a -- the ray rotated cyclically until .x holds component a, .y component
+// a+1 and .z component a+2 (mod 3): {nsign, pa = p00[a], p00[a+1], p00[a+2], extent along a+1, extent along a+2, and the 1/|e|^2
+// that go with them}.  Where e1 lies along a+2 the u and v fields are stored swapped (kIsectUvSwapped): the same operations run
+// on the same operands, the caller trades the two results back.  The records are walked in index order from the scene frame, so
+// each one also says how many cyclic steps (x,y,z) <- (y,z,x) lead from its predecessor's frame to its own (0..2).
+// `axes` also repeats the kind (kIsectAxisAligned): the one scalar the walk waits for before it can turn the ray and branch.
+enum { kIsectStepsMask = 3, kIsectUvSwapped = 4, kIsectAxisAligned = 8, kIsectAxisShift = 4 };
 struct IsectRec {
     float f[14];
     int32_t kind;   // 0 generic, 1 axis-aligned
-    int32_t axes;   // axis | uaxis << 2 | vaxis << 4
+    int32_t axes;   // steps from the previous record's frame | kIsectUvSwapped | kIsectAxisAligned | frame axis << kIsectAxisShift
 };
+// The record of one rectangle, from what build_dscene derives; `cur` is the frame axis of the record before it (0 for the first),
+// the return value this record's.  Host code (tests/test_rect_frame_bits.py compiles it stand-alone).
+// Axis-aligned fast path: n, e1, e2 each have exactly one non-zero component, on three different axes, and n is +-1 there.
+inline int isect_rec_build(IsectRec *rec, const float *n, const float *p00, const float *e1, const float *e2, float inv_l1, float inv_l2, int cur) {
+    int ax[3];
+    const float *vec[3] = {n, e1, e2};
+    for (int j = 0; j < 3; ++j) {
+        int nz = 0;
+        ax[j] = -1;
+        for (int k = 0; k < 3; ++k)
+            if (vec[j][k] != 0) { nz++; ax[j] = k; }
+        if (nz != 1) ax[j] = -1;
+    }
+    const int an = ax[0], a1 = ax[1], a2 = ax[2];
+    for (int k = 0; k < 14; ++k) rec->f[k] = 0;
+    int frame = 0;
+    bool swapped = false;
+    if (an >= 0 && an <= 2 && a1 >= 0 && a2 >= 0 && an != a1 && an != a2 && a1 != a2 && (n[an] == 1.0f || n[an] == -1.0f)) {
+        swapped = a1 != (an + 1) % 3;   // e1 along a+2: u and v trade places
+        const int au = swapped ? a2 : a1, av = swapped ? a1 : a2;
+        frame = an;
+        rec->kind = 1;
+        rec->f[0] = n[an]; rec->f[1] = p00[an]; rec->f[2] = p00[au]; rec->f[3] = p00[av];
+        rec->f[4] = swapped ? e2[a2] : e1[a1]; rec->f[5] = swapped ? e1[a1] : e2[a2];
+        rec->f[6] = swapped ? inv_l2 : inv_l1; rec->f[7] = swapped ? inv_l1 : inv_l2;
+    } else {
+        rec->kind = 0;
+        for (int k = 0; k < 3; ++k) { rec->f[k] = n[k]; rec->f[3 + k] = p00[k]; rec->f[6 + k] = e1[k]; rec->f[9 + k] = e2[k]; }
+        rec->f[12] = inv_l1; rec->f[13] = inv_l2;
+    }
+    if (cur < 0 || cur > 2) cur = 0;
+    rec->axes = ((frame - cur + 3) % 3) | (swapped ? kIsectUvSwapped : 0) | (rec->kind == 1 ? kIsectAxisAligned : 0) | (frame << kIsectAxisShift);
+    return frame;
+}
 // guiding field in HBM (see vspg_guiding.h): [0] surface, [1] volume; nodes == nullptr -> untrained
 struct DField {
     int32_t n_nodes, n_regions;
@@ -794,20 +834,36 @@ VDEV bool beyond(float num, float denom, float tMax) {
     return __builtin_fabsf(num) > tMax * __builtin_fabsf(denom) * 1.000001f;
 }
 VDEV float comp(V3 v, int axis) { return axis == 0 ? v.x : (axis == 1 ? v.y : v.z); }  // axis is wave-uniform
+// two registers trade contents in one instruction (v_swap_b32); a cyclic step of a vector is two of them, where moves take four
+VDEV void swap_regs(float &a, float &b) { asm("v_swap_b32 %0, %1" : "+v"(a), "+v"(b)); }
+// The ray in the frame of the next record (IsectRec): `steps` cyclic steps (x,y,z) <- (y,z,x).  `steps` is wave-uniform, so the
+// loop is a scalar branch around four instructions; it is ONE step in a loop and not a rotation by one or by two as straight-line
+// code because the loops over the records are inlined several times over.  The mask bounds it whatever a record holds.
+VDEV void rect_frame(V3 &o, V3 &d, int steps) {
+#pragma nounroll
+    for (int k = steps & kIsectStepsMask; k > 0; --k) {
+        swap_regs(o.x, o.y);
+        swap_regs(o.y, o.z);
+        swap_regs(d.x, d.y);
+        swap_regs(d.y, d.z);
+    }
+}
+// o, d: the ray in the frame of the record's axis (rect_frame).  A kIsectUvSwapped record reports (v, u).
 VDEV bool rect_hit_uv(const IsectRec &r, V3 o, V3 d, float tMax, float *tHit, float *uHit, float *vHit) {
     float num, denom, u, v, t;
-    if (r.kind == 1) {
+    if (r.axes & kIsectAxisAligned) {
         // axis-aligned rectangle: n.d == nsign*d[a] and n.(p00-o) == nsign*(p00[a]-o[a]) exactly (the other
-        // products are +-0), so t == (p00[a]-o[a])/d[a] exactly; likewise (p-p00).e1 == rel[uaxis]*l1.
-        const int a = r.axes & 3, ua = (r.axes >> 2) & 3, va = (r.axes >> 4) & 3;
-        denom = r.f[0] * comp(d, a);
-        num = r.f[0] * (r.f[1] - comp(o, a));
-        bool cand = (num > 0 && denom > 0) || (num < 0 && denom < 0);
-        if (!cand) return false;
+        // products are +-0), so t == (p00[a]-o[a])/d[a] exactly -- nsign = +-1 negates both, which no IEEE quotient
+        // and no absolute value sees, so it is left out; likewise (p-p00).e1 == rel[uaxis]*l1.
+        denom = d.x;
+        num = r.f[1] - o.x;
+        // the sign pre-test on the bit patterns: zeros, infinities and NaNs of equal sign go on to the division
+        // and are rejected by the exact tests on t
+        if ((int32_t)(__builtin_bit_cast(uint32_t, num) ^ __builtin_bit_cast(uint32_t, denom)) < 0) return false;
         if (beyond(num, denom, tMax)) return false;
         t = num / denom;
         if (!(t > 0) || !(t < tMax)) return false;
-        float pu = comp(o, ua) + comp(d, ua) * t, pv = comp(o, va) + comp(d, va) * t;
+        float pu = o.y + d.y * t, pv = o.z + d.z * t;
         u = ((pu - r.f[2]) * r.f[4]) * r.f[6];
         v = ((pv - r.f[3]) * r.f[5]) * r.f[7];
     } else {
@@ -829,6 +885,43 @@ VDEV bool rect_hit_uv(const IsectRec &r, V3 o, V3 d, float tMax, float *tHit, fl
     *uHit = u;
     *vHit = v;
     return true;
+}
+// The closest rectangle of `n` records in index order -- the first one keeps winning equal distances -- with the winner's (u, v) in
+// the rectangle's own e1 / e2 order.  *tBest = tMax, *iBest = 0 and (u, v) = (0, 0) where nothing is hit.
+VDEV bool rects_closest(const IsectRec *recs, int n, V3 o, V3 d, float tMax, float *tBest, int *iBest, float *uBest, float *vBest) {
+    bool hit = false;
+    float bt = tMax, bu = 0, bv = 0;
+    int bi = 0;
+    V3 fo = o, fd = d;   // the ray in the current record's frame
+    for (int i = 0; i < n; ++i) {
+        const IsectRec &r = recs[i];
+        float t, u, v;
+        rect_frame(fo, fd, r.axes);
+        if (rect_hit_uv(r, fo, fd, bt, &t, &u, &v)) {
+            const bool swapped = (r.axes & kIsectUvSwapped) != 0;   // wave-uniform
+            hit = true;
+            bt = t;
+            bi = i;
+            bu = swapped ? v : u;
+            bv = swapped ? u : v;
+        }
+    }
+    *tBest = bt;
+    *iBest = bi;
+    *uBest = bu;
+    *vBest = bv;
+    return hit;
+}
+VDEV bool rects_any(const IsectRec *recs, int n, V3 o, V3 d, float tMax) {
+    bool any = false;
+    V3 fo = o, fd = d;
+    for (int i = 0; i < n; ++i) {
+        const IsectRec &r = recs[i];
+        float t, u, v;   // (u, v) of a swapped record trade places: the [0,1]^2 test does not care
+        rect_frame(fo, fd, r.axes);
+        any = any || rect_hit_uv(r, fo, fd, tMax, &t, &u, &v);
+    }
+    return any;
 }
 VDEV bool quad_hit_uv(const DQuad &q, V3 o, V3 d, float tMax, float *tHit, float *uHit, float *vHit) {
     V3 n = ld3(q.n), p00 = ld3(q.p00);
@@ -1143,20 +1236,8 @@ VDEV SphereSurf sphere_interaction(const DSphere &S, V3 pHit) {
 template <bool FULL = true>
 VLEAF Isect scene_intersect(const DScene &S, V3 o, V3 d, float tMax) {
     Isect best;
-    best.hit = false;
-    best.t = tMax;
-    best.quad = 0;
-    float bu = 0, bv = 0;
-    for (int i = 0; i < S.n_quads; ++i) {
-        float t, u, v;
-        if (rect_hit_uv(S.irec[i], o, d, best.t, &t, &u, &v)) {
-            best.hit = true;
-            best.t = t;
-            best.quad = i;
-            bu = u;
-            bv = v;
-        }
-    }
+    float bu, bv;
+    best.hit = rects_closest(S.irec, S.n_quads, o, d, tMax, &best.t, &best.quad, &bu, &bv);
     const DQuad &q = quad_at(best.quad);  // per-lane index: LDS copy
     best.p = quad_point(q, bu, bv);
     best.n = ld3(q.n);
@@ -1190,11 +1271,7 @@ VLEAF Isect scene_intersect(const DScene &S, V3 o, V3 d, float tMax) {
 }
 template <bool FULL = true>
 VLEAF bool scene_intersect_any(const DScene &S, V3 o, V3 d, float tMax) {
-    bool any = false;
-    for (int i = 0; i < S.n_quads; ++i) {
-        float t, u, v;
-        any = any || rect_hit_uv(S.irec[i], o, d, tMax, &t, &u, &v);
-    }
+    bool any = rects_any(S.irec, S.n_quads, o, d, tMax);
     if (FULL && S.n_tris > 0 && !any) any = bvh_any(S, o, d, tMax);
     if (FULL && S.n_spheres > 0 && !any) {
         for (int i = 0; i < S.n_spheres; ++i) {
