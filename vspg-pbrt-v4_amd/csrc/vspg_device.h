@@ -349,6 +349,14 @@ VLEAF float cosf_(float x) {
     if constexpr (kArith >= 2) return __builtin_amdgcn_cosf(__builtin_amdgcn_fractf(x * 0.159154937f));
     else return vspg_libm::cosf_host_exact(x);
 }
+VLEAF void sincosf_(float x, float *s, float *c) {  // sinf_(x) and cosf_(x) as a pair
+    if constexpr (kArith >= 2) {  // the hardware's v_sin_f32 / v_cos_f32: nothing to share
+        *s = sinf_(x);
+        *c = cosf_(x);
+    } else {  // the host-exact pair: one reduction, each polynomial once (vspg_libm.h)
+        vspg_libm::sincosf_host_exact(x, s, c);
+    }
+}
 VLEAF float neg_log1m_d(float x) {  // -std::log(1.0 - x)
     if constexpr (kArith >= 2) return -(__builtin_amdgcn_logf(1 - x) * 0.693147182f);
     else return (float)(-vspg_libm::log_host_exact(1.0 - (double)x));
@@ -462,7 +470,9 @@ VDEV V3 hg_post(V3 wo, float g, float sinTheta, float cosTheta, float sinPhi, fl
 VDEV V3 sample_henyey_greenstein(V3 wo, float g, float u0, float u1, float *pdf) {
     float st, ct;
     float phi = hg_pre(g, u0, u1, &st, &ct);
-    return hg_post(wo, g, st, ct, sinf_(phi), cosf_(phi), pdf);
+    float sinPhi, cosPhi;
+    sincosf_(phi, &sinPhi, &cosPhi);
+    return hg_post(wo, g, st, ct, sinPhi, cosPhi, pdf);
 }
 // SampleCosineHemisphere / SampleUniformDiskConcentric (sampling.h:325-341, 409-413), split the same way
 VDEV float cos_hemi_pre(float u0, float u1, float *r, bool *degenerate) {
@@ -485,7 +495,9 @@ VDEV V3 sample_cosine_hemisphere(float u0, float u1) {
     float r;
     bool deg;
     float theta = cos_hemi_pre(u0, u1, &r, &deg);
-    return cos_hemi_post(r, deg, sinf_(theta), cosf_(theta));
+    float sinTheta, cosTheta;
+    sincosf_(theta, &sinTheta, &cosTheta);
+    return cos_hemi_post(r, deg, sinTheta, cosTheta);
 }
 
 // ---------------------------------------------------------------------------------------
@@ -528,6 +540,16 @@ VDEV V3 offset_ray_origin(P3i pi, V3 n, V3 w) {
     if (dot(w, n) < 0) offset = -offset;
     V3 po = pi.mid() + offset;
     return V3{offset_axis(po.x, offset.x), offset_axis(po.y, offset.y), offset_axis(po.z, offset.z)};
+}
+// offset_ray_origin(pi, n = (0, 0, 0), w) for every pi and w, bit for bit: what a medium vertex spawns its rays from.  With a zero
+// normal d = 0 . err and offset = 0 * d are +0 in every component -- or NaN in every component where pi holds an infinity or a NaN
+// (err is inf - inf there) --, dot(w, n) is +-0 or NaN and never < 0, and offset_axis keeps po for an offset of +0 or NaN.  What
+// is left runs the same operations on the same operands: the sign test, its negation and the three offset_axis steps are gone.
+// (`pi.mid() + 0` alone would miss the NaN cases: tests/test_needless_work_bits.py holds both against offset_ray_origin.)
+VDEV V3 medium_ray_origin(P3i pi) {
+    const V3 n = V3{0.f, 0.f, 0.f};
+    const float d = dot(n, pi.err());
+    return pi.mid() + n * d;
 }
 
 // ---------------------------------------------------------------------------------------

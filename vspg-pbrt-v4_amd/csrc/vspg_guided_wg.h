@@ -187,7 +187,8 @@ VDEV bool li_vertex_guided_wg(const DScene &S, const Medium &medium, const Pool 
                 okf = !(a1 == 0 || !c.bsdf.has_lobes);
                 ang = cos_hemi_pre(ua, ub, &a0, &degenerate);
             }
-            const float sinA = sinf_(ang), cosA = cosf_(ang);
+            float sinA, cosA;
+            sincosf_(ang, &sinA, &cosA);
             if (volume_vertex) {
                 w0 = hg_post(-st.rd, vg, a0, a1, sinA, cosA, &sf0);
                 ok0 = true;

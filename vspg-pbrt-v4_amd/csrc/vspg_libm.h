@@ -430,6 +430,28 @@ VSPG_HD float cosf_host_exact(float y) {
     double s = sincosf_sign(n & 3);
     return sincosf_poly(x * s, x * x, (n & 2) != 0, n ^ 1);
 }
+// sinf_host_exact(y) and cosf_host_exact(y) as a pair.  The two share the reduction, and each evaluates one of the SAME two
+// polynomials of the same arguments -- the sine polynomial where its quadrant number is even, the cosine polynomial where it is
+// odd, and cosf's number is sinf's with bit 0 flipped.  As two calls a wavefront whose lanes hold quadrants of both parities runs
+// both polynomials twice, each under half a mask, after two reductions; here every lane evaluates each polynomial once and picks.
+// The same operations on the same operands, so the same bits (tests/test_needless_work_bits.py: every float in [0, 8] and its
+// negative, the range tests/test_libm_model.py::test_sincos_exhaustive pins).
+VSPG_HD void sincosf_host_exact(float y, float *sin_y, float *cos_y) {
+    uint32_t top = (asuint(y) >> 20) & 0x7ffu;
+    if (top > 0x42eu) {  // |y| >= 120, inf, nan
+        *sin_y = VSPG_LIBM_OUT_OF_SCOPE((float)sin((double)y));
+        *cos_y = VSPG_LIBM_OUT_OF_SCOPE((float)cos((double)y));
+        return;
+    }
+    int n;
+    double x = sincosf_reduce_fast((double)y, &n);
+    double s = sincosf_sign(n & 3);
+    const float ps = sincosf_poly(x * s, x * x, (n & 2) != 0, 0), pc = sincosf_poly(x * s, x * x, (n & 2) != 0, 1);
+    const bool odd = (n & 1) != 0;
+    const float r = odd ? pc : ps;
+    *sin_y = y == 0.f ? y : r;
+    *cos_y = odd ? ps : pc;
+}
 
 // ---- atanhf (std::atanh(float) of SampleVisibleWavelengths, util/sampling.h:169-171: the wavelengths a temperature grid's
 // blackbody emission is evaluated at).  glibc 2.35: sysdeps/ieee754/flt-32/e_atanhf.c (0.5 * log1pf(...)) over s_log1pf.c, the

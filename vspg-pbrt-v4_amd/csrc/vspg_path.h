@@ -176,6 +176,23 @@ VDEV float light_pdf_li(const DQuad &q, const LsCtx &ctx, V3 wi) {  // shapes.cp
     float pdf = wrcp(q.area) * wdiv(len2(d), absdot(ld3(q.n), -wi));
     return isinf_(pdf) ? 0 : pdf;
 }
+// light_pdf_li for the ray that has just HIT q, in the rectangles-only instantiations: `pHit` is the Isect::p scene_intersect
+// delivered for the segment (ro, wi).  light_pdf_li would intersect q again from an origin it rebuilds out of the previous vertex,
+// and that origin is the segment's own: after a surface vertex vertex_tail stored offset_ray_origin(pi, n, wi) in ro -- the same
+// function of the same (Isect::p, rectangle, wi) the context expands to --, after a medium vertex ro is the vertex itself and the
+// rebuilt origin is (vp + vp) / 2 + 0, which is vp but for the sign of a zero component.  With the same ray the plane formula of
+// quad_hit_uv accepts what rect_hit_uv accepted and finds the same t and the same (u, v) but for a zero's sign
+// (tests/test_rect_frame_bits.py), so its point differs from pHit at most in the sign of a zero component; that sign ends in the
+// squares of len2.  Proved for rays whose components are finite with |vp| <= FLT_MAX / 2 (vp + vp does not overflow), checked on
+// the host by tests/test_needless_work_bits.py; rays with an infinite or NaN component are excluded -- the plane formula's dot
+// products turn 0 * inf into NaN where the axis-aligned test forms no product, and no such ray has a defined result in either text.
+// Full scenes keep light_pdf_li: after LI_SKIP the ray no longer starts at the previous vertex.
+VDEV float light_pdf_li_hit(const DQuad &q, const LsCtx &ctx, V3 wi, V3 pHit) {
+    V3 p = p3i_from_err(pHit, ld3(q.perr)).mid();
+    V3 d = ctx.pi.mid() - p;
+    float pdf = wrcp(q.area) * wdiv(len2(d), absdot(ld3(q.n), -wi));
+    return isinf_(pdf) ? 0 : pdf;
+}
 
 // ---------------------------------------------------------------------------------------
 // per-lane counters (reduced per workgroup at kernel end)
@@ -273,7 +290,11 @@ VDEV Spec sample_Ld_shadow(const DScene &S, const Medium &medium, const Intr &in
                            float scatterPDF, Spec r_p, PC &pc, bool delta_light = false) {
     constexpr bool kFull = !Medium::kSimpleScene;
     // lightRay = intr.SpawnRayTo(ls->pLight) (interaction.h:111-115, ray.h:103-108)
-    V3 pf = offset_ray_origin(intr.pi, intr.n, ls.pLight.mid() - intr.pi.mid());
+    // A medium vertex (n = 0) takes no offset: medium_ray_origin is offset_ray_origin without the steps a zero normal leaves
+    // idle.  A branch, so that a wavefront of volume vertices only -- the common chunk -- skips the surface side as a whole.
+    V3 pf;
+    if (intr.is_surface) pf = offset_ray_origin(intr.pi, intr.n, ls.pLight.mid() - intr.pi.mid());
+    else pf = medium_ray_origin(intr.pi);
     V3 pt = offset_ray_origin(ls.pLight, ls.nLight, pf - ls.pLight.mid());
     V3 lo = pf, ld = pt - pf;
     Spec T_ray = sp(1.f), r_l = sp(1.f), r_u = sp(1.f);
@@ -752,14 +773,17 @@ VDEV int li_surface_pre(const DScene &S, PathState &st, IsgSample &isg, PC &pc, 
     Spec Le = !tri_hit && q.is_light ? light_L(q, si.n, -st.rd) : sp(0.f);  // :377 (triangles and spheres carry no area light)
     float w_direct = 0.f;
     if (nonzero(Le)) {
-        if (st.depth == 0 || st.specularBounce) {
+        // (the hint only orders the two blocks, the camera ray's first: with the MIS side first the pinned k_render_wave_wg3 holds
+        //  ten SGPRs in lanes over its loop, with the whole emitter branch out of line six where its carry twin holds eight --
+        //  tests/test_headline_kernel_resources.py, tests/test_wg3_carry_kernel.py; this order gives eight and eight)
+        if (__builtin_expect(st.depth == 0 || st.specularBounce, 1)) {
             st.L = st.L + wdiv(st.beta * Le, avg(st.r_u));
             w_direct = 1.0f;
         } else {
             const LsCtx pctx = st.prevCtx.template expand<FULL>(S);
             const float pmf = FULL && S.lsamp.mode != VSPG_LIGHTSAMPLER_UNIFORM ? light_sampler_pmf(S, pctx.pi.mid(), pctx.n, S.lsamp.light_of_quad[si.quad])
                                                                                  : wrcp((float)(FULL ? S.n_lights + S.n_inf : S.n_lights));
-            float lightPDF = pmf * light_pdf_li(q, pctx, st.rd);
+            float lightPDF = pmf * (FULL ? light_pdf_li(q, pctx, st.rd) : light_pdf_li_hit(q, pctx, st.rd, si.p));
             st.r_l = st.r_l * lightPDF;
             float w_l = S.prm.usenee ? wrcp(avg(st.r_u + st.r_l)) : 1.0f;
             st.L = st.L + st.beta * w_l * Le;
@@ -942,7 +966,8 @@ VDEV bool vertex_tail(const DScene &S, PathState &st, Sampler &sampler, const Ve
         if (a1 == 0 || !bsdf.has_lobes) return false;
         ang = cos_hemi_pre(u20, u21, &a0, &degenerate);  // a0 = r
     }
-    const float sinA = sinf_(ang), cosA = cosf_(ang);
+    float sinA, cosA;
+    sincosf_(ang, &sinA, &cosA);
 
     if (volume_vertex) {
         VSPG_PROF(PS_VOL_SAMPLE);
@@ -1149,7 +1174,8 @@ VDEV bool li_vertex_guided_impl(const DScene &S, const Medium &medium, PathState
             okf = !(a1 == 0 || !bsdf.has_lobes);
             ang = cos_hemi_pre(ua, ub, &a0, &degenerate);  // a0 = r
         }
-        const float sinA = sinf_(ang), cosA = cosf_(ang);
+        float sinA, cosA;
+        sincosf_(ang, &sinA, &cosA);
         if (volume_vertex) {
             w0 = hg_post(wo, vg, a0, a1, sinA, cosA, &sf0);
             ok0 = true;
