@@ -164,8 +164,12 @@ typedef struct VspgMedium {
  * HOST pointers, copied at create time. */
 /* Infinite lights (src/pbrt/lights.h:  UniformInfiniteLight :554-601, DistantLight :207-250; escaped-ray MIS
  * guidedvolpathvspgintegrator.cpp:353-374): L = scale * Lemit already multiplied out (RGB).  Distant: w_light = the
- * normalised direction TOWARDS the light in render space. */
-enum { VSPG_LIGHT_UNIFORM_INFINITE = 0, VSPG_LIGHT_DISTANT = 1 };
+ * normalised direction TOWARDS the light in render space.
+ * Image (ImageInfiniteLight, lights.h:607-697, lights.cpp:1072-1142): L = the RGB multiplier of the image's texels (the
+ * reference's `scale`, multiplied out); w_light is ignored.  The image itself is not part of the scene record: a renderer created
+ * with such a slot holds a 1 x 1 image of (1, 1, 1) under the identity transform (the uniform sky of colour L; lights.cpp:1683 "happily,
+ * this all just works") until vspg_renderer_set_environment_image replaces it. */
+enum { VSPG_LIGHT_UNIFORM_INFINITE = 0, VSPG_LIGHT_DISTANT = 1, VSPG_LIGHT_IMAGE_INFINITE = 2 };
 #define VSPG_MAX_INFINITE_LIGHTS 4
 typedef struct VspgInfiniteLight {
     int32_t type;
@@ -677,6 +681,35 @@ int vspg_libm_powf_batch(VspgRenderer *r, int n, const float *x, const float *y,
  * host's atanhf, bit for bit) and BlackbodySpectrum(T[i]).Sample(lambda) (:568-588) as the kernels evaluate a temperature grid's
  * emission (media.h:333-341, :724-735). */
 int vspg_blackbody_batch(VspgRenderer *r, int n, const float *u, const float *T, float *out6, void *stream);
+
+/* The image of an image infinite light (slot `infinite_light_index` of the scene's infinite lights, which must be of type
+ * VSPG_LIGHT_IMAGE_INFINITE): an equal-area octahedral map of the whole sphere (util/math.cpp:292-361), res x res texels.
+ *   host_rgb          res*res*3 floats (HOST array), top row first, R G B per texel, as pbrt's Image holds them
+ *   res               1 .. VSPG_ENV_MAX_RES (4096)
+ *   render_from_light rows 0..2 of the light's transform, 3 x 4 row-major (the translation column is read by nothing: the light
+ *                     transforms directions only); NULL = identity
+ * The host builds, in the reference's order of operations, the texel table, d = the average of R, G, B per texel
+ * (Image::GetSamplingDistribution, util/image.h:450-469), the COMPENSATED function max(d - average(d), 0) (all ones where that
+ * leaves nothing; lights.cpp:1104-1110) and its PiecewiseConstant2D (util/sampling.h:625-649, 737-754), uploads them and swaps them
+ * in behind `stream`.  Only the compensated distribution exists on the device: every call site of the integrator samples and
+ * evaluates lights with allowIncompletePDF = true (guidedvolpathvspgintegrator.cpp:365, 1166), so the plain distribution of
+ * lights.cpp:1100-1102 is never read.  The "power" light sampler's table is rebuilt with the light's Phi (lights.cpp:1125-1142).
+ * Like vspg_renderer_update_grid the call finishes parked samples and suspended paths on `stream` first, synchronises `stream`
+ * before it returns, and touches nothing else: film, VSP buffer, guiding fields and training state, counters and the error log
+ * persist.
+ * VSPG_EINVAL, with the renderer exactly as it was: a null renderer or image, an index that is no infinite light or one of another
+ * type, res < 1 or res > VSPG_ENV_MAX_RES, a texel that is NaN or infinite (lights.cpp:1694-1703), a singular or non-finite matrix. */
+#define VSPG_ENV_MAX_RES 4096
+int vspg_renderer_set_environment_image(VspgRenderer *r, int infinite_light_index, const float *host_rgb, int res,
+                                        const float *render_from_light /*12 or NULL*/, void *stream);
+/* Batch driver of the image infinite light (parity tests), as the path kernels evaluate it.  dirs: 3n floats, u: 2n floats, out:
+ * VSPG_ENVLIGHT_OUT floats per element (HOST arrays):
+ *   [0..2] Le(dirs[i])   [3..4] the (u, v) that Le looked up   [5] PDF_Li(dirs[i])
+ *   SampleLi(ctx.p = 0, u[i]):  [6] 1 = a sample, 0 = none (everything after it is 0 then)   [7..8] its (u, v)   [9..11] wi
+ *   [12] pdf   [13..15] L */
+#define VSPG_ENVLIGHT_OUT 16
+int vspg_envlight_batch(VspgRenderer *r, int infinite_light_index, int n, const float *dirs /*3n*/, const float *u /*2n*/,
+                        float *out /*16n*/, void *stream);
 
 #ifdef __cplusplus
 }

@@ -68,7 +68,9 @@ class VspgMedium(C.Structure):
 
 
 VSPG_MAX_INFINITE_LIGHTS = 4
-LIGHT_UNIFORM_INFINITE, LIGHT_DISTANT = 0, 1
+LIGHT_UNIFORM_INFINITE, LIGHT_DISTANT, LIGHT_IMAGE_INFINITE = 0, 1, 2
+ENV_MAX_RES = 4096   # VSPG_ENV_MAX_RES
+ENVLIGHT_OUT = 16    # VSPG_ENVLIGHT_OUT: floats per element of vspg_envlight_batch
 
 
 class VspgInfiniteLight(C.Structure):
@@ -289,6 +291,8 @@ SYMBOLS = [
     ("vspg_libm_log1m_batch", C.c_int, [_vp, C.c_int, _P(C.c_float), _P(C.c_float), _vp]),
     ("vspg_libm_powf_batch", C.c_int, [_vp, C.c_int, _P(C.c_float), _P(C.c_float), _P(C.c_float), _vp]),
     ("vspg_blackbody_batch", C.c_int, [_vp, C.c_int, _P(C.c_float), _P(C.c_float), _P(C.c_float), _vp]),
+    ("vspg_renderer_set_environment_image", C.c_int, [_vp, C.c_int, _P(C.c_float), C.c_int, _P(C.c_float), _vp]),
+    ("vspg_envlight_batch", C.c_int, [_vp, C.c_int, C.c_int, _P(C.c_float), _P(C.c_float), _P(C.c_float), _vp]),
     ("vspg_renderer_get_tr_buffer", C.c_int, [_vp, _P(C.c_float), _P(C.c_int32), _vp]),
     ("vspg_renderer_set_tr_buffer", C.c_int, [_vp, _P(C.c_float), _vp]),
     ("vspg_renderer_set_guiding_field", C.c_int, [_vp, _P(VspgField), _P(VspgField), _vp]),
@@ -490,7 +494,8 @@ def set_medium_transform(scene, m):
 
 
 def add_infinite_light(scene, kind, L, w_light=(0.0, 1.0, 0.0)):
-    """kind: LIGHT_UNIFORM_INFINITE (sky, radiance L) or LIGHT_DISTANT (sun, radiance L from direction w_light, normalised here)."""
+    """kind: LIGHT_UNIFORM_INFINITE (sky, radiance L), LIGHT_DISTANT (sun, radiance L from direction w_light, normalised here) or
+    LIGHT_IMAGE_INFINITE (environment map: L multiplies the texels; the image is given to the renderer, Renderer.set_environment_image)."""
     import numpy as np
     k = scene.n_infinite_lights
     assert k < VSPG_MAX_INFINITE_LIGHTS
@@ -526,6 +531,32 @@ def app_f_params():
     p.volumeguiding = 0
     p.vspsecondaryguiding = 0
     return p
+
+
+def environment_image_source(image, render_from_light=None):
+    """What vspg_renderer_set_environment_image is handed: (image array, res, matrix array or None).  The image is a float32 NumPy array
+    of shape [res, res, 3], C-contiguous, top row first, 1 <= res <= ENV_MAX_RES; the matrix, if any, 3 x 4 (or 12) numbers.  Anything
+    else raises ValueError -- here, before the library is called."""
+    import numpy as np
+    if not isinstance(image, np.ndarray):
+        raise ValueError("environment image must be a NumPy array, not %s" % type(image).__name__)
+    if image.dtype != np.float32:
+        raise ValueError("environment image must be float32, not %s" % image.dtype)
+    if image.ndim != 3 or image.shape[2] != 3:
+        raise ValueError("environment image must have shape [res, res, 3], not %s" % (tuple(image.shape),))
+    if image.shape[0] != image.shape[1]:
+        raise ValueError("environment image must be square (an equal-area map of the sphere), not %d x %d" % (image.shape[1], image.shape[0]))
+    if not 1 <= image.shape[0] <= ENV_MAX_RES:
+        raise ValueError("environment image resolution must be 1 .. %d, not %d" % (ENV_MAX_RES, image.shape[0]))
+    if not image.flags["C_CONTIGUOUS"]:
+        raise ValueError("environment image must be C-contiguous (top row first, R G B per texel)")
+    m = None
+    if render_from_light is not None:
+        m = np.ascontiguousarray(render_from_light, dtype=np.float32)
+        if m.size != 12:
+            raise ValueError("render_from_light must be a 3 x 4 matrix, not %s" % (tuple(m.shape),))
+        m = m.reshape(3, 4)
+    return image, int(image.shape[0]), m
 
 
 def grid_update_source(n_voxels, values, device):
@@ -740,6 +771,29 @@ class Renderer:
         fp = _P(C.c_float)
         _check(self.lib, self.lib.vspg_blackbody_batch(self.h, u.shape[0], u.ctypes.data_as(fp), T.ctypes.data_as(fp),
                                                       out.ctypes.data_as(fp), _vp(0)))
+        return out
+
+    def set_environment_image(self, index, image, render_from_light=None, stream=None):
+        """Give image infinite light `index` (of the scene's infinite lights) its image (vspg_renderer_set_environment_image): a
+        float32 NumPy array [res, res, 3], top row first, an equal-area octahedral map of the sphere; render_from_light: 3 x 4 or
+        None (identity).  Film, statistics, VSP buffer, guiding fields and counters stay."""
+        img, res, m = environment_image_source(image, render_from_light)
+        fp = _P(C.c_float)
+        _check(self.lib, self.lib.vspg_renderer_set_environment_image(self.h, int(index), img.ctypes.data_as(fp), res,
+                                                                     m.ctypes.data_as(fp) if m is not None else None, _vp(stream or 0)))
+
+    def envlight_batch(self, index, dirs, u):
+        """[n, 16] float32 per (direction, variate pair): Le (3), its uv (2), PDF_Li, then SampleLi(u): valid, uv (2), wi (3), pdf,
+        L (3) of image infinite light `index`, as the path kernels evaluate them (vspg_envlight_batch)."""
+        import numpy as np
+        d = np.ascontiguousarray(dirs, dtype=np.float32).reshape(-1, 3)
+        uu = np.ascontiguousarray(u, dtype=np.float32).reshape(-1, 2)
+        if d.shape[0] != uu.shape[0]:
+            raise ValueError("envlight_batch: %d directions but %d variate pairs" % (d.shape[0], uu.shape[0]))
+        out = np.empty((d.shape[0], ENVLIGHT_OUT), dtype=np.float32)
+        fp = _P(C.c_float)
+        _check(self.lib, self.lib.vspg_envlight_batch(self.h, int(index), d.shape[0], d.ctypes.data_as(fp), uu.ctypes.data_as(fp),
+                                                     out.ctypes.data_as(fp), _vp(0)))
         return out
 
     def counters(self, stream=None):

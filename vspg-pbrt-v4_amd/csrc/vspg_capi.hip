@@ -1534,6 +1534,27 @@ __global__ __launch_bounds__(kBlock) void k_blackbody(int n, const float *__rest
     for (int k = 0; k < 3; ++k) out[6 * i + k] = sample_visible_wavelength(u[i], k);
     out[6 * i + 3] = s.r; out[6 * i + 4] = s.g; out[6 * i + 5] = s.b;
 }
+// vspg_envlight_batch (include/vspg.h): Le, PDF_Li and SampleLi of image infinite light k as the path kernels evaluate them
+__global__ __launch_bounds__(kBlock) void k_envlight(const DScene *__restrict__ Sp, int k, int n, const float *__restrict__ dirs,
+                                                     const float *__restrict__ u, float *__restrict__ out) {
+    const int i = blockIdx.x * kBlock + threadIdx.x;
+    if (i >= n) return;
+    const DScene &S = *Sp;
+    float *o = out + (size_t)VSPG_ENVLIGHT_OUT * i;
+    const V3 d = ld3(dirs + 3 * (size_t)i);
+    float uv[2];
+    const Spec Le = env_Le(S, k, d, uv);
+    o[0] = Le.r; o[1] = Le.g; o[2] = Le.b;
+    o[3] = uv[0]; o[4] = uv[1];
+    o[5] = env_pdf_li(S, k, d);
+    LightLi ls{};
+    const bool ok = env_sample_li(S, k, mk(0, 0, 0), u[2 * (size_t)i], u[2 * (size_t)i + 1], &ls, uv);
+    o[6] = ok ? 1.f : 0.f;
+    o[7] = ok ? uv[0] : 0.f; o[8] = ok ? uv[1] : 0.f;
+    o[9] = ok ? ls.wi.x : 0.f; o[10] = ok ? ls.wi.y : 0.f; o[11] = ok ? ls.wi.z : 0.f;
+    o[12] = ok ? ls.pdf : 0.f;
+    o[13] = ok ? ls.L.r : 0.f; o[14] = ok ? ls.L.g : 0.f; o[15] = ok ? ls.L.b : 0.f;
+}
 __global__ __launch_bounds__(kBlock) void k_libm_log1m(int n, const float *__restrict__ x, float *__restrict__ out) {
     int i = blockIdx.x * kBlock + threadIdx.x;
     vspg_libm::stage_log_tab_lds();
@@ -1744,6 +1765,7 @@ struct VspgRenderer {
     float *le_scale = nullptr;  // emissive GridMedium: LeScale grid
     float *temperature = nullptr;  // temperature grid (raw samples)
     float *majorant = nullptr;  // 16^3 majorant grid
+    float *env_buf[VSPG_MAX_INFINITE_LIGHTS] = {nullptr, nullptr, nullptr, nullptr};  // image infinite lights: one allocation per light (DEnvLight's arrays)
     DTri *tris = nullptr;          // triangle soup in BVH leaf order + the BVH (depth-first, skip links)
     DBvh4Node *bvh = nullptr;
     // wavefront pipeline (vspg_wavefront.h): path SoA, lists and per-iteration control blocks, allocated at first use
@@ -2042,6 +2064,7 @@ static lightbounds_t quad_light_bounds(const DQuad &q, int reverse_orientation) 
     lb.twoSided = q.two_sided;
     return lb;
 }
+// (called again by vspg_renderer_set_environment_image: the power sampler's table depends on an image light's Phi)
 static void build(const VspgScene &sc, const VspgIntegratorParams &prm, DScene *D) {
     DLightSampler *ls = &D->lsamp;
     std::memset(ls, 0, sizeof *ls);
@@ -2074,7 +2097,8 @@ static void build(const VspgScene &sc, const VspgIntegratorParams &prm, DScene *
             pdf[i] = lambda < 360 || lambda > 830 ? 0.f : 0.0039398042f / sqr(coshf(0.0072f * (lambda - 538)));
         }
         for (int i = 0; i < n_all; ++i) {
-            float L[3], k;
+            float L[3], k, phi[3] = {0.f, 0.f, 0.f};
+            bool have_phi = false;
             if (i < D->n_lights) {
                 const DQuad &q = D->quads[D->light_quads[i]];
                 for (int c = 0; c < 3; ++c) L[c] = q.Le[c];
@@ -2083,9 +2107,15 @@ static void build(const VspgScene &sc, const VspgIntegratorParams &prm, DScene *
                 const int j = i - D->n_lights;
                 for (int c = 0; c < 3; ++c) L[c] = D->inf_L[j][c];
                 k = D->inf_type[j] == VSPG_LIGHT_DISTANT ? PI_F * sqr(D->scene_radius) : 4 * PI_F * PI_F * sqr(D->scene_radius);
+                if (D->inf_type[j] == VSPG_LIGHT_IMAGE_INFINITE) {
+                    // ImageInfiniteLight::Phi (lights.cpp:1141) in its order: 4 * Pi * Pi * Sqr(sceneRadius) * scale * sumL / (width * height)
+                    const DEnvLight &E = D->env[j];
+                    for (int c = 0; c < 3; ++c) phi[c] = k * L[c] * E.sum_L[c] / (float)(E.res * E.res);
+                    have_phi = true;
+                }
             }
             float s = 0.f;
-            for (int c = 0; c < 3; ++c) s += pdf[c] != 0 ? (k * L[c]) / pdf[c] : 0.f;
+            for (int c = 0; c < 3; ++c) s += pdf[c] != 0 ? (have_phi ? phi[c] : k * L[c]) / pdf[c] : 0.f;
             power[i] = s / 3;
             acc0 += power[i];
         }
@@ -2116,6 +2146,109 @@ static void build(const VspgScene &sc, const VspgIntegratorParams &prm, DScene *
 }  // namespace lsb
 
 static bool derive_triangle(const float *p9, const float *kd, int id, DTri *T, const int32_t *flags = nullptr);
+
+// ---- image infinite light: the host side of vspg_envlight.h ----------------------------------------------------------------
+// The arrays of one DEnvLight, laid out in one buffer: texels | func | cdf | mfunc | mcdf
+struct EnvTables {
+    int res = 0;
+    float integral = 0.f, sum_L[3] = {0.f, 0.f, 0.f};
+    std::vector<float> buf;
+    size_t o_func = 0, o_cdf = 0, o_mfunc = 0, o_mcdf = 0;
+};
+// PiecewiseConstant1D's constructor over [0, 1] (util/sampling.h:625-649): func (made absolute) and cdf[n + 1], sequential float sums
+static float env_build_1d(float *func, float *cdf, int n) {
+    for (int i = 0; i < n; ++i) func[i] = std::fabs(func[i]);
+    cdf[0] = 0;
+    for (int i = 1; i < n + 1; ++i) cdf[i] = cdf[i - 1] + func[i - 1] * (1.f - 0.f) / (float)n;
+    const float funcInt = cdf[n];
+    if (funcInt == 0)
+        for (int i = 1; i < n + 1; ++i) cdf[i] = (float)i / (float)n;
+    else
+        for (int i = 1; i < n + 1; ++i) cdf[i] /= funcInt;
+    return funcInt;
+}
+// What ImageInfiniteLight's constructor derives from the image (lights.cpp:1100-1110), compensated distribution only
+static void env_build_tables(const float *rgb, int res, EnvTables *T) {
+    const size_t n = (size_t)res * res;
+    T->res = res;
+    T->o_func = 3 * n;
+    T->o_cdf = T->o_func + n;
+    T->o_mfunc = T->o_cdf + (size_t)res * (res + 1);
+    T->o_mcdf = T->o_mfunc + res;
+    T->buf.assign(T->o_mcdf + res + 1, 0.f);
+    std::memcpy(T->buf.data(), rgb, 3 * n * sizeof(float));
+    float *d = T->buf.data() + T->o_func;
+    float sumL[3] = {0.f, 0.f, 0.f};  // Phi (lights.cpp:1127-1138): ClampZero(rgb) summed per channel, rows then columns
+    for (size_t i = 0; i < n; ++i) {
+        float sum = 0;  // ImageChannelValues::Average (util/image.h:205-210); dxdA = 1 (GetSamplingDistribution, image.h:338-339, 450-469)
+        for (int c = 0; c < 3; ++c) sum += rgb[3 * i + c];
+        d[i] = sum / 3;
+        for (int c = 0; c < 3; ++c) sumL[c] += rgb[3 * i + c] > 0.f ? rgb[3 * i + c] : 0.f;
+    }
+    for (int c = 0; c < 3; ++c) T->sum_L[c] = sumL[c];
+    double acc = 0.;  // std::accumulate(d.begin(), d.end(), 0.) / d.size() (lights.cpp:1105)
+    for (size_t i = 0; i < n; ++i) acc += d[i];
+    const float average = (float)(acc / (double)n);  // `Float average`: the double quotient rounded to float once
+    bool all_zero = true;
+    for (size_t i = 0; i < n; ++i) {
+        const float v = d[i] - average;                    // std::max<Float>(v - average, 0): a float subtraction
+        d[i] = v < 0.f ? 0.f : v;                          // (std::max(a, b) = a < b ? b : a; a NaN cannot occur: the texels are finite)
+        all_zero = all_zero && d[i] == 0;
+    }
+    if (all_zero) for (size_t i = 0; i < n; ++i) d[i] = 1.f;
+    // PiecewiseConstant2D (util/sampling.h:737-754): a 1-D distribution per row, then the marginal over the rows' integrals
+    float *cdf = T->buf.data() + T->o_cdf, *mfunc = T->buf.data() + T->o_mfunc, *mcdf = T->buf.data() + T->o_mcdf;
+    for (int v = 0; v < res; ++v) mfunc[v] = env_build_1d(d + (size_t)v * res, cdf + (size_t)v * (res + 1), res);
+    T->integral = env_build_1d(mfunc, mcdf, res);
+}
+// The linear part of render_from_light (3 x 4 row-major, NULL = identity) and its inverse: cofactors over the determinant in double,
+// each entry rounded to float once.  false: a non-finite entry or a singular matrix.
+static bool env_matrices(const float *m34, float *m, float *mi) {
+    static const float ident[12] = {1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1, 0};
+    const float *s = m34 ? m34 : ident;
+    double A[9];
+    for (int r = 0; r < 3; ++r)
+        for (int c = 0; c < 3; ++c) {
+            m[3 * r + c] = s[4 * r + c];
+            A[3 * r + c] = (double)s[4 * r + c];
+            if (!std::isfinite(s[4 * r + c])) return false;
+        }
+    const double a = A[0], b = A[1], c = A[2], d = A[3], e = A[4], f = A[5], g = A[6], h = A[7], i = A[8];
+    const double c00 = e * i - f * h, c01 = f * g - d * i, c02 = d * h - e * g;
+    const double det = (a * c00 + b * c01) + c * c02;
+    if (!(det != 0) || !std::isfinite(det)) return false;
+    const double adj[9] = {c00, c * h - b * i, b * f - c * e, c01, a * i - c * g, c * d - a * f, c02, b * g - a * h, a * e - b * d};
+    for (int k = 0; k < 9; ++k) {
+        mi[k] = (float)(adj[k] / det);
+        if (!std::isfinite(mi[k])) return false;
+    }
+    return true;
+}
+// Upload one light's tables into a fresh allocation and point the HOST scene record's slot at it.  The caller copies the record to
+// the device and frees *old_buf once no launch can read it.
+static int env_install(VspgRenderer *r, int k, const EnvTables &T, const float *m, const float *mi, hipStream_t s, float **old_buf) {
+    float *buf = nullptr;
+    HIPCHK(hipMalloc(&buf, T.buf.size() * sizeof(float)));
+    hipError_t e = hipMemcpyAsync(buf, T.buf.data(), T.buf.size() * sizeof(float), hipMemcpyHostToDevice, s);
+    if (e == hipSuccess) e = hipStreamSynchronize(s);  // (the host vector is pageable and the caller's to drop)
+    if (e != hipSuccess) {
+        (void)hipFree(buf);
+        return fail(VSPG_EHIP, std::string("uploading the environment image: ") + hipGetErrorName(e));
+    }
+    DEnvLight &E = r->hscene.env[k];
+    E.res = T.res;
+    E.integral = T.integral;
+    for (int j = 0; j < 9; ++j) { E.m[j] = m[j]; E.mi[j] = mi[j]; }
+    for (int c = 0; c < 3; ++c) E.sum_L[c] = T.sum_L[c];
+    E.texels = buf;
+    E.func = buf + T.o_func;
+    E.cdf = buf + T.o_cdf;
+    E.mfunc = buf + T.o_mfunc;
+    E.mcdf = buf + T.o_mcdf;
+    *old_buf = r->env_buf[k];
+    r->env_buf[k] = buf;
+    return 0;
+}
 // SURF_* flags from the C-ABI's material / medium_interface pair: a MediumInterface only counts when it is a TRANSITION
 // (inside != outside, base/medium.h:124)
 static int32_t surf_flags_of(int material, int medium_interface) {
@@ -2166,6 +2299,11 @@ static void build_dscene(const VspgScene &sc, const VspgIntegratorParams &prm, c
     for (int i = 0; i < sc.n_infinite_lights && i < VSPG_MAX_INFINITE_LIGHTS; ++i) {
         D->inf_type[i] = sc.infinite_lights[i].type;
         for (int k = 0; k < 3; ++k) { D->inf_L[i][k] = sc.infinite_lights[i].L[k]; D->inf_w[i][k] = sc.infinite_lights[i].w_light[k]; }
+        if (D->inf_type[i] == VSPG_LIGHT_IMAGE_INFINITE) {  // the 1 x 1 white image under the identity; vspg_renderer_create uploads its tables
+            DEnvLight &E = D->env[i];
+            E.res = 1;
+            for (int k = 0; k < 3; ++k) { E.m[4 * k] = E.mi[4 * k] = 1.f; E.sum_L[k] = 1.f; }
+        }
     }
     {   // scene bounds = union of the primitives' bounds; light.Preprocess: BoundingSphere (integrators.h:74-81, vecmath.h:1335-1338)
         float lo[3] = {kInf, kInf, kInf}, hi[3] = {-kInf, -kInf, -kInf};
@@ -2591,7 +2729,8 @@ static int validate(const VspgScene *scene, const VspgIntegratorParams *p, const
     if (scene->n_triangles > 0 && !scene->tri_p) return fail(VSPG_EINVAL, "triangles without vertex data");
     if (scene->n_infinite_lights < 0 || scene->n_infinite_lights > VSPG_MAX_INFINITE_LIGHTS) return fail(VSPG_EINVAL, "n_infinite_lights out of range");
     for (int i = 0; i < scene->n_infinite_lights; ++i)
-        if (scene->infinite_lights[i].type != VSPG_LIGHT_UNIFORM_INFINITE && scene->infinite_lights[i].type != VSPG_LIGHT_DISTANT)
+        if (scene->infinite_lights[i].type != VSPG_LIGHT_UNIFORM_INFINITE && scene->infinite_lights[i].type != VSPG_LIGHT_DISTANT &&
+            scene->infinite_lights[i].type != VSPG_LIGHT_IMAGE_INFINITE)
             return fail(VSPG_EINVAL, "unknown infinite light type");
     int nl = scene->n_infinite_lights;
     for (int i = 0; i < scene->n_quads; ++i)
@@ -3038,6 +3177,15 @@ int vspg_renderer_create(const VspgScene *scene, const VspgIntegratorParams *par
         r->scene.tri_kd = nullptr;
         r->scene.tri_flags = nullptr;
     }
+    for (int k = 0; k < r->hscene.n_inf; ++k)
+        if (r->hscene.inf_type[k] == VSPG_LIGHT_IMAGE_INFINITE) {  // the 1 x 1 white image (include/vspg.h): the light is valid from creation on
+            const float white[3] = {1.f, 1.f, 1.f};
+            EnvTables T;
+            env_build_tables(white, 1, &T);
+            float m[9], mi[9], *old = nullptr;
+            env_matrices(nullptr, m, mi);
+            if (const int erc = env_install(r, k, T, m, mi, nullptr, &old)) { vspg_renderer_destroy(r); return erc; }
+        }
     CK(hipMalloc(&r->dscene, sizeof(DScene)));
     CK(hipMemcpy(r->dscene, &r->hscene, sizeof(DScene), hipMemcpyHostToDevice));
     CK(hipMalloc(&r->film, r->npix * sizeof(float4)));
@@ -3174,6 +3322,7 @@ int vspg_renderer_destroy(VspgRenderer *r) {
     if (r->le_scale) (void)hipFree(r->le_scale);
     if (r->temperature) (void)hipFree(r->temperature);
     if (r->majorant) (void)hipFree(r->majorant);
+    for (int k = 0; k < VSPG_MAX_INFINITE_LIGHTS; ++k) if (r->env_buf[k]) (void)hipFree(r->env_buf[k]);
     if (r->fe_ref) (void)hipFree(r->fe_ref);
     if (r->fe_partials) (void)hipFree(r->fe_partials);
     if (r->fe_log) (void)hipFree(r->fe_log);
@@ -4313,6 +4462,62 @@ int vspg_blackbody_batch(VspgRenderer *r, int n, const float *u, const float *T,
     hipLaunchKernelGGL(k_blackbody, dim3((n + kBlock - 1) / kBlock), dim3(kBlock), 0, s, n, (const float *)du.p, (const float *)dT.p, (float *)dout.p);
     HIPCHK(hipGetLastError());
     HIPCHK(hipMemcpyAsync(out6, dout.p, (size_t)n * 24, hipMemcpyDeviceToHost, s));
+    HIPCHK(hipStreamSynchronize(s));
+    return 0;
+}
+
+int vspg_renderer_set_environment_image(VspgRenderer *r, int infinite_light_index, const float *host_rgb, int res,
+                                        const float *render_from_light, void *stream) {
+    // every refusal comes before anything of the renderer changes -- parked samples included
+    if (!r || !host_rgb) return fail(VSPG_EINVAL, "null argument");
+    const int k = infinite_light_index;
+    if (k < 0 || k >= r->hscene.n_inf) return fail(VSPG_EINVAL, "infinite_light_index names no infinite light of the scene");
+    if (r->hscene.inf_type[k] != VSPG_LIGHT_IMAGE_INFINITE) return fail(VSPG_EINVAL, "the infinite light is not of type VSPG_LIGHT_IMAGE_INFINITE");
+    if (res < 1 || res > VSPG_ENV_MAX_RES) return fail(VSPG_EINVAL, "environment image resolution outside 1 .. VSPG_ENV_MAX_RES (4096)");
+    const size_t n3 = (size_t)res * res * 3;
+    for (size_t i = 0; i < n3; ++i) {
+        if (host_rgb[i] != host_rgb[i]) return fail(VSPG_EINVAL, "environment image has not-a-number pixel values and so is not suitable as a light");
+        if (std::isinf(host_rgb[i])) return fail(VSPG_EINVAL, "environment image has infinite pixel values and so is not suitable as a light");
+    }
+    float m[9], mi[9];
+    if (!env_matrices(render_from_light, m, mi)) return fail(VSPG_EINVAL, "render_from_light is singular or not finite");
+    EnvTables T;
+    env_build_tables(host_rgb, res, &T);
+    HIPCHK(hipSetDevice(r->cfg.device));
+    hipStream_t s = (hipStream_t)stream;
+    if (const int rc = flush_parked_samples(r, s)) return rc;  // (paths in flight end under the sky they started under)
+    HIPCHK(hipStreamSynchronize(s));  // no launch may still read the old tables
+    float *old = nullptr;
+    if (const int rc = env_install(r, k, T, m, mi, s, &old)) return rc;
+    lsb::build(r->scene, r->prm, &r->hscene);  // the power sampler's alias table: the light's Phi changed
+    // the light sampler and the environment slots are the tail of the record; the rest of the device's copy (the guiding fields a
+    // training renderer updates in place) is not touched
+    const size_t tail = offsetof(DScene, lsamp);
+    HIPCHK(hipMemcpyAsync(reinterpret_cast<char *>(r->dscene) + tail, reinterpret_cast<const char *>(&r->hscene) + tail, sizeof(DScene) - tail,
+                          hipMemcpyHostToDevice, s));
+    HIPCHK(hipStreamSynchronize(s));
+    if (old) (void)hipFree(old);
+    return 0;
+}
+
+int vspg_envlight_batch(VspgRenderer *r, int infinite_light_index, int n, const float *dirs, const float *u, float *out, void *stream) {
+    if (!r || n < 0 || (n > 0 && (!dirs || !u || !out))) return fail(VSPG_EINVAL, "null argument");
+    const int k = infinite_light_index;
+    if (k < 0 || k >= r->hscene.n_inf || r->hscene.inf_type[k] != VSPG_LIGHT_IMAGE_INFINITE)
+        return fail(VSPG_EINVAL, "infinite_light_index names no image infinite light of the scene");
+    if (n == 0) return 0;
+    HIPCHK(hipSetDevice(r->cfg.device));
+    hipStream_t s = (hipStream_t)stream;
+    DevBuf dd, du, dout;
+    HIPCHK(hipMalloc(&dd.p, (size_t)n * 12));
+    HIPCHK(hipMalloc(&du.p, (size_t)n * 8));
+    HIPCHK(hipMalloc(&dout.p, (size_t)n * VSPG_ENVLIGHT_OUT * 4));
+    HIPCHK(hipMemcpyAsync(dd.p, dirs, (size_t)n * 12, hipMemcpyHostToDevice, s));
+    HIPCHK(hipMemcpyAsync(du.p, u, (size_t)n * 8, hipMemcpyHostToDevice, s));
+    hipLaunchKernelGGL(k_envlight, dim3((n + kBlock - 1) / kBlock), dim3(kBlock), 0, s, r->dscene, k, n, (const float *)dd.p, (const float *)du.p,
+                       (float *)dout.p);
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipMemcpyAsync(out, dout.p, (size_t)n * VSPG_ENVLIGHT_OUT * 4, hipMemcpyDeviceToHost, s));
     HIPCHK(hipStreamSynchronize(s));
     return 0;
 }

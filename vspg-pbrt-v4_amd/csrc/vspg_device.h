@@ -695,6 +695,20 @@ __host__ __device__ __forceinline__ int win_tile_y0(const PixelWindow &w) { retu
 __host__ __device__ __forceinline__ int win_tiles_x(const PixelWindow &w) { return ((w.x1 + 7) >> 3) - (w.x0 >> 3); }
 __host__ __device__ __forceinline__ int win_tiles_y(const PixelWindow &w) { return ((w.y1 + 7) >> 3) - (w.y0 >> 3); }
 __host__ __device__ __forceinline__ bool win_has(const PixelWindow &w, int px, int py) { return px >= w.x0 && px < w.x1 && py >= w.y0 && py < w.y1; }
+// Image infinite light (vspg_envlight.h; built by vspg_renderer_set_environment_image): the texels, and the light's compensated
+// PiecewiseConstant2D (util/sampling.h:697-779) as flat arrays in HBM -- per row the function and its CDF, the rows' integrals (the
+// marginal's function) and the marginal's CDF.  m / mi: the linear part of renderFromLight and of its inverse, row-major.
+struct DEnvLight {
+    int32_t res;
+    float integral;        // the marginal's funcInt = PiecewiseConstant2D::Integral()
+    float m[9], mi[9];
+    float sum_L[3];        // host only: the clamped texels summed per channel in image order (the "power" light sampler's Phi)
+    const float *texels;   // res * res * 3, top row first
+    const float *func;     // res rows of res
+    const float *cdf;      // res rows of res + 1
+    const float *mfunc;    // res
+    const float *mcdf;     // res + 1
+};
 struct DScene {
     int32_t n_quads, n_lights;
     int32_t n_tris, n_bvh_nodes;
@@ -772,6 +786,9 @@ struct DScene {
     int32_t contrib_ready;
     // LightSampler::Create(prm.lightsampler, lights): lsamp.mode is UNIFORM wherever the pick is trivial
     DLightSampler lsamp;
+    // image infinite lights: slot k describes infinite light k where inf_type[k] == VSPG_LIGHT_IMAGE_INFINITE.  Behind everything
+    // else: no offset of the record the existing kernels read moves.
+    DEnvLight env[VSPG_MAX_INFINITE_LIGHTS];
 };
 // DScene::has_boundaries as the path code reads it.  (-DVSPG_NO_BOUNDARIES: a diagnostic build without the boundary code, to price
 // its presence in the kernels that serve scenes without boundaries -- same results on those scenes.)

@@ -86,6 +86,7 @@ struct LightLi {
     P3i pLight;
     V3 nLight;
 };
+#include "vspg_envlight.h"  // the image infinite light: env_Le / env_sample_li / env_pdf_li (fills a LightLi)
 VDEV bool light_sample_li(const DQuad &q, V3 ctxp, float u0, float u1, LightLi *ls) {
     V3 p00 = ld3(q.p00), p10 = ld3(q.p10), p01 = ld3(q.p01), p11 = ld3(q.p11);
     V3 pu0 = lerp(u1, p00, p01), pu1 = lerp(u1, p10, p11);
@@ -121,6 +122,10 @@ VDEV bool sample_light(const DScene &S, int lightIndex, V3 ctxp, float u0, float
     *delta_light = false;
     if (!FULL || lightIndex < S.n_lights) return light_sample_li(light_quad_at(lightIndex), ctxp, u0, u1, ls);
     const int k = lightIndex - S.n_lights;
+    if (S.inf_type[k] == VSPG_LIGHT_IMAGE_INFINITE) {  // ImageInfiniteLight::SampleLi (lights.h:650-674); `!ls->L || ls->pdf == 0` of :1167
+        if (!env_sample_li(S, k, ctxp, u0, u1, ls)) return false;
+        return nonzero(ls->L) && ls->pdf != 0;
+    }
     // UniformInfiniteLight::SampleLi returns {} for the incomplete PDF (lights.cpp:1019-1023): the sky is reached by escaping rays only
     if (S.inf_type[k] != VSPG_LIGHT_DISTANT) return false;
     // DistantLight::SampleLi (lights.h:320-327)
@@ -750,16 +755,19 @@ VDEV int li_surface_pre(const DScene &S, PathState &st, IsgSample &isg, PC &pc, 
     if (!si.hit) {  // :353-374: infinite light sources (this fork lists DeltaDirection lights among them, integrators.h:79)
         const int n_all = S.n_lights + S.n_inf;
         for (int k = 0; FULL && k < S.n_inf; ++k) {
-            Spec Le = lds(S.inf_L[k]);  // UniformInfiniteLight::Le / DistantLight::Le (lights.cpp:1014-1017, lights.h:291-293)
+            const bool image = S.inf_type[k] == VSPG_LIGHT_IMAGE_INFINITE;
+            // UniformInfiniteLight::Le / DistantLight::Le (lights.cpp:1014-1017, lights.h:291-293) / ImageInfiniteLight::Le (lights.h:643-647)
+            Spec Le = image ? env_Le(S, k, st.rd) : lds(S.inf_L[k]);
             if (S.inf_type[k] == VSPG_LIGHT_DISTANT && st.depth != 0) Le = sp(0.f);
             if (st.depth == 0 || st.specularBounce) {
                 st.L = st.L + wdiv(st.beta * Le, avg(st.r_u));
                 if constexpr (kRec) pc.rec.add_infinite_light_emission(st.ro + st.rd * kGuidingInfiniteLightDistance, Le, 1.0f);  // :361
             } else {
-                // lightSampler.PMF * light.PDF_Li(prevIntrContext, ray.d, true): both light types return 0 for the incomplete PDF
+                // lightSampler.PMF * light.PDF_Li(prevIntrContext, ray.d, true): the uniform and the distant light return 0 for the
+                // incomplete PDF, the image light its compensated distribution's (lights.cpp:1113-1123)
                 const float pmf = S.lsamp.mode != VSPG_LIGHTSAMPLER_UNIFORM ? light_sampler_pmf(S, st.prevCtx.template expand<FULL>(S).pi.mid(), st.prevCtx.template expand<FULL>(S).n, S.n_lights + k)
                                                                             : wrcp((float)n_all);
-                const float lightPDF = pmf * 0.f;
+                const float lightPDF = pmf * (image ? env_pdf_li(S, k, st.rd) : 0.f);
                 st.r_l = st.r_l * lightPDF;
                 const float w_b = S.prm.usenee ? wrcp(avg(st.r_u + st.r_l)) : 1.f;
                 st.L = st.L + st.beta * w_b * Le;

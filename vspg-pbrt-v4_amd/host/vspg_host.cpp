@@ -667,6 +667,10 @@ void GuidedVolPathVSPGIntegrator::SetMseReference(const std::vector<float> &fram
     if (vspg_renderer_set_reference_image(renderer, frameImage.data(), nullptr) != 0) throw Error(vspg_last_error());
     mseOut = out;
 }
+void GuidedVolPathVSPGIntegrator::SetEnvironmentImage(int light, const std::vector<float> &rgb, int res, const float *renderFromLight) {
+    if (res < 1 || rgb.size() != (size_t)res * res * 3) throw Error("the environment image does not hold res * res * 3 values");
+    if (vspg_renderer_set_environment_image(renderer, light, rgb.data(), res, renderFromLight, nullptr) != 0) throw Error(vspg_last_error());
+}
 void GuidedVolPathVSPGIntegrator::SetMediumDensity(const std::vector<float> &values) {
     if (vspg_renderer_update_grid(renderer, VSPG_GRID_DENSITY, values.data(), values.size(), VSPG_MEM_HOST, nullptr) != 0) throw Error(vspg_last_error());
 }

@@ -168,6 +168,9 @@ class Integrator {
     // the film's pixelBounds [x0, x1) x [y0, y1), inside the frame and not empty (film.cpp:97-172; the scene-file reader resolves
     // "cropwindow" / "pixelbounds"): Render() covers these pixels only (integrators.cpp:183).  Default: the whole frame.
     virtual void SetPixelBounds(int x0, int y0, int x1, int y1) = 0;
+    // The image of image infinite light `light` (an index into the scene's infinite lights): res * res * 3 floats, top row first, and
+    // the rows of renderFromLight (12 floats) or nullptr for the identity (vspg_renderer_set_environment_image).  Throws on refusal.
+    virtual void SetEnvironmentImage(int light, const std::vector<float> &rgb, int res, const float *renderFromLight) = 0;
     // Integrator::Create: "guidedvolpathvspg"; "guidedvolpath" is accepted as an alias ONLY when
     // the dictionary carries "vspguiding" (the option BASELINE.json names), see SURVEY.md 0.1
     static std::unique_ptr<Integrator> Create(const std::string &name, const ParameterDictionary &parameters,
@@ -189,6 +192,7 @@ class GuidedVolPathVSPGIntegrator : public Integrator {
     std::string ToString() const override;
     Film GetFilm();               // the pixels of the pixel bounds (RGBFilm::WriteImage, film.cpp:541-557)
     void SetPixelBounds(int x0, int y0, int x1, int y1) override;
+    void SetEnvironmentImage(int light, const std::vector<float> &rgb, int res, const float *renderFromLight) override;
     VspgCounters Counters();
     VspgTrainStats TrainingStats();      // guideTraining / guiding_field->GetIteration()
     GuidingCache GetGuidingCache();      // the field as it stands (trained in-loop or loaded)

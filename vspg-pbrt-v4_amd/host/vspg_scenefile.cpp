@@ -1,5 +1,6 @@
 // vspg_scenefile.cpp -- see vspg_scenefile.h
 #include "vspg_scenefile.h"
+#include "vspg_image.h"
 
 #include <algorithm>
 #include <cmath>
@@ -343,9 +344,39 @@ class Parser {
         p.GetOneRGB("L", L);
         const float sc = p.GetOneFloat("scale", 1.f);
         if (type == "infinite") {
-            if (!p.GetOneString("filename", "").empty()) fail("image infinite lights are outside this build's scope");
-            il.type = VSPG_LIGHT_UNIFORM_INFINITE;
+            // Light::Create, "infinite" (lights.cpp:1618-1750).  `scale /= SpectrumToPhotometric(illuminant)` is the same step in the
+            // uniform and in the image branch (:1629, :1652, :1717), and under PBRT_RGB_RENDERING SpectrumToPhotometric is `return 1.f`
+            // (util/spectrum.cpp:48-49): the uniform branch below takes L * scale as it stands, and so does the image branch.
+            std::string fn = p.GetOneString("filename", "");
+            if (!p.GetPoint3Array("portal").empty()) fail("LightSource \"infinite\": \"portal\" (PortalImageInfiniteLight) is outside this build's scope");
+            if (p.Has("illuminance")) fail("LightSource \"infinite\": \"illuminance\" is outside this build's scope (give \"scale\")");
             il.w_light[0] = 0; il.w_light[1] = 1; il.w_light[2] = 0;
+            if (fn.empty()) {
+                il.type = VSPG_LIGHT_UNIFORM_INFINITE;
+            } else {
+                if (p.Has("L")) fail("Can't specify both emission \"L\" and \"filename\" with ImageInfiniteLight");  // lights.cpp:1647
+                if (fn[0] != '/' && !baseDir.empty()) fn = baseDir + "/" + fn;  // ResolveFilename
+                const Image img = ReadImage(fn);
+                for (const char *c : {"R", "G", "B"})
+                    if (img.ChannelIndex(c) < 0) fail(fn + ": image provided to \"infinite\" light must have R, G, and B channels.");  // :1710-1714
+                if (img.xres != img.yres)  // lights.cpp:1096-1099
+                    fail(fn + ": image resolution (" + std::to_string(img.xres) + ", " + std::to_string(img.yres) +
+                         ") is non-square. It's unlikely this is an equal area environment map.");
+                if (img.xres > VSPG_ENV_MAX_RES) fail(fn + ": environment maps above " + std::to_string(VSPG_ENV_MAX_RES) + " texels a side are outside this build's scope");
+                SceneDescription::EnvImage e;
+                e.light = sd->scene.n_infinite_lights;
+                e.res = img.xres;
+                e.rgb = img.Gather({"R", "G", "B"}, fn);
+                for (float v : e.rgb) {  // lights.cpp:1694-1703
+                    if (std::isinf(v)) fail(fn + ": image has infinite pixel values and so is not suitable as a light.");
+                    if (v != v) fail(fn + ": image has not-a-number pixel values and so is not suitable as a light.");
+                }
+                for (int i = 0; i < 3; ++i)
+                    for (int j = 0; j < 4; ++j) e.renderFromLight[4 * i + j] = gs.ctm.m[i][j];
+                sd->envImages.push_back(std::move(e));
+                il.type = VSPG_LIGHT_IMAGE_INFINITE;
+                L[0] = L[1] = L[2] = 1.f;  // the multiplier is `scale` alone
+            }
         } else if (type == "distant") {
             float from[3] = {0, 0, 0}, to[3] = {0, 0, 1};
             p.GetOnePoint3("from", from);
@@ -543,6 +574,7 @@ std::unique_ptr<Integrator> CreateIntegrator(const SceneDescription &sd, int dev
     }
     auto integrator = Integrator::Create(sd.integratorName, sd.integratorParams, sd.scene, sd.xres, sd.yres, sd.pixelSamples, sd.seed, device);
     integrator->SetPixelBounds(b[0], b[1], b[2], b[3]);
+    for (const SceneDescription::EnvImage &e : sd.envImages) integrator->SetEnvironmentImage(e.light, e.rgb, e.res, e.renderFromLight);
     return integrator;
 }
 

@@ -11,7 +11,8 @@
 // (xresolution, yresolution, filename, savefp16, cropwindow, pixelbounds), Integrator, Option (ignored), ColorSpace (ignored), WorldBegin, AttributeBegin/End,
 // Identity, Translate, Scale, Rotate, Transform, ConcatTransform, ReverseOrientation, Material "diffuse" (reflectance) / "interface",
 // MakeNamedMaterial / NamedMaterial ("diffuse", "interface"), AreaLightSource "diffuse" (L, scale, twosided), LightSource "infinite"
-// (L, scale; no image) / "distant" (L, scale, from, to), MakeNamedMedium ("homogeneous", "uniformgrid"), MediumInterface,
+// (L, scale; or "filename": an equal-area octahedral environment map, .exr / .pfm, square, with R, G, B -- the CTM in effect is the
+// light's transform; no "portal", no "illuminance") / "distant" (L, scale, from, to), MakeNamedMedium ("homogeneous", "uniformgrid"), MediumInterface,
 // Include (as a directive, and -- beyond pbrt -- inside a parameter list, for the block the reference's nanovdb2pbrt prints),
 // Shape "bilinearmesh" (one patch: a parallelogram becomes a rectangle, anything else two triangles) / "trianglemesh"
 // (P, indices) / "sphere" (radius; full spheres).  Anything else is an Error naming the directive: nothing is silently dropped.
@@ -35,6 +36,15 @@ struct SceneDescription {
     VspgScene scene;                     // pointers inside refer to the vectors below: keep the description alive while creating
     std::vector<float> density, leScale, temperature, triP, triKd;
     std::vector<int32_t> triFlags;       // VSPG_TRI_* per triangle (material, MediumInterface, orientation)
+    // LightSource "infinite" "string filename": the image of infinite light `light` (R, G, B interleaved, top row first) and the
+    // rows of its renderFromLight (the CTM at the directive).  CreateIntegrator hands them to the renderer it creates
+    // (Integrator::SetEnvironmentImage -> vspg_renderer_set_environment_image); a host that creates the renderer itself does the same.
+    struct EnvImage {
+        int light = 0, res = 0;
+        std::vector<float> rgb;
+        float renderFromLight[12] = {1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1, 0};
+    };
+    std::vector<EnvImage> envImages;
     std::string integratorName = "volpath";
     ParameterDictionary integratorParams;
     int xres = 1280, yres = 720;         // Film defaults (film.cpp)
