@@ -888,8 +888,18 @@ VDEV void rect_frame(V3 &o, V3 &d, int steps) {
     }
 }
 // o, d: the ray in the frame of the record's axis (rect_frame).  A kIsectUvSwapped record reports (v, u).
+// One lane mask and one wave vote per record: the sign and range pre-tests make `cand`, the wavefront goes to the next record when no
+// lane is a candidate, and past the vote the body is straight-line -- every lane divides and forms (u, v), the exact tests only
+// narrow `cand`, and the callers keep the winner with selects.  An accepted lane runs the operations it always ran on the same
+// operands; a rejected lane computes values nobody reads (*tHit, *uHit, *vHit mean something only where true is returned).  Four
+// nested early returns per record cost a saved exec mask, a branch and a mask merge each, and on an incoherent wavefront the inner
+// three skipped nothing: some lane always passed.  `cand` implies `some`, so what a lane returns does not depend on the
+// other lanes.  The host has no wavefront: its vote is the lane itself, or, with VSPG_RECT_VOTE_TAKEN, always taken, which is what a
+// lane sees whose neighbour is a candidate.  VSPG_RECT_VOTE_TAKEN is for tests/test_rect_vote_bits.py alone, which builds both;
+// nothing else may define it, and no device build reads it.
 VDEV bool rect_hit_uv(const IsectRec &r, V3 o, V3 d, float tMax, float *tHit, float *uHit, float *vHit) {
     float num, denom, u, v, t;
+    bool cand;
     if (r.axes & kIsectAxisAligned) {
         // axis-aligned rectangle: n.d == nsign*d[a] and n.(p00-o) == nsign*(p00[a]-o[a]) exactly (the other
         // products are +-0), so t == (p00[a]-o[a])/d[a] exactly -- nsign = +-1 negates both, which no IEEE quotient
@@ -898,10 +908,18 @@ VDEV bool rect_hit_uv(const IsectRec &r, V3 o, V3 d, float tMax, float *tHit, fl
         num = r.f[1] - o.x;
         // the sign pre-test on the bit patterns: zeros, infinities and NaNs of equal sign go on to the division
         // and are rejected by the exact tests on t
-        if ((int32_t)(__builtin_bit_cast(uint32_t, num) ^ __builtin_bit_cast(uint32_t, denom)) < 0) return false;
-        if (beyond(num, denom, tMax)) return false;
+        cand = (int32_t)(__builtin_bit_cast(uint32_t, num) ^ __builtin_bit_cast(uint32_t, denom)) >= 0;
+        cand = cand & !beyond(num, denom, tMax);
+#if defined(__HIP_DEVICE_COMPILE__)
+        const bool some = __ballot(cand) != 0ull;
+#elif defined(VSPG_RECT_VOTE_TAKEN)
+        const bool some = true;
+#else
+        const bool some = cand;
+#endif
+        if (!some) return false;   // wave-uniform
         t = num / denom;
-        if (!(t > 0) || !(t < tMax)) return false;
+        cand = cand & (t > 0) & (t < tMax);
         float pu = o.y + d.y * t, pv = o.z + d.z * t;
         u = ((pu - r.f[2]) * r.f[4]) * r.f[6];
         v = ((pv - r.f[3]) * r.f[5]) * r.f[7];
@@ -909,21 +927,28 @@ VDEV bool rect_hit_uv(const IsectRec &r, V3 o, V3 d, float tMax, float *tHit, fl
         V3 n = V3{r.f[0], r.f[1], r.f[2]}, p00 = V3{r.f[3], r.f[4], r.f[5]};
         denom = dot(n, d);
         num = dot(n, p00 - o);
-        bool cand = (num > 0 && denom > 0) || (num < 0 && denom < 0);
-        if (!cand) return false;
-        if (beyond(num, denom, tMax)) return false;
+        cand = ((num > 0) & (denom > 0)) | ((num < 0) & (denom < 0));
+        cand = cand & !beyond(num, denom, tMax);
+#if defined(__HIP_DEVICE_COMPILE__)
+        const bool some = __ballot(cand) != 0ull;
+#elif defined(VSPG_RECT_VOTE_TAKEN)
+        const bool some = true;
+#else
+        const bool some = cand;
+#endif
+        if (!some) return false;   // wave-uniform
         t = num / denom;
-        if (!(t > 0) || !(t < tMax)) return false;
+        cand = cand & (t > 0) & (t < tMax);
         V3 p = o + d * t;
         V3 rel = p - p00;
         u = dot(rel, V3{r.f[6], r.f[7], r.f[8]}) * r.f[12];
         v = dot(rel, V3{r.f[9], r.f[10], r.f[11]}) * r.f[13];
     }
-    if (u < 0 || u > 1 || v < 0 || v > 1) return false;
+    cand = cand & !((u < 0) | (u > 1) | (v < 0) | (v > 1));   // a NaN u or v passes, as it always did
     *tHit = t;
     *uHit = u;
     *vHit = v;
-    return true;
+    return cand;
 }
 // The closest rectangle of `n` records in index order -- the first one keeps winning equal distances -- with the winner's (u, v) in
 // the rectangle's own e1 / e2 order.  *tBest = tMax, *iBest = 0 and (u, v) = (0, 0) where nothing is hit.
@@ -936,14 +961,13 @@ VDEV bool rects_closest(const IsectRec *recs, int n, V3 o, V3 d, float tMax, flo
         const IsectRec &r = recs[i];
         float t, u, v;
         rect_frame(fo, fd, r.axes);
-        if (rect_hit_uv(r, fo, fd, bt, &t, &u, &v)) {
-            const bool swapped = (r.axes & kIsectUvSwapped) != 0;   // wave-uniform
-            hit = true;
-            bt = t;
-            bi = i;
-            bu = swapped ? v : u;
-            bv = swapped ? u : v;
-        }
+        const bool h = rect_hit_uv(r, fo, fd, bt, &t, &u, &v);
+        const bool swapped = (r.axes & kIsectUvSwapped) != 0;   // wave-uniform
+        hit = hit | h;
+        bt = h ? t : bt;
+        bi = h ? i : bi;
+        bu = h ? (swapped ? v : u) : bu;
+        bv = h ? (swapped ? u : v) : bv;
     }
     *tBest = bt;
     *iBest = bi;
@@ -958,7 +982,7 @@ VDEV bool rects_any(const IsectRec *recs, int n, V3 o, V3 d, float tMax) {
         const IsectRec &r = recs[i];
         float t, u, v;   // (u, v) of a swapped record trade places: the [0,1]^2 test does not care
         rect_frame(fo, fd, r.axes);
-        any = any || rect_hit_uv(r, fo, fd, tMax, &t, &u, &v);
+        any = any | rect_hit_uv(r, fo, fd, tMax, &t, &u, &v);
     }
     return any;
 }

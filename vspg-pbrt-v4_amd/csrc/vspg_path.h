@@ -781,10 +781,11 @@ VDEV int li_surface_pre(const DScene &S, PathState &st, IsgSample &isg, PC &pc, 
     Spec Le = !tri_hit && q.is_light ? light_L(q, si.n, -st.rd) : sp(0.f);  // :377 (triangles and spheres carry no area light)
     float w_direct = 0.f;
     if (nonzero(Le)) {
-        // (the hint only orders the two blocks, the camera ray's first: with the MIS side first the pinned k_render_wave_wg3 holds
-        //  ten SGPRs in lanes over its loop, with the whole emitter branch out of line six where its carry twin holds eight --
-        //  tests/test_headline_kernel_resources.py, tests/test_wg3_carry_kernel.py; this order gives eight and eight)
-        if (__builtin_expect(st.depth == 0 || st.specularBounce, 1)) {
+        // (no branch hint: one used to order these two blocks to hold the pinned k_render_wave_wg3 and its carry twin at eight SGPRs
+        //  in lanes each.  Since the rectangle walks keep one lane mask per record both hold two without it, and with it the pinned
+        //  kernel holds none but its twin two -- more than the pinned one, which tests/test_wg3_carry_kernel.py does not allow --
+        //  and 359 vector instructions more than it, where 357 are allowed; without it 353.)
+        if (st.depth == 0 || st.specularBounce) {
             st.L = st.L + wdiv(st.beta * Le, avg(st.r_u));
             w_direct = 1.0f;
         } else {
