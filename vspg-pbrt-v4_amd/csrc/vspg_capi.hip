@@ -2295,6 +2295,7 @@ static void build_dscene(const VspgScene &sc, const VspgIntegratorParams &prm, c
         frame = isect_rec_build(&D->irec[i], q.n, q.p00, q.e1, q.e2, q.inv_l1, q.inv_l2, frame);
         if (light) D->light_quads[D->n_lights++] = i;
     }
+    rect_planes_build(&D->planes, D->irec, D->n_quads);
     D->n_inf = sc.n_infinite_lights;
     for (int i = 0; i < sc.n_infinite_lights && i < VSPG_MAX_INFINITE_LIGHTS; ++i) {
         D->inf_type[i] = sc.infinite_lights[i].type;

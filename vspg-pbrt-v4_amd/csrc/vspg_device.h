@@ -616,6 +616,44 @@ inline int isect_rec_build(IsectRec *rec, const float *n, const float *p00, cons
     rec->axes = ((frame - cur + 3) % 3) | (swapped ? kIsectUvSwapped : 0) | (rec->kind == 1 ? kIsectAxisAligned : 0) | (frame << kIsectAxisShift);
     return frame;
 }
+// The planes of the axis-aligned records, one short list per axis, for the any-hit walk's pre-pass (rects_any_planes): whether some
+// lane of a wavefront can hit a record's plane before tMax needs the plane's coordinate and axis only, not the record.  c[a][k] is
+// the coordinate (rec.f[1]) of the k-th axis-aligned record on axis a, in index order, for the first kPlaneChunk of them.  Every
+// record has a POSITION, a bit of a 32-bit mask: plane k of axis a has position 4 a + k + 1, and every other record -- the generic
+// ones, and an axis-aligned one whose axis already lists kPlaneChunk planes -- takes the positions from 13 on in index order; those
+// are walked without a pre-test, as every record was before.  `listed` and `always` have the bits of the two kinds, `order` names
+// the record at each position (4 bits each, position 1 first).  Fixed positions: the pre-pass needs no count and no shift, and
+// the lists load with no address that waits for one.  Bit 0 stays clear: 0-or-1 is the one select the compiler moves to the
+// vector unit.
+constexpr int kPlaneChunk = 4;   // planes listed per axis (the fog box has 2, 3 and 2)
+struct RectPlanes {
+    float c[3][kPlaneChunk];
+    uint32_t listed, always;
+    uint32_t order[4];
+};
+static_assert(VSPG_MAX_QUADS <= 16 && 3 * kPlaneChunk + VSPG_MAX_QUADS < 32, "a record index is 4 bits of RectPlanes::order, a position one bit of 32");
+// Host code, next to isect_rec_build wherever records are built.
+inline void rect_planes_build(RectPlanes *T, const IsectRec *recs, int n) {
+    *T = RectPlanes{};
+    uint32_t done = 0;
+    int count[3] = {0, 0, 0};
+    auto place = [&](int pos, int i) { T->order[(pos - 1) >> 3] |= (uint32_t)i << (4 * ((pos - 1) & 7)); };
+    for (int i = 0; i < n; ++i) {
+        const int a = (recs[i].axes >> kIsectAxisShift) & 3;
+        if (!(recs[i].axes & kIsectAxisAligned) || a > 2 || count[a] == kPlaneChunk) continue;
+        const int pos = kPlaneChunk * a + count[a] + 1;
+        T->c[a][count[a]++] = recs[i].f[1];
+        T->listed |= 1u << pos;
+        place(pos, i);
+        done |= 1u << i;
+    }
+    int pos = 3 * kPlaneChunk + 1;
+    for (int i = 0; i < n; ++i)
+        if (!(done >> i & 1u)) {
+            T->always |= 1u << pos;
+            place(pos++, i);
+        }
+}
 // guiding field in HBM (see vspg_guiding.h): [0] surface, [1] volume; nodes == nullptr -> untrained
 struct DField {
     int32_t n_nodes, n_regions;
@@ -734,6 +772,7 @@ struct DScene {
     VspgIntegratorParams prm;
     // render config
     int32_t xres, yres, seed, shard_index, shard_count;
+    RectPlanes planes;         // of irec (rect_planes_build), inside the first 4 KB like everything above
     DSphere spheres[VSPG_MAX_SPHERES];
     const DTri *tris;          // in BVH leaf order
     const DBvh4Node *bvh;
@@ -790,6 +829,8 @@ struct DScene {
     // else: no offset of the record the existing kernels read moves.
     DEnvLight env[VSPG_MAX_INFINITE_LIGHTS];
 };
+static_assert(offsetof(DScene, planes) + sizeof(RectPlanes) <= 4096 && offsetof(DScene, shard_count) < 4096,
+              "the fields the path loops read, the plane table among them, lie in the first 4 KB of DScene (scalar loads with no base register of their own)");
 // DScene::has_boundaries as the path code reads it.  (-DVSPG_NO_BOUNDARIES: a diagnostic build without the boundary code, to price
 // its presence in the kernels that serve scenes without boundaries -- same results on those scenes.)
 // BND: what the instantiation knows at compile time -- 0: no boundaries (the code for them is not compiled in: the wavefront
@@ -875,6 +916,10 @@ VDEV bool beyond(float num, float denom, float tMax) {
 VDEV float comp(V3 v, int axis) { return axis == 0 ? v.x : (axis == 1 ? v.y : v.z); }  // axis is wave-uniform
 // two registers trade contents in one instruction (v_swap_b32); a cyclic step of a vector is two of them, where moves take four
 VDEV void swap_regs(float &a, float &b) { asm("v_swap_b32 %0, %1" : "+v"(a), "+v"(b)); }
+// four wave-uniform values are formed where this stands, in scalar registers (no instruction): the compiler would otherwise move each
+// scalar load down to its first use, behind a branch and with a wait of its own.  The arguments MUST be wave-uniform by construction
+// (loads through a kernel argument at a uniform address): for a per-lane value the compiler would quietly take the first lane's.
+VDEV void here(float a, float b, float c, float d) { asm volatile("" : : "s"(a), "s"(b), "s"(c), "s"(d)); }
 // The ray in the frame of the next record (IsectRec): `steps` cyclic steps (x,y,z) <- (y,z,x).  `steps` is wave-uniform, so the
 // loop is a scalar branch around four instructions; it is ONE step in a loop and not a rotation by one or by two as straight-line
 // code because the loops over the records are inlined several times over.  The mask bounds it whatever a record holds.
@@ -982,6 +1027,70 @@ VDEV bool rects_any(const IsectRec *recs, int n, V3 o, V3 d, float tMax) {
         const IsectRec &r = recs[i];
         float t, u, v;   // (u, v) of a swapped record trade places: the [0,1]^2 test does not care
         rect_frame(fo, fd, r.axes);
+        any = any | rect_hit_uv(r, fo, fd, tMax, &t, &u, &v);
+    }
+    return any;
+}
+// rects_any in two stages (the kernels call this one; rects_any above is the plain walk it has to equal, record for record).
+// A record's any-hit test depends on the ray and tMax alone and the result is an OR over the records, so the records may be asked in
+// any order, and a record none of whose lanes passes rect_hit_uv's pre-tests need not be visited: the plain walk left it at its vote.
+//   Pre-pass: the pre-tests of every axis-aligned record, from the plane lists (RectPlanes) -- num = c - o[a], the sign test on the
+// bit patterns, |num| > tMax * |d[a]| * 1.000001f with beyond()'s two multiplications in beyond()'s order, one vote per plane.  They
+// are rect_hit_uv's operations on rect_hit_uv's operands (the turned ray's .x IS component a), so each lane is a candidate of exactly
+// the planes it was a candidate of; but the threshold has three values and not one per record, the ray is not turned and no record
+// is loaded.  In a closed room a shadow ray is a candidate of nothing -- the walls lie behind it or beyond tMax -- and the walk
+// ends here, on one branch.
+//   Walk: over the positions whose vote passed and those that are not listed (generic records, a fifth plane on an axis), with
+// rect_frame / rect_hit_uv as they are; the steps come from the record's frame axis and the current one, since the records between
+// them were skipped.  The order is the positions', not the records': an OR does not care.
+// The host's vote is the lane itself or, with VSPG_RECT_VOTE_TAKEN, always taken -- then every record is walked (rect_hit_uv).
+VDEV uint32_t plane_vote(float c, float oa, float da, float thr, uint32_t bit) {
+    const float num = c - oa;
+    const bool same = (int32_t)(__builtin_bit_cast(uint32_t, num) ^ __builtin_bit_cast(uint32_t, da)) >= 0, within = !(__builtin_fabsf(num) > thr);
+#if defined(__HIP_DEVICE_COMPILE__)
+    // the two compares' own lane masks (a vote on their conjunction goes through an int per lane)
+    const bool some = (__builtin_amdgcn_ballot_w64(same) & __builtin_amdgcn_ballot_w64(within)) != 0ull;
+#elif defined(VSPG_RECT_VOTE_TAKEN)
+    const bool some = true;
+#else
+    const bool some = same & within;
+#endif
+    return some ? bit : 0u;   // wave-uniform
+}
+// the votes of the planes listed on axis a, each at its position
+VDEV uint32_t axis_votes(const float *c, uint32_t listed, int a, float oa, float da, float tMax) {
+    const float thr = tMax * __builtin_fabsf(da) * 1.000001f;
+    static_assert(kPlaneChunk == 4, "one four-word load");
+    const float p[kPlaneChunk] = {c[0], c[1], c[2], c[3]};
+    here(p[0], p[1], p[2], p[3]);   // the list in one load ahead of the guards, not a word and a wait behind each of them
+    uint32_t m = 0;
+#pragma unroll
+    for (int k = 0; k < kPlaneChunk; ++k) {
+        const uint32_t bit = 2u << (kPlaneChunk * a + k);
+        if (!(listed & bit)) return m;   // a list has no holes
+        m |= plane_vote(p[k], oa, da, thr, bit);
+    }
+    return m;
+}
+VDEV bool rects_any_planes(const RectPlanes &T, const IsectRec *recs, V3 o, V3 d, float tMax) {
+    const uint32_t listed = T.listed;
+    uint32_t mask = T.always;
+    mask |= axis_votes(T.c[0], listed, 0, o.x, d.x, tMax);
+    mask |= axis_votes(T.c[1], listed, 1, o.y, d.y, tMax);
+    mask |= axis_votes(T.c[2], listed, 2, o.z, d.z, tMax);
+    if (mask == 0) return false;   // wave-uniform
+    bool any = false;
+    V3 fo = o, fd = d;
+    int cur = 0;   // the frame axis fo, fd are in
+#pragma nounroll
+    while (mask != 0) {
+        const int pos = __builtin_ctz(mask) - 1;
+        mask &= mask - 1;
+        const IsectRec &r = recs[(T.order[pos >> 3] >> (4 * (pos & 7))) & 15u];
+        const int frame = (r.axes >> kIsectAxisShift) & 3;
+        float t, u, v;
+        rect_frame(fo, fd, frame - cur + (frame < cur ? 3 : 0));
+        cur = frame;
         any = any | rect_hit_uv(r, fo, fd, tMax, &t, &u, &v);
     }
     return any;
@@ -1334,7 +1443,7 @@ VLEAF Isect scene_intersect(const DScene &S, V3 o, V3 d, float tMax) {
 }
 template <bool FULL = true>
 VLEAF bool scene_intersect_any(const DScene &S, V3 o, V3 d, float tMax) {
-    bool any = rects_any(S.irec, S.n_quads, o, d, tMax);
+    bool any = rects_any_planes(S.planes, S.irec, o, d, tMax);
     if (FULL && S.n_tris > 0 && !any) any = bvh_any(S, o, d, tMax);
     if (FULL && S.n_spheres > 0 && !any) {
         for (int i = 0; i < S.n_spheres; ++i) {
