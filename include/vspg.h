@@ -177,6 +177,28 @@ typedef struct VspgInfiniteLight {
     float w_light[3];
 } VspgInfiniteLight;
 
+/* Point and spot lights (PointLight, src/pbrt/lights.h:203-263, lights.cpp:196-248; SpotLight, lights.h:811-873,
+ * lights.cpp:1425-1555): lights AT a position inside the scene, delta lights like the distant light (SampleLi has pdf 1, PDF_Li is 0,
+ * the estimate is weighted as IsDeltaLight prescribes, guidedvolpathvspgintegrator.cpp:1248-1249).
+ *   I                  the reference's `scale * I` multiplied out (RGB), the convention of VspgInfiniteLight.L
+ *   render_from_light  the light's Transform, row-major and affine (last row 0 0 0 1), BOTH matrices as for VspgSphere / VspgMedium
+ *   light_from_render  so that ApplyInverse sees the caller's floats.  The light sits at render_from_light(0, 0, 0); a spot light
+ *                      shines along render_from_light(0, 0, 1).  vspg_point_light_at / vspg_spot_light_look_at fill both.
+ *   cone_angle_deg     spot lights only: "coneangle" (the whole cone's half angle) and "conedeltaangle" (the width of the smooth falloff
+ *   cone_delta_deg     band inside it).  The library forms cosFalloffEnd = cosf(Radians(cone_angle_deg)) and cosFalloffStart =
+ *                      cosf(Radians(cone_angle_deg - cone_delta_deg)) on the host, as the constructor does (lights.cpp:1438-1439).
+ * A context point that coincides with the light's position divides by zero, as in the reference, which has no guard. */
+enum { VSPG_LIGHT_POINT = 3, VSPG_LIGHT_SPOT = 4 };
+#define VSPG_MAX_POINT_LIGHTS 8
+typedef struct VspgPointLight {
+    int32_t type;                 /* VSPG_LIGHT_POINT | VSPG_LIGHT_SPOT */
+    float I[3];
+    float render_from_light[16];
+    float light_from_render[16];
+    float cone_angle_deg;
+    float cone_delta_deg;
+} VspgPointLight;
+
 /* tri_flags (optional, one int32 per triangle, HOST pointer; NULL = all 0): bit 0 = VSPG_MATERIAL_INTERFACE, bits 1-2 =
  * the VSPG_IFACE_* bits, bit 3 = flip the geometric normal (the mesh's reverseOrientation ^ transformSwapsHandedness,
  * shapes.h:934-936 -- only a medium transition can tell the two sides of a diffuse triangle apart). */
@@ -200,6 +222,13 @@ typedef struct VspgScene {
     /* the camera's medium (CameraBase::medium = the current OUTSIDE medium at the Camera directive, scene.cpp:153-155):
      * 0 = the scene's medium (as ever), 1 = none -- the camera looks at the volume from outside */
     int32_t camera_outside_medium;
+    /* Point and spot lights.  THE RECORD GREW by this tail (VSPG_ABI_VERSION stays 7: nothing in front of it moved): callers are
+     * recompiled against this header, and a caller that fills the record field by field zeroes it first (memset), which leaves
+     * n_point_lights = 0.
+     * The scene's LIGHT LIST, which every light sampler indexes, is: the emissive rectangles in rectangle order, then the infinite
+     * lights, then the point lights -- every index of a scene without point lights keeps its meaning. */
+    int32_t n_point_lights;
+    VspgPointLight point_lights[VSPG_MAX_POINT_LIGHTS];
 } VspgScene;
 
 /* ---- integrator parameters: same names and defaults as
@@ -324,6 +353,16 @@ int vspg_camera_look_at(VspgCamera *cam, const float eye[3], const float look[3]
                         const float up[3], float fov_degrees, int xres, int yres);
 /* inv = m^-1 for an affine row-major 4x4 (computed in double, rounded once); returns VSPG_EINVAL for a singular matrix. */
 int vspg_transform_inverse(const float m[16], float inv[16]);
+/* The transform of a spot light given like the scene file's "from" / "to" under the current transformation matrix `ctm` (row-major,
+ * affine; NULL = identity), SpotLight::Create (lights.cpp:1531-1536):
+ *   renderFromLight = ctm * Translate(from) * Inverse(Frame::FromZ(Normalize(to - from)))
+ * Fills l->render_from_light and l->light_from_render (the product of the inverses in the opposite order) and nothing else.  The
+ * frame is CoordinateSystem's (util/vecmath.h:1007-1013) in float; matrix products accumulate by fused multiply-add in float, as
+ * SquareMatrix's do; the inverse of the frame and of `ctm` are vspg_transform_inverse's.  VSPG_EINVAL: a null argument, from == to,
+ * a non-finite argument, a `ctm` that is not affine or is singular. */
+int vspg_spot_light_look_at(VspgPointLight *l, const float from[3], const float to[3], const float ctm[16] /* or NULL */);
+/* The same for a point light at `from` (PointLight::Create, lights.cpp:240-242): renderFromLight = ctm * Translate(from). */
+int vspg_point_light_at(VspgPointLight *l, const float from[3], const float ctm[16] /* or NULL */);
 /* Fills `scene` with the App.-F fog box: box [-1,1]^3, Kd .73 walls, 0.5x0.5 ceiling
  * light Le (17,12,4) at y=.999, homogeneous fog sigma_a .05 sigma_s .45 g 0, camera at
  * (0,0,-.95) looking +z, fov 60. */
@@ -710,6 +749,19 @@ int vspg_renderer_set_environment_image(VspgRenderer *r, int infinite_light_inde
 #define VSPG_ENVLIGHT_OUT 16
 int vspg_envlight_batch(VspgRenderer *r, int infinite_light_index, int n, const float *dirs /*3n*/, const float *u /*2n*/,
                         float *out /*16n*/, void *stream);
+
+/* Batch driver of light sampling (parity tests): per element the renderer's light sampler picks a light for the context and that
+ * light is sampled -- the light_sampler_sample, light_sampler_pmf and sample_light the path kernels call, under the sampler the
+ * renderer was created with ("uniform", "power", "bvh") and for every light kind the scene holds.  HOST arrays.
+ *   ctx_p  3n floats: the context point            ctx_n  3n floats: its normal, zeros = a medium vertex
+ *   u      3n floats: the pick's variate, then the two of SampleLi
+ *   out    VSPG_LIGHT_SAMPLE_OUT floats per element:
+ *   [0] the picked index into the light list, -1 = none (everything after it is 0 then)   [1] the pmf Sample returned
+ *   [2] PMF(ctx, that light)   [3] 1 = SampleLi gave a sample, 0 = none (everything after it is 0 then)
+ *   [4..6] wi   [7..9] L   [10] pdf   [11..13] pLight   [14] 1 = a delta light   [15] 0 */
+#define VSPG_LIGHT_SAMPLE_OUT 16
+int vspg_light_sample_batch(VspgRenderer *r, int n, const float *ctx_p /*3n*/, const float *ctx_n /*3n*/, const float *u /*3n*/,
+                            float *out /*16n*/, void *stream);
 
 #ifdef __cplusplus
 }

@@ -77,13 +77,24 @@ class VspgInfiniteLight(C.Structure):
     _fields_ = [("type", C.c_int32), ("L", f3), ("w_light", f3)]
 
 
+VSPG_MAX_POINT_LIGHTS = 8
+LIGHT_POINT, LIGHT_SPOT = 3, 4
+LIGHT_SAMPLE_OUT = 16  # VSPG_LIGHT_SAMPLE_OUT: floats per element of vspg_light_sample_batch
+
+
+class VspgPointLight(C.Structure):
+    _fields_ = [("type", C.c_int32), ("I", f3), ("render_from_light", C.c_float * 16), ("light_from_render", C.c_float * 16),
+                ("cone_angle_deg", C.c_float), ("cone_delta_deg", C.c_float)]
+
+
 class VspgScene(C.Structure):
     _fields_ = [("n_quads", C.c_int32), ("quads", VspgQuad * VSPG_MAX_QUADS),
                 ("camera", VspgCamera), ("medium", VspgMedium),
                 ("n_triangles", C.c_int32), ("tri_p", C.POINTER(C.c_float)), ("tri_kd", C.POINTER(C.c_float)),
                 ("n_infinite_lights", C.c_int32), ("infinite_lights", VspgInfiniteLight * VSPG_MAX_INFINITE_LIGHTS),
                 ("tri_flags", C.POINTER(C.c_int32)), ("n_spheres", C.c_int32), ("spheres", VspgSphere * VSPG_MAX_SPHERES),
-                ("camera_outside_medium", C.c_int32)]
+                ("camera_outside_medium", C.c_int32),
+                ("n_point_lights", C.c_int32), ("point_lights", VspgPointLight * VSPG_MAX_POINT_LIGHTS)]
 
 
 class VspgIntegratorParams(C.Structure):
@@ -293,6 +304,9 @@ SYMBOLS = [
     ("vspg_blackbody_batch", C.c_int, [_vp, C.c_int, _P(C.c_float), _P(C.c_float), _P(C.c_float), _vp]),
     ("vspg_renderer_set_environment_image", C.c_int, [_vp, C.c_int, _P(C.c_float), C.c_int, _P(C.c_float), _vp]),
     ("vspg_envlight_batch", C.c_int, [_vp, C.c_int, C.c_int, _P(C.c_float), _P(C.c_float), _P(C.c_float), _vp]),
+    ("vspg_spot_light_look_at", C.c_int, [_P(VspgPointLight), f3, f3, _P(C.c_float)]),
+    ("vspg_point_light_at", C.c_int, [_P(VspgPointLight), f3, _P(C.c_float)]),
+    ("vspg_light_sample_batch", C.c_int, [_vp, C.c_int, _P(C.c_float), _P(C.c_float), _P(C.c_float), _P(C.c_float), _vp]),
     ("vspg_renderer_get_tr_buffer", C.c_int, [_vp, _P(C.c_float), _P(C.c_int32), _vp]),
     ("vspg_renderer_set_tr_buffer", C.c_int, [_vp, _P(C.c_float), _vp]),
     ("vspg_renderer_set_guiding_field", C.c_int, [_vp, _P(VspgField), _P(VspgField), _vp]),
@@ -507,6 +521,62 @@ def add_infinite_light(scene, kind, L, w_light=(0.0, 1.0, 0.0)):
     il.w_light[:] = [float(x) for x in w]
     scene.n_infinite_lights = k + 1
     return scene
+
+
+def _add_point_light(scene, kind, I, scale, fill_transform):
+    """Appends a VspgPointLight of `kind` with I * scale (float32, as the host multiplies them out) and lets `fill_transform(light)` fill
+    both matrices; returns the light's index among the scene's point lights."""
+    import numpy as np
+    if scene.n_point_lights >= VSPG_MAX_POINT_LIGHTS:
+        raise ValueError("too many point lights (VSPG_MAX_POINT_LIGHTS = %d)" % VSPG_MAX_POINT_LIGHTS)
+    l = scene.point_lights[scene.n_point_lights]
+    l.type = kind
+    for k in range(3):
+        l.I[k] = np.float32(I[k]) * np.float32(scale)
+    _check(load(), fill_transform(l))
+    scene.n_point_lights += 1
+    return scene.n_point_lights - 1
+
+
+def _ctm_pointer(ctm):
+    import numpy as np
+    if ctm is None:
+        return None, None
+    a = np.ascontiguousarray(np.asarray(ctm, dtype=np.float32).reshape(16))
+    return a, a.ctypes.data_as(C.POINTER(C.c_float))
+
+
+def add_point_light(scene, I, from_, scale=1, power=None, ctm=None):
+    """LightSource "point" (PointLight::Create, lights.cpp:224-248): intensity I (RGB) times `scale`, at `from_` under the current
+    transformation matrix `ctm` (4 x 4 row-major, None = identity).  power > 0 rescales as Create does: scale *= power / (4 Pi)."""
+    import numpy as np
+    lib = load()
+    sc = np.float32(scale)
+    if power is not None and power > 0:
+        sc = sc * (np.float32(power) / (np.float32(4) * np.float32(np.pi)))
+    keep, cp = _ctm_pointer(ctm)
+    return _add_point_light(scene, LIGHT_POINT, I, sc, lambda l: lib.vspg_point_light_at(C.byref(l), f3(*[float(v) for v in from_]), cp))
+
+
+def add_spot_light(scene, I, from_, to, coneangle=30, conedelta=5, scale=1, power=None, ctm=None):
+    """LightSource "spot" (SpotLight::Create, lights.cpp:1520-1555): intensity I (RGB) times `scale`, at `from_` shining towards `to`
+    under `ctm`; full intensity inside coneangle - conedelta degrees of the axis, a smooth falloff to zero at coneangle.  power > 0
+    rescales as Create does: scale *= power / (2 Pi ((1 - cosStart) + (cosStart - cosEnd) / 2))."""
+    import numpy as np
+    lib = load()
+    one, two = np.float32(1), np.float32(2)
+    sc = np.float32(scale)
+    if power is not None and power > 0:
+        rad = np.float32(np.pi) / np.float32(180)
+        ce = np.cos(rad * np.float32(coneangle))
+        cs = np.cos(rad * (np.float32(coneangle) - np.float32(conedelta)))
+        sc = sc * (np.float32(power) / (two * np.float32(np.pi) * ((one - cs) + (cs - ce) / two)))
+
+    def fill(l):
+        l.cone_angle_deg, l.cone_delta_deg = coneangle, conedelta
+        return lib.vspg_spot_light_look_at(C.byref(l), f3(*[float(v) for v in from_]), f3(*[float(v) for v in to]), cp)
+    keep, cp = _ctm_pointer(ctm)
+    return _add_point_light(scene, LIGHT_SPOT, I, sc, fill)
 
 
 def set_triangles(scene, tri_p, tri_kd=None):
@@ -794,6 +864,22 @@ class Renderer:
         fp = _P(C.c_float)
         _check(self.lib, self.lib.vspg_envlight_batch(self.h, int(index), d.shape[0], d.ctypes.data_as(fp), uu.ctypes.data_as(fp),
                                                      out.ctypes.data_as(fp), _vp(0)))
+        return out
+
+    def light_sample_batch(self, ctx_p, ctx_n, u):
+        """Per context (point ctx_p, normal ctx_n -- zeros = a medium vertex) and variates u = (pick, u0, u1): the light the renderer's
+        light sampler picks and that light's SampleLi, as the path kernels evaluate them (vspg_light_sample_batch).  Returns an
+        (n, LIGHT_SAMPLE_OUT) float32 array: index | pmf | PMF(ctx, light) | has sample | wi (3) | L (3) | pdf | pLight (3) | delta | 0."""
+        import numpy as np
+        p = np.ascontiguousarray(np.asarray(ctx_p, dtype=np.float32).reshape(-1, 3))
+        nn = np.ascontiguousarray(np.asarray(ctx_n, dtype=np.float32).reshape(-1, 3))
+        uu = np.ascontiguousarray(np.asarray(u, dtype=np.float32).reshape(-1, 3))
+        if not (p.shape[0] == nn.shape[0] == uu.shape[0]):
+            raise ValueError("light_sample_batch: %d points, %d normals, %d variate triples" % (p.shape[0], nn.shape[0], uu.shape[0]))
+        out = np.empty((p.shape[0], LIGHT_SAMPLE_OUT), dtype=np.float32)
+        fp = C.POINTER(C.c_float)
+        _check(self.lib, self.lib.vspg_light_sample_batch(self.h, p.shape[0], p.ctypes.data_as(fp), nn.ctypes.data_as(fp), uu.ctypes.data_as(fp),
+                                                          out.ctypes.data_as(fp), None))
         return out
 
     def counters(self, stream=None):

@@ -1555,6 +1555,37 @@ __global__ __launch_bounds__(kBlock) void k_envlight(const DScene *__restrict__ 
     o[12] = ok ? ls.pdf : 0.f;
     o[13] = ok ? ls.L.r : 0.f; o[14] = ok ? ls.L.g : 0.f; o[15] = ok ? ls.L.b : 0.f;
 }
+// vspg_light_sample_batch (include/vspg.h): lightSampler.Sample, lightSampler.PMF and light.SampleLi as the path kernels call them
+__global__ __launch_bounds__(kBlock) void k_light_sample_batch(const DScene *__restrict__ Sp, int n, const float *__restrict__ ctx_p,
+                                                               const float *__restrict__ ctx_n, const float *__restrict__ u, float *__restrict__ out) {
+    const int i = blockIdx.x * kBlock + threadIdx.x;
+    const DScene &S = *Sp;
+    stage_scene_lds(S);  // sample_light reads a rectangle light's record from the LDS copy
+    __syncthreads();
+    if (i >= n) return;
+    float *o = out + (size_t)VSPG_LIGHT_SAMPLE_OUT * i;
+    for (int k = 0; k < VSPG_LIGHT_SAMPLE_OUT; ++k) o[k] = 0.f;
+    const V3 p = ld3(ctx_p + 3 * (size_t)i), nn = ld3(ctx_n + 3 * (size_t)i);
+    int lightIndex = 0;
+    float pmf = 0.f;
+    if (!light_sampler_sample(S, p, nn, u[3 * (size_t)i], &lightIndex, &pmf)) {
+        o[0] = -1.f;
+        return;
+    }
+    o[0] = (float)lightIndex;
+    o[1] = pmf;
+    o[2] = light_sampler_pmf(S, p, nn, lightIndex);
+    LightLi ls{};
+    bool delta_light = false;
+    if (!sample_light(S, lightIndex, p, u[3 * (size_t)i + 1], u[3 * (size_t)i + 2], &ls, &delta_light)) return;
+    o[3] = 1.f;
+    o[4] = ls.wi.x; o[5] = ls.wi.y; o[6] = ls.wi.z;
+    o[7] = ls.L.r; o[8] = ls.L.g; o[9] = ls.L.b;
+    o[10] = ls.pdf;
+    const V3 pl = ls.pLight.mid();
+    o[11] = pl.x; o[12] = pl.y; o[13] = pl.z;
+    o[14] = delta_light ? 1.f : 0.f;
+}
 __global__ __launch_bounds__(kBlock) void k_libm_log1m(int n, const float *__restrict__ x, float *__restrict__ out) {
     int i = blockIdx.x * kBlock + threadIdx.x;
     vspg_libm::stage_log_tab_lds();
@@ -2064,11 +2095,33 @@ static lightbounds_t quad_light_bounds(const DQuad &q, int reverse_orientation) 
     lb.twoSided = q.two_sided;
     return lb;
 }
+// PointLight::Bounds (lights.cpp:200-205) / SpotLight::Bounds (:1457-1467): a degenerate box at the light's position
+static lightbounds_t point_light_bounds(const DPointLight &P) {
+    lightbounds_t lb;
+    lb.bmin = lb.bmax = V3(P.pos[0], P.pos[1], P.pos[2]);
+    const float maxI = fmaxf(P.I[0], fmaxf(P.I[1], P.I[2]));  // scale * I->MaxValue()
+    lb.twoSided = 0;
+    if (P.type == VSPG_LIGHT_SPOT) {
+        lb.w = V3(P.axis[0], P.axis[1], P.axis[2]);
+        lb.phi = maxI * 4 * PI_F;
+        lb.cosTheta_o = P.cosFalloffStart;
+        float cosTheta_e = cosf(acosf(P.cosFalloffEnd) - acosf(P.cosFalloffStart));
+        // "Allow a little slop here to deal with fp round-off error in the computation of cosTheta_p in the importance function."
+        if (cosTheta_e == 1 && P.cosFalloffEnd != P.cosFalloffStart) cosTheta_e = 0.999f;
+        lb.cosTheta_e = cosTheta_e;
+    } else {
+        lb.w = V3(0, 0, 1);
+        lb.phi = 4 * PI_F * maxI;
+        lb.cosTheta_o = cosf(PI_F);
+        lb.cosTheta_e = cosf(PI_F / 2);
+    }
+    return lb;
+}
 // (called again by vspg_renderer_set_environment_image: the power sampler's table depends on an image light's Phi)
 static void build(const VspgScene &sc, const VspgIntegratorParams &prm, DScene *D) {
     DLightSampler *ls = &D->lsamp;
     std::memset(ls, 0, sizeof *ls);
-    const int n_all = D->n_lights + D->n_inf;
+    const int n_all = D->n_lights + D->n_inf + D->n_point, first_point = D->n_lights + D->n_inf;
     for (int i = 0; i < kMaxLights; ++i) ls->bit_trail[i] = 0xffffffffu;
     for (int i = 0; i < VSPG_MAX_QUADS; ++i) ls->light_of_quad[i] = -1;
     for (int i = 0; i < D->n_lights; ++i) ls->light_of_quad[D->light_quads[i]] = i;
@@ -2078,9 +2131,13 @@ static void build(const VspgScene &sc, const VspgIntegratorParams &prm, DScene *
     int n_items = 0;
     v3 amin = V3(INFINITY, INFINITY, INFINITY), amax = V3(-INFINITY, -INFINITY, -INFINITY);
     for (int i = 0; i < n_all; ++i) {
-        if (i >= D->n_lights) { ls->inf_light[ls->n_inf++] = i; continue; }  // Bounds() == {}
-        const int qi = D->light_quads[i];
-        lightbounds_t lb = quad_light_bounds(D->quads[qi], sc.quads[qi].reverse_orientation);
+        if (i >= D->n_lights && i < first_point) { ls->inf_light[ls->n_inf++] = i; continue; }  // Bounds() == {}
+        lightbounds_t lb;
+        if (i >= first_point) lb = point_light_bounds(D->point[i - first_point]);
+        else {
+            const int qi = D->light_quads[i];
+            lb = quad_light_bounds(D->quads[qi], sc.quads[qi].reverse_orientation);
+        }
         if (lb.phi > 0) {
             items[n_items].light = i; items[n_items].lb = lb; n_items++;
             amin = v_min3(amin, lb.bmin); amax = v_max3(amax, lb.bmax);
@@ -2103,6 +2160,16 @@ static void build(const VspgScene &sc, const VspgIntegratorParams &prm, DScene *
                 const DQuad &q = D->quads[D->light_quads[i]];
                 for (int c = 0; c < 3; ++c) L[c] = q.Le[c];
                 k = PI_F * (q.two_sided ? 2 : 1) * q.area;  // DiffuseAreaLight::Phi (lights.cpp:826-843)
+            } else if (i >= first_point) {
+                const DPointLight &P = D->point[i - first_point];
+                for (int c = 0; c < 3; ++c) L[c] = P.I[c];
+                k = 4 * PI_F;  // PointLight::Phi = 4 * Pi * scale * I (lights.cpp:196-198)
+                if (P.type == VSPG_LIGHT_SPOT) {
+                    // SpotLight::Phi (lights.cpp:1452-1455) in its order: scale * Iemit * 2 * Pi * ((1 - cosStart) + (cosStart - cosEnd) / 2)
+                    const float cone = (1 - P.cosFalloffStart) + (P.cosFalloffStart - P.cosFalloffEnd) / 2;
+                    for (int c = 0; c < 3; ++c) phi[c] = L[c] * 2 * PI_F * cone;
+                    have_phi = true;
+                }
             } else {
                 const int j = i - D->n_lights;
                 for (int c = 0; c < 3; ++c) L[c] = D->inf_L[j][c];
@@ -2304,6 +2371,49 @@ static void build_dscene(const VspgScene &sc, const VspgIntegratorParams &prm, c
             DEnvLight &E = D->env[i];
             E.res = 1;
             for (int k = 0; k < 3; ++k) { E.m[4 * k] = E.mi[4 * k] = 1.f; E.sum_L[k] = 1.f; }
+        }
+    }
+    // point and spot lights (vspg_pointlight.h): what the constructors and SampleLi's first line derive from the transform
+    D->n_point = sc.n_point_lights;
+    for (int i = 0; i < sc.n_point_lights && i < VSPG_MAX_POINT_LIGHTS; ++i) {
+        const VspgPointLight &in = sc.point_lights[i];
+        DPointLight &P = D->point[i];
+        P.type = in.type;
+        const float *m = in.render_from_light;
+        // renderFromLight(Point3f(0, 0, 0)), Transform::operator()(Point3f) (transform.h:310-319): the sums as written, then `wp == 1`
+        float q[4];
+        for (int k = 0; k < 4; ++k) {
+            volatile float a = m[4 * k] * 0.f;  // volatile: one rounding per operation, no contraction
+            volatile float b = m[4 * k + 1] * 0.f;
+            volatile float c2 = m[4 * k + 2] * 0.f;
+            volatile float sum = a + b;
+            sum = sum + c2;
+            sum = sum + m[4 * k + 3];
+            q[k] = sum;
+        }
+        for (int k = 0; k < 3; ++k) P.pos[k] = q[3] == 1 ? q[k] : q[k] / q[3];
+        for (int k = 0; k < 3; ++k) P.I[k] = in.I[k];
+        for (int k = 0; k < 12; ++k) P.mi[k] = in.light_from_render[k];
+        P.cosFalloffEnd = P.cosFalloffStart = 0.f;
+        P.axis[0] = P.axis[1] = 0.f; P.axis[2] = 1.f;
+        if (in.type == VSPG_LIGHT_SPOT) {
+            // the constructor's cosines (lights.cpp:1438-1439): totalWidth = coneangle, falloffStart = coneangle - conedelta; Radians (math.h:261-263)
+            volatile float start_deg = in.cone_angle_deg - in.cone_delta_deg;
+            const float deg2rad = 3.14159265358979323846f / 180;
+            volatile float rad_end = deg2rad * in.cone_angle_deg, rad_start = deg2rad * start_deg;
+            P.cosFalloffEnd = std::cos((float)rad_end);
+            P.cosFalloffStart = std::cos((float)rad_start);
+            // Normalize(renderFromLight(Vector3f(0, 0, 1))) (transform.h:351-356), the w of SpotLight::Bounds
+            float w[3];
+            for (int k = 0; k < 3; ++k) {
+                volatile float a = m[4 * k] * 0.f;
+                volatile float b = m[4 * k + 1] * 0.f;
+                volatile float c2 = m[4 * k + 2] * 1.f;
+                volatile float sum = a + b;
+                sum = sum + c2;
+                w[k] = sum;
+            }
+            stv(P.axis, normv(H3{w[0], w[1], w[2]}));
         }
     }
     {   // scene bounds = union of the primitives' bounds; light.Preprocess: BoundingSphere (integrators.h:74-81, vecmath.h:1335-1338)
@@ -2733,6 +2843,23 @@ static int validate(const VspgScene *scene, const VspgIntegratorParams *p, const
         if (scene->infinite_lights[i].type != VSPG_LIGHT_UNIFORM_INFINITE && scene->infinite_lights[i].type != VSPG_LIGHT_DISTANT &&
             scene->infinite_lights[i].type != VSPG_LIGHT_IMAGE_INFINITE)
             return fail(VSPG_EINVAL, "unknown infinite light type");
+    if (scene->n_point_lights < 0 || scene->n_point_lights > VSPG_MAX_POINT_LIGHTS) return fail(VSPG_EINVAL, "n_point_lights out of range");
+    for (int i = 0; i < scene->n_point_lights; ++i) {
+        const VspgPointLight &pl = scene->point_lights[i];
+        if (pl.type != VSPG_LIGHT_POINT && pl.type != VSPG_LIGHT_SPOT) return fail(VSPG_EINVAL, "unknown point light type");
+        const float *a = pl.render_from_light, *b = pl.light_from_render;
+        for (int k = 0; k < 16; ++k)
+            if (!std::isfinite(a[k]) || !std::isfinite(b[k])) return fail(VSPG_EINVAL, "a point light's renderFromLight is not finite");
+        if (a[12] != 0 || a[13] != 0 || a[14] != 0 || a[15] != 1 || b[12] != 0 || b[13] != 0 || b[14] != 0 || b[15] != 1)
+            return fail(VSPG_EINVAL, "a point light's renderFromLight must be affine (last row 0 0 0 1)");
+        for (int k = 0; k < 3; ++k)
+            if (!std::isfinite(pl.I[k])) return fail(VSPG_EINVAL, "a point light's I is not finite");
+        if (pl.type == VSPG_LIGHT_SPOT) {
+            if (!(pl.cone_angle_deg > 0 && pl.cone_angle_deg <= 180)) return fail(VSPG_EINVAL, "a spot light's cone_angle_deg must be in (0, 180]");
+            if (!(pl.cone_delta_deg >= 0)) return fail(VSPG_EINVAL, "a spot light's cone_delta_deg must be >= 0");
+            if (!(pl.cone_delta_deg <= pl.cone_angle_deg)) return fail(VSPG_EINVAL, "a spot light's cone_delta_deg exceeds cone_angle_deg");
+        }
+    }
     int nl = scene->n_infinite_lights;
     for (int i = 0; i < scene->n_quads; ++i)
         if (scene->quads[i].Le[0] != 0 || scene->quads[i].Le[1] != 0 || scene->quads[i].Le[2] != 0) nl++;
@@ -2974,6 +3101,75 @@ int vspg_transform_inverse(const float m[16], float inv[16]) {
     inv[12] = inv[13] = inv[14] = 0.f;
     inv[15] = 1.f;
     return 0;
+}
+
+// ---- transforms of point and spot lights (PointLight::Create lights.cpp:240-242, SpotLight::Create :1531-1536) ------------------
+// SquareMatrix<4> product (util/math.h: FMA accumulation from 0), row-major
+static void mat4_mul(const float a[16], const float b[16], float out[16]) {
+    float r[16];
+    for (int i = 0; i < 4; ++i)
+        for (int j = 0; j < 4; ++j) {
+            float s = 0.f;
+            for (int k = 0; k < 4; ++k) s = std::fmaf(a[4 * i + k], b[4 * k + j], s);
+            r[4 * i + j] = s;
+        }
+    memcpy(out, r, sizeof r);
+}
+static void mat4_identity(float m[16]) { for (int i = 0; i < 16; ++i) m[i] = i % 5 == 0 ? 1.f : 0.f; }
+// m = ctm * t, inv = t_inv * ctm^-1 (Transform::operator*, transform.cpp:305-307); ctm NULL = identity (t as it stands)
+static int light_compose(VspgPointLight *l, const float *ctm, const float t[16], const float t_inv[16]) {
+    if (!ctm) {
+        memcpy(l->render_from_light, t, 64);
+        memcpy(l->light_from_render, t_inv, 64);
+        return 0;
+    }
+    for (int k = 0; k < 16; ++k)
+        if (!std::isfinite(ctm[k])) return fail(VSPG_EINVAL, "ctm is not finite");
+    float ci[16];
+    if (const int rc = vspg_transform_inverse(ctm, ci)) return rc;
+    mat4_mul(ctm, t, l->render_from_light);
+    mat4_mul(t_inv, ci, l->light_from_render);
+    return 0;
+}
+int vspg_point_light_at(VspgPointLight *l, const float from[3], const float ctm[16]) {
+    if (!l || !from) return fail(VSPG_EINVAL, "null argument");
+    for (int k = 0; k < 3; ++k)
+        if (!std::isfinite(from[k])) return fail(VSPG_EINVAL, "from is not finite");
+    float t[16], ti[16];
+    mat4_identity(t);
+    mat4_identity(ti);
+    for (int k = 0; k < 3; ++k) { t[4 * k + 3] = from[k]; ti[4 * k + 3] = -from[k]; }  // Translate (transform.cpp:38-43)
+    return light_compose(l, ctm, t, ti);
+}
+int vspg_spot_light_look_at(VspgPointLight *l, const float from[3], const float to[3], const float ctm[16]) {
+    if (!l || !from || !to) return fail(VSPG_EINVAL, "null argument");
+    for (int k = 0; k < 3; ++k)
+        if (!std::isfinite(from[k]) || !std::isfinite(to[k])) return fail(VSPG_EINVAL, "from / to is not finite");
+    using namespace hostmath;
+    const H3 dv = H3{to[0] - from[0], to[1] - from[1], to[2] - from[2]};
+    if (!(len2v(dv) > 0)) return fail(VSPG_EINVAL, "spot light: from == to");
+    const H3 z = normv(dv);
+    // Frame::FromZ: CoordinateSystem (util/vecmath.h:1007-1013)
+    const float sign = std::copysign(1.f, z.z);
+    const float a = -1 / (sign + z.z);
+    const float b = z.x * z.y * a;
+    const H3 x = H3{1 + sign * (z.x * z.x) * a, sign * b, -sign * z.x};
+    const H3 y = H3{b, sign + (z.y * z.y) * a, -z.y};
+    // dirToZ = Transform(Frame): rows x, y, z; its inverse through the library's own helper
+    float f[16], fi[16];
+    mat4_identity(f);
+    f[0] = x.x; f[1] = x.y; f[2] = x.z;
+    f[4] = y.x; f[5] = y.y; f[6] = y.z;
+    f[8] = z.x; f[9] = z.y; f[10] = z.z;
+    if (const int rc = vspg_transform_inverse(f, fi)) return rc;
+    // t = Translate(from) * Inverse(dirToZ): m = T * fi, mInv = f * T^-1
+    float T[16], Ti[16], t[16], t_inv[16];
+    mat4_identity(T);
+    mat4_identity(Ti);
+    for (int k = 0; k < 3; ++k) { T[4 * k + 3] = from[k]; Ti[4 * k + 3] = -from[k]; }
+    mat4_mul(T, fi, t);
+    mat4_mul(f, Ti, t_inv);
+    return light_compose(l, ctm, t, t_inv);
 }
 
 static void quad(VspgQuad *q, float px, float py, float pz, float ax, float ay, float az, float bx, float by, float bz,
@@ -3340,6 +3536,7 @@ static ChoiceFacts choice_facts(const VspgRenderer *r) {
     ChoiceFacts f;
     f.medium_type = r->scene.medium.type;
     f.n_tris = r->hscene.n_tris, f.n_inf = r->hscene.n_inf, f.n_spheres = r->hscene.n_spheres;
+    f.n_point = r->hscene.n_point;
     f.has_boundaries = r->hscene.has_boundaries != 0;
     f.lightsampler = r->hscene.lsamp.mode;
     f.medium_grey = r->medium_grey, f.surfaces_grey = r->surfaces_grey, f.null_zero = r->null_zero;
@@ -4519,6 +4716,27 @@ int vspg_envlight_batch(VspgRenderer *r, int infinite_light_index, int n, const 
                        (float *)dout.p);
     HIPCHK(hipGetLastError());
     HIPCHK(hipMemcpyAsync(out, dout.p, (size_t)n * VSPG_ENVLIGHT_OUT * 4, hipMemcpyDeviceToHost, s));
+    HIPCHK(hipStreamSynchronize(s));
+    return 0;
+}
+
+int vspg_light_sample_batch(VspgRenderer *r, int n, const float *ctx_p, const float *ctx_n, const float *u, float *out, void *stream) {
+    if (!r || n < 0 || (n > 0 && (!ctx_p || !ctx_n || !u || !out))) return fail(VSPG_EINVAL, "null argument");
+    if (n == 0) return 0;
+    HIPCHK(hipSetDevice(r->cfg.device));
+    hipStream_t s = (hipStream_t)stream;
+    DevBuf dp, dn, du, dout;
+    HIPCHK(hipMalloc(&dp.p, (size_t)n * 12));
+    HIPCHK(hipMalloc(&dn.p, (size_t)n * 12));
+    HIPCHK(hipMalloc(&du.p, (size_t)n * 12));
+    HIPCHK(hipMalloc(&dout.p, (size_t)n * VSPG_LIGHT_SAMPLE_OUT * 4));
+    HIPCHK(hipMemcpyAsync(dp.p, ctx_p, (size_t)n * 12, hipMemcpyHostToDevice, s));
+    HIPCHK(hipMemcpyAsync(dn.p, ctx_n, (size_t)n * 12, hipMemcpyHostToDevice, s));
+    HIPCHK(hipMemcpyAsync(du.p, u, (size_t)n * 12, hipMemcpyHostToDevice, s));
+    hipLaunchKernelGGL(k_light_sample_batch, dim3((n + kBlock - 1) / kBlock), dim3(kBlock), 0, s, r->dscene, n, (const float *)dp.p, (const float *)dn.p,
+                       (const float *)du.p, (float *)dout.p);
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipMemcpyAsync(out, dout.p, (size_t)n * VSPG_LIGHT_SAMPLE_OUT * 4, hipMemcpyDeviceToHost, s));
     HIPCHK(hipStreamSynchronize(s));
     return 0;
 }

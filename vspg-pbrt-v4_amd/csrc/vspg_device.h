@@ -669,7 +669,8 @@ struct DField {
 };
 // Light samplers beyond the uniform pick (vspg_lightsampler.h): the BVH light sampler's nodes as CompactLightBounds' accessors
 // return them, the light -> bit-trail map of its PMF, the power sampler's alias table.  Built on the host with the renderer.
-constexpr int kMaxLights = VSPG_MAX_QUADS + VSPG_MAX_INFINITE_LIGHTS;
+// The light list: the emissive rectangles in rectangle order, then the infinite lights, then the point and spot lights.
+constexpr int kMaxLights = VSPG_MAX_QUADS + VSPG_MAX_INFINITE_LIGHTS + VSPG_MAX_POINT_LIGHTS;
 struct DLightNode {
     float bmin[3], bmax[3], w[3];
     float phi, cosTheta_o, cosTheta_e;
@@ -746,6 +747,16 @@ struct DEnvLight {
     const float *cdf;      // res rows of res + 1
     const float *mfunc;    // res
     const float *mcdf;     // res + 1
+};
+// Point / spot light (vspg_pointlight.h): the position renderFromLight(0, 0, 0), I = scale * I multiplied out, rows 0..2 of mInv
+// (row-major, 3 x 4) and the SpotLight constructor's two cosines, all formed on the host.
+struct DPointLight {
+    int32_t type;  // VSPG_LIGHT_POINT | VSPG_LIGHT_SPOT
+    float pos[3];
+    float I[3];
+    float mi[12];
+    float cosFalloffEnd, cosFalloffStart;
+    float axis[3];  // host only: Normalize(renderFromLight(Vector3f(0, 0, 1))), the w of SpotLight::Bounds
 };
 struct DScene {
     int32_t n_quads, n_lights;
@@ -828,7 +839,13 @@ struct DScene {
     // image infinite lights: slot k describes infinite light k where inf_type[k] == VSPG_LIGHT_IMAGE_INFINITE.  Behind everything
     // else: no offset of the record the existing kernels read moves.
     DEnvLight env[VSPG_MAX_INFINITE_LIGHTS];
+    // point and spot lights: the last n_point entries of the light list.  Behind the image lights: the kernels of scenes without
+    // them (kSimpleScene instantiations above all) read nothing here, and no field in front of lsamp moves.
+    int32_t n_point;
+    DPointLight point[VSPG_MAX_POINT_LIGHTS];
 };
+static_assert(offsetof(DScene, lsamp) == 5556,
+              "the light sampler's offset as it was before point lights enlarged it (printed from that commit): every field in front of it stays where the rectangle-scene kernels read it");
 static_assert(offsetof(DScene, planes) + sizeof(RectPlanes) <= 4096 && offsetof(DScene, shard_count) < 4096,
               "the fields the path loops read, the plane table among them, lie in the first 4 KB of DScene (scalar loads with no base register of their own)");
 // DScene::has_boundaries as the path code reads it.  (-DVSPG_NO_BOUNDARIES: a diagnostic build without the boundary code, to price

@@ -87,6 +87,7 @@ struct LightLi {
     V3 nLight;
 };
 #include "vspg_envlight.h"  // the image infinite light: env_Le / env_sample_li / env_pdf_li (fills a LightLi)
+#include "vspg_pointlight.h"  // point and spot lights: point_sample_li / spot_sample_li (fill a LightLi)
 VDEV bool light_sample_li(const DQuad &q, V3 ctxp, float u0, float u1, LightLi *ls) {
     V3 p00 = ld3(q.p00), p10 = ld3(q.p10), p01 = ld3(q.p01), p11 = ld3(q.p11);
     V3 pu0 = lerp(u1, p00, p01), pu1 = lerp(u1, p10, p11);
@@ -122,6 +123,11 @@ VDEV bool sample_light(const DScene &S, int lightIndex, V3 ctxp, float u0, float
     *delta_light = false;
     if (!FULL || lightIndex < S.n_lights) return light_sample_li(light_quad_at(lightIndex), ctxp, u0, u1, ls);
     const int k = lightIndex - S.n_lights;
+    if (k >= S.n_inf) {  // the third range of the light list: PointLight / SpotLight::SampleLi (vspg_pointlight.h)
+        const DPointLight &P = S.point[k - S.n_inf];
+        *delta_light = true;
+        return P.type == VSPG_LIGHT_SPOT ? spot_sample_li(P, ctxp, ls) : point_sample_li(P, ctxp, ls);
+    }
     if (S.inf_type[k] == VSPG_LIGHT_IMAGE_INFINITE) {  // ImageInfiniteLight::SampleLi (lights.h:650-674); `!ls->L || ls->pdf == 0` of :1167
         if (!env_sample_li(S, k, ctxp, u0, u1, ls)) return false;
         return nonzero(ls->L) && ls->pdf != 0;
@@ -393,10 +399,10 @@ VDEV Spec sample_Ld(const DScene &S, const Medium &medium, const Intr &intr, con
     V3 ctxp = intr.pi.mid();
     if (intr.is_surface && bsdf->has_lobes) ctxp = offset_ray_origin(intr.pi, intr.n, intr.wo);  // :1147-1149
     float u = sampler.get1d();
-    // lightSampler.Sample(ctx, u) (:1157) over the emissive rectangles followed by the infinite lights: UniformLightSampler
+    // lightSampler.Sample(ctx, u) (:1157) over the emissive rectangles, the infinite lights, then the point lights: UniformLightSampler
     // (lightsamplers.h:33-38) inline; the power / BVH samplers of multi-light scenes (vspg_lightsampler.h) in the full-scene kernels
     constexpr bool kFull = !Medium::kSimpleScene;
-    const int n_all = kFull ? S.n_lights + S.n_inf : S.n_lights;
+    const int n_all = kFull ? S.n_lights + S.n_inf + S.n_point : S.n_lights;
     bool have_light = n_all > 0;
     int lightIndex = 0;
     float lightPmf = 0;
@@ -753,7 +759,7 @@ VDEV int li_surface_pre(const DScene &S, PathState &st, IsgSample &isg, PC &pc, 
     VSPG_PROF(PS_SURF_PRE);
     if constexpr (kRec) pc.rec.add_transmittance_weight(tw);  // :350
     if (!si.hit) {  // :353-374: infinite light sources (this fork lists DeltaDirection lights among them, integrators.h:79)
-        const int n_all = S.n_lights + S.n_inf;
+        const int n_all = S.n_lights + S.n_inf + S.n_point;
         for (int k = 0; FULL && k < S.n_inf; ++k) {
             const bool image = S.inf_type[k] == VSPG_LIGHT_IMAGE_INFINITE;
             // UniformInfiniteLight::Le / DistantLight::Le (lights.cpp:1014-1017, lights.h:291-293) / ImageInfiniteLight::Le (lights.h:643-647)
@@ -791,7 +797,7 @@ VDEV int li_surface_pre(const DScene &S, PathState &st, IsgSample &isg, PC &pc, 
         } else {
             const LsCtx pctx = st.prevCtx.template expand<FULL>(S);
             const float pmf = FULL && S.lsamp.mode != VSPG_LIGHTSAMPLER_UNIFORM ? light_sampler_pmf(S, pctx.pi.mid(), pctx.n, S.lsamp.light_of_quad[si.quad])
-                                                                                 : wrcp((float)(FULL ? S.n_lights + S.n_inf : S.n_lights));
+                                                                                 : wrcp((float)(FULL ? S.n_lights + S.n_inf + S.n_point : S.n_lights));
             float lightPDF = pmf * (FULL ? light_pdf_li(q, pctx, st.rd) : light_pdf_li_hit(q, pctx, st.rd, si.p));
             st.r_l = st.r_l * lightPDF;
             float w_l = S.prm.usenee ? wrcp(avg(st.r_u + st.r_l)) : 1.0f;

@@ -477,7 +477,7 @@ VDEV ShadowSetup sample_Ld_begin(const DScene &S, const Medium &medium, int ch, 
     V3 ctxp = intr.pi.mid();
     if (intr.is_surface && bsdf->has_lobes) ctxp = offset_ray_origin(intr.pi, intr.n, intr.wo);  // :1147-1149
     float u = sampler.get1d();
-    const int n_all = S.n_lights + S.n_inf;
+    const int n_all = S.n_lights + S.n_inf + S.n_point;
     bool have_light = n_all > 0;
     int lightIndex = 0;
     float lightPmf = 0;

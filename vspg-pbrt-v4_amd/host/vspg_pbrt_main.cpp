@@ -73,6 +73,11 @@ int main(int argc, char **argv) {
             mseImage = vspg::LoadMseReferenceImage(mseImagePath, sd->xres, sd->yres, sd->boundsX0, sd->boundsY0, sd->boundsX1, sd->boundsY1);
             std::printf("MSE reference image: %s\n", mseImagePath.c_str());
         }
+        for (int i = 0; i < sd->scene.n_point_lights; ++i) {  // one line per point light: position (renderFromLight's translation) and I, %.9g round-trips a float
+            const VspgPointLight &pl = sd->scene.point_lights[i];
+            std::printf("point light %d: type %d at (%.9g, %.9g, %.9g) I (%.9g, %.9g, %.9g)\n", i, pl.type, pl.render_from_light[3], pl.render_from_light[7],
+                        pl.render_from_light[11], pl.I[0], pl.I[1], pl.I[2]);
+        }
         if (parseOnly) return 0;
         auto integrator = vspg::CreateIntegrator(*sd, device);
         std::printf("%s\n", integrator->ToString().c_str());

@@ -337,7 +337,36 @@ class Parser {
         p.ReportUnused();
         std::memcpy(gs.Kd, kd, sizeof kd);
     }
+    // LightSource "point" (PointLight::Create, lights.cpp:224-248): I, scale, power, from under the current CTM.  Under
+    // PBRT_RGB_RENDERING SpectrumToPhotometric is 1 (util/spectrum.cpp:48-49), so the record's I is I * scale with `power` folded into
+    // the scale as Create does.  The transform is the library's (vspg_point_light_at): ctm * Translate(from).
+    void point_light(ParameterDictionary &p) {
+        if (sd->scene.n_point_lights >= VSPG_MAX_POINT_LIGHTS) fail("too many point lights");
+        VspgPointLight &pl = sd->scene.point_lights[sd->scene.n_point_lights];
+        std::memset(&pl, 0, sizeof pl);
+        pl.type = VSPG_LIGHT_POINT;
+        float I[3] = {1, 1, 1}, from[3] = {0, 0, 0};
+        p.GetOneRGB("I", I);
+        float sc = p.GetOneFloat("scale", 1.f);
+        const float phi_v = p.GetOneFloat("power", -1.f);
+        if (phi_v > 0) {
+            const float k_e = 4 * 3.14159265358979323846f;
+            sc *= phi_v / k_e;
+        }
+        p.GetOnePoint3("from", from);
+        p.ReportUnused();
+        for (int k = 0; k < 3; ++k) pl.I[k] = I[k] * sc;
+        float ctm[16];
+        for (int i = 0; i < 4; ++i)
+            for (int j = 0; j < 4; ++j) ctm[4 * i + j] = gs.ctm.m[i][j];
+        if (vspg_point_light_at(&pl, from, ctm) != 0) fail(std::string("LightSource \"point\": ") + vspg_last_error());
+        sd->scene.n_point_lights++;
+    }
     void light_source(const std::string &type, ParameterDictionary &p) {
+        if (type == "point") { point_light(p); return; }
+        // (The library, its binding and vspg_spot_light_look_at carry everything a "spot" needs; the reader does not accept it yet.)
+        if (type == "spot")
+            fail("LightSource \"spot\": not read from scene files yet -- build the scene through the C-ABI (VspgScene.point_lights, vspg_spot_light_look_at)");
         if (sd->scene.n_infinite_lights >= VSPG_MAX_INFINITE_LIGHTS) fail("too many infinite lights");
         VspgInfiniteLight &il = sd->scene.infinite_lights[sd->scene.n_infinite_lights];
         float L[3] = {1, 1, 1};
@@ -390,7 +419,7 @@ class Parser {
             for (int k = 0; k < 3; ++k) il.w_light[k] = wr[k] / l;
             il.type = VSPG_LIGHT_DISTANT;
         } else {
-            fail("LightSource \"" + type + "\": only \"infinite\" (uniform) and \"distant\" are inside this build's scope");
+            fail("LightSource \"" + type + "\": only \"infinite\", \"distant\" and \"point\" are inside this build's scope");
         }
         p.ReportUnused();
         for (int k = 0; k < 3; ++k) il.L[k] = L[k] * sc;

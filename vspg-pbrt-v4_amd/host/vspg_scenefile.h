@@ -12,7 +12,9 @@
 // Identity, Translate, Scale, Rotate, Transform, ConcatTransform, ReverseOrientation, Material "diffuse" (reflectance) / "interface",
 // MakeNamedMaterial / NamedMaterial ("diffuse", "interface"), AreaLightSource "diffuse" (L, scale, twosided), LightSource "infinite"
 // (L, scale; or "filename": an equal-area octahedral environment map, .exr / .pfm, square, with R, G, B -- the CTM in effect is the
-// light's transform; no "portal", no "illuminance") / "distant" (L, scale, from, to), MakeNamedMedium ("homogeneous", "uniformgrid"), MediumInterface,
+// light's transform; no "portal", no "illuminance") / "distant" (L, scale, from, to) / "point" (I, scale, power, from under the CTM: a
+// VspgPointLight filled by vspg_point_light_at; LightSource "spot" is still REFUSED by name here -- the library, its binding and
+// vspg_spot_light_look_at carry everything it needs, the reader's few lines are a follow-up), MakeNamedMedium ("homogeneous", "uniformgrid"), MediumInterface,
 // Include (as a directive, and -- beyond pbrt -- inside a parameter list, for the block the reference's nanovdb2pbrt prints),
 // Shape "bilinearmesh" (one patch: a parallelogram becomes a rectangle, anything else two triangles) / "trianglemesh"
 // (P, indices) / "sphere" (radius; full spheres).  Anything else is an Error naming the directive: nothing is silently dropped.
