@@ -1,5 +1,5 @@
 """A plain NumPy statement of the device layout of a grid medium's density ("octet bricks"), written from the description
-in csrc/vspg_capi.hip / csrc/vspg_device.h / include/vspg.h and not from the builder kernels:
+in csrc/vspg_capi.hip / csrc/vspg_probe_kernels.h / csrc/vspg_device.h / include/vspg.h and not from the builder kernels:
 
   * the octet of base voxel (ix, iy, iz), -1 <= i <= n - 1 per axis, is the eight raw values at (ix + dx, iy + dy, iz + dz),
     corner number dx + 2 dy + 4 dz, zero outside the grid: what one trilinear lookup reads;

@@ -1,4 +1,4 @@
-"""A NumPy mirror of ONE guiding-field update (Field::Update: csrc/vspg_capi.hip k_train_*, oracle/vspg_oracle.c field_update_one).
+"""A NumPy mirror of ONE guiding-field update (Field::Update: csrc/vspg_train_kernels.h k_train_*, oracle/vspg_oracle.c field_update_one).
 
 The update consists of sums over the samples (position statistics, E-step statistics) and of plain float32 arithmetic on
 those sums (decay, +=, the split decision, the halving, the pivot division, the M-step).  The mirror does the second kind --

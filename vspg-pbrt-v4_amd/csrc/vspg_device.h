@@ -708,7 +708,7 @@ struct DSphere {
     float Kd[3];
     int32_t flip, has_lobes, flags;
 };
-// Four-wide BVH (round 5; own builder in vspg_capi.hip: binned SAH over triangles, then every inner node absorbs the children of
+// Four-wide BVH (round 5; own builder in vspg_scene_build.hip: binned SAH over triangles, then every inner node absorbs the children of
 // its largest children until it has four).  A node is the BOXES OF ITS CHILDREN, structure-of-arrays -- one 128-byte fetch tests
 // four boxes, and a ray makes half as many dependent fetches on its way down as through the binary tree of rounds 1-4 -- plus
 // what each child is: >= 0 an inner node's index, < 0 a leaf -(first triangle * 8 + count) - 1 (count 1..7), kBvhAbsent: no child.

@@ -1,7 +1,7 @@
 // vspg_lightsampler.h -- PowerLightSampler / BVHLightSampler (src/pbrt/lightsamplers.h:63-98, 100-430; round 3).
 //
 // "bvh" is the reference's default light sampler (guidedvolpathvspgintegrator.cpp:1318).  The tree is built once per renderer on
-// the host (vspg_capi.hip: lsb::build, the reference's buildBVH restated) over the light list {emissive rectangles in rectangle
+// the host (vspg_scene_build.hip: lsb::build, the reference's buildBVH restated) over the light list {emissive rectangles in rectangle
 // order, then the infinite lights, then the point and spot lights -- bounded lights like the rectangles: they enter the tree}; a
 // node record keeps what CompactLightBounds' accessors return -- the box, the cosines and the axis after their round trip through
 // the 16-bit / 15-bit / octahedral quantisation -- so the device does the float arithmetic of CompactLightBounds::Importance on

@@ -1,0 +1,66 @@
+// vspg_scene_build.h -- host-side scene preprocessing: what vspg_renderer_create and the update entry points derive from a
+// VspgScene before anything is uploaded.  Host code only (vspg_scene_build.hip): no kernel, no HIP call, no renderer.  Built with
+// the kernels' flags (-ffp-contract=off -fno-fast-math): the floats computed here are the ones the kernels consume bit for bit.
+#pragma once
+#include <vector>
+
+#include "vspg_device.h"
+#include "vspg_lightsampler.h"
+
+#pragma GCC visibility push(hidden)  // shared between the library's units, not part of its ABI
+namespace vspg_host {
+using namespace vspg;
+
+// ---- host float helpers for scene preprocessing (same formulas as the kernels use) ----
+namespace hostmath {
+struct H3 { float x, y, z; };
+static H3 ld(const float *p) { return H3{p[0], p[1], p[2]}; }
+static void stv(float *d, H3 v) { d[0] = v.x; d[1] = v.y; d[2] = v.z; }
+static H3 add(H3 a, H3 b) { return H3{a.x + b.x, a.y + b.y, a.z + b.z}; }
+static H3 absv(H3 a) { return H3{std::fabs(a.x), std::fabs(a.y), std::fabs(a.z)}; }
+static float dop(float a, float b, float c, float d) {
+    float cd = c * d;
+    float r = std::fmaf(a, b, -cd);
+    float e = std::fmaf(-c, d, cd);
+    return r + e;
+}
+static H3 crossv(H3 v, H3 w) { return H3{dop(v.y, w.z, v.z, w.y), dop(v.z, w.x, v.x, w.z), dop(v.x, w.y, v.y, w.x)}; }
+static float len2v(H3 a) { return a.x * a.x + a.y * a.y + a.z * a.z; }
+static H3 normv(H3 a) { float l = std::sqrt(len2v(a)); return H3{a.x / l, a.y / l, a.z / l}; }
+}  // namespace hostmath
+
+// 0, or VSPG_EINVAL with the message set (vspg_error.h)
+int validate(const VspgScene *scene, const VspgIntegratorParams *p, const VspgRenderConfig *cfg);
+// everything of the device scene that needs no device memory, light sampler included
+void build_dscene(const VspgScene &sc, const VspgIntegratorParams &prm, const VspgRenderConfig &cfg, DScene *D);
+namespace lsb {
+void build(const VspgScene &sc, const VspgIntegratorParams &prm, DScene *D);  // the light sampler alone (a light's power changed)
+}
+PcgJump pcg_jump(unsigned long long delta);
+bool wants_guiding(const VspgIntegratorParams &p);
+bool wants_training(const VspgIntegratorParams &p);
+
+// false: a degenerate triangle, which no ray hits
+bool derive_triangle(const float *p9, const float *kd, int id, DTri *T, const int32_t *flags = nullptr);
+// The triangle soup as the kernels read it: the accepted triangles in leaf order and the four-wide BVH over them (both empty when no
+// triangle is accepted).  0, or VSPG_ESCOPE when even median splits leave the tree too deep for the traversal's stack (kBvhStack).
+int build_triangle_bvh(const VspgScene &sc, std::vector<DTri> *tris, std::vector<DBvh4Node> *nodes);
+
+int majorant_res(const VspgMedium &m);
+std::vector<int2> majorant_axis_ranges(const VspgMedium &m);
+std::vector<float> build_majorant_grid(const VspgMedium &m);
+std::vector<float> build_majorant_grid_nvdb(const VspgMedium &m);
+
+// ---- image infinite light: the host side of vspg_envlight.h ----------------------------------------------------------------
+// The arrays of one DEnvLight, laid out in one buffer: texels | func | cdf | mfunc | mcdf
+struct EnvTables {
+    int res = 0;
+    float integral = 0.f, sum_L[3] = {0.f, 0.f, 0.f};
+    std::vector<float> buf;
+    size_t o_func = 0, o_cdf = 0, o_mfunc = 0, o_mcdf = 0;
+};
+void env_build_tables(const float *rgb, int res, EnvTables *T);
+bool env_matrices(const float *m34, float *m, float *mi);
+
+}  // namespace vspg_host
+#pragma GCC visibility pop

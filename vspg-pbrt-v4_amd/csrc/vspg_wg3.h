@@ -24,7 +24,7 @@
 // Termination: the tile head has run dry and no slot holds a path (`live`, raised by 64 BEFORE a tile is claimed).
 //
 // Per path nothing changes: the operations, their order and the sampler dimensions are li_segment_a's and li_segment_b's, a
-// finished path parks {L, ISG code} exactly as under k_render_wave_wg2 (deferred resolve, vspg_capi.hip): the three schedulers
+// finished path parks {L, ISG code} exactly as under k_render_wave_wg2 (deferred resolve, vspg_wg_sched.h): the three schedulers
 // give the same film bit for bit (tests: test_workgroup_schedulers_are_bit_identical).
 #pragma once
 #include <type_traits>
