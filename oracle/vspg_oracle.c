@@ -932,7 +932,10 @@ static int tri_intersect(v3 o, v3 d, float tMax, v3 p0, v3 p1, v3 p2, float *t_o
 /* closest hit (stands in for Integrator::Intersect -> BVHAggregate::Intersect, integrators.cpp:341-349, cpu/aggregates.cpp:529-590):
  * rectangles first, then EVERY triangle against the rectangles' closest distance (brute force: no BVH on this side);
  * equal distances go to the smaller triangle index -- the device's BVH traversal applies the same rule, so the visiting
- * order never matters.  (The reference's traversal lets the LAST visited of equal distances win: ties are measure-zero.) */
+ * order never matters.  (The reference's traversal lets the LAST visited of equal distances win: ties are measure-zero.)
+ * The reference's own slab test is no guide on rays that run along a box face with a zero direction component (0 * inf = NaN in
+ * Bounds3::IntersectP with dirIsNeg, util/vecmath.h:1574-1608: it drops the node when the NaN sits in the x slab and keeps it for y
+ * and z), so the contract of the device's traversal is this loop: brute force (tests/test_bvh_traverse_bits.py, _gpu.py). */
 static isect_t scene_intersect(const OracleRenderer *r, v3 o, v3 d, float tMax) {
     isect_t best;
     memset(&best, 0, sizeof best);

@@ -1207,16 +1207,27 @@ VDEV bool tri_intersect(V3 o, const TriRay &R, float tMax, V3 p0, V3 p1, V3 p2, 
 }
 // slab test for the traversal only: a conservative SUPERSET test (every triangle whose hit distance is <= tLimit lies in a
 // box this accepts), so which boxes are visited never changes a result.  *t_near: where the ray enters the box.
+// One slab: a, b are the distances to its two planes.  A NaN in ONE of them (0 * inf: d = +-0 along this axis and the origin on that
+// plane, so the ray runs along a face of the box) says nothing about the interval, and the slab must leave it alone.  fmin_ / fmax_
+// do not: they are not symmetric in a NaN operand -- with the NaN on the upper plane (a = -+inf, b = NaN) they give t1 = -inf or
+// t0 = +inf, and a ray along the upper face of a box lost every triangle in it.  Two NaNs (a flat box, a NaN origin) they ignore.
+// GUARD = true skips such a slab; it costs a compare and two selects per slab (+5.5 % per wave on the terrain scenes when every
+// ray pays it, profiles/bvh_slab_nan_ab.txt), and only a ray with an infinite 1 / d can need it, so the traversal asks that once
+// per ray and every other lane takes the slabs unguarded.  Held to brute force by tests/test_bvh_traverse_bits.py.
+template <bool GUARD> struct BvhGuard { static constexpr bool value = GUARD; };
+template <bool GUARD>
+VDEV void bvh_slab(float a, float b, float *t0, float *t1) {
+    if (GUARD && __builtin_isunordered(a, b)) return;
+    *t0 = fmax_(*t0, fmin_(a, b)); *t1 = fmin_(*t1, fmax_(a, b) * 1.00001f);
+}
+template <bool GUARD>
 VDEV bool bvh_box_hit(float lox, float loy, float loz, float hix, float hiy, float hiz, V3 o, V3 inv, float tLimit, float *t_near) {
     float t0 = 0.f, t1 = tLimit;
-    float a = (lox - o.x) * inv.x, b = (hix - o.x) * inv.x;
-    t0 = fmax_(t0, fmin_(a, b)); t1 = fmin_(t1, fmax_(a, b) * 1.00001f);
-    a = (loy - o.y) * inv.y; b = (hiy - o.y) * inv.y;
-    t0 = fmax_(t0, fmin_(a, b)); t1 = fmin_(t1, fmax_(a, b) * 1.00001f);
-    a = (loz - o.z) * inv.z; b = (hiz - o.z) * inv.z;
-    t0 = fmax_(t0, fmin_(a, b)); t1 = fmin_(t1, fmax_(a, b) * 1.00001f);
+    bvh_slab<GUARD>((lox - o.x) * inv.x, (hix - o.x) * inv.x, &t0, &t1);
+    bvh_slab<GUARD>((loy - o.y) * inv.y, (hiy - o.y) * inv.y, &t0, &t1);
+    bvh_slab<GUARD>((loz - o.z) * inv.z, (hiz - o.z) * inv.z, &t0, &t1);
     *t_near = t0;
-    return !(t0 > t1);  // NaN (0 * inf on a slab boundary) keeps the node
+    return !(t0 > t1);  // (a NaN tLimit keeps the node)
 }
 // One traversal for both queries.  ANY = false: the closest triangle hit with distance < tMax -- every triangle is tested against
 // the RAY's tMax (never against the running closest distance: the test's acceptance would then depend on the visiting order),
@@ -1227,6 +1238,9 @@ VDEV bool bvh_box_hit(float lox, float loy, float loz, float hix, float hiy, flo
 template <bool ANY>
 VDEV bool bvh_traverse(const DScene &S, V3 o, V3 d, float tMax, int *tri_pos, TriHit *best) {
     const V3 inv = V3{1 / d.x, 1 / d.y, 1 / d.z};
+    // only a ray with a zero (or denormal) direction component can run along a box face (0 * inf): the guarded slabs are for it alone,
+    // chosen per node by one branch on this loop-invariant flag -- a wavefront without such a lane skips them
+    const bool axis_parallel = __builtin_isinf(inv.x) | __builtin_isinf(inv.y) | __builtin_isinf(inv.z);
     const TriRay R = tri_ray(d);
     int st_ref[kBvhStack];
     float st_t[ANY ? 1 : kBvhStack];
@@ -1241,11 +1255,14 @@ VDEV bool bvh_traverse(const DScene &S, V3 o, V3 d, float tMax, int *tri_pos, Tr
             const float4 *nd = reinterpret_cast<const float4 *>(S.bvh + ref);
             const float4 lox = nd[0], loy = nd[1], loz = nd[2], hix = nd[3], hiy = nd[4], hiz = nd[5];
             const int4 ch = *reinterpret_cast<const int4 *>(nd + 6);
-            const float lim = !ANY && found ? limit * 1.00001f : limit;  // cull with slack: the box may touch the triangle exactly where it is hit
+            // cull with slack: the box may touch the triangle exactly where it is hit, and the slab's distance to that face and the
+            // triangle test's t round differently -- against the ray's tMax as much as against the closest hit so far (a flat box hit
+            // at t three floats below its entry distance, tMax between the two: the node was dropped and the hit lost)
+            const float lim = limit * 1.00001f;
             float next_t = kInf;
-            const auto child = [&](float bx0, float by0, float bz0, float bx1, float by1, float bz1, int c) {
+            const auto child = [&](auto guard, float bx0, float by0, float bz0, float bx1, float by1, float bz1, int c) {
                 float tn;
-                if (c != kBvhAbsent && bvh_box_hit(bx0, by0, bz0, bx1, by1, bz1, o, inv, lim, &tn)) {
+                if (c != kBvhAbsent && bvh_box_hit<decltype(guard)::value>(bx0, by0, bz0, bx1, by1, bz1, o, inv, lim, &tn)) {
                     int push = c;
                     float push_t = tn;
                     if (tn < next_t || next == kBvhAbsent) {  // the nearest hit child is visited next, the others wait
@@ -1259,10 +1276,13 @@ VDEV bool bvh_traverse(const DScene &S, V3 o, V3 d, float tMax, int *tri_pos, Tr
                     }
                 }
             };
-            child(lox.x, loy.x, loz.x, hix.x, hiy.x, hiz.x, ch.x);
-            child(lox.y, loy.y, loz.y, hix.y, hiy.y, hiz.y, ch.y);
-            child(lox.z, loy.z, loz.z, hix.z, hiy.z, hiz.z, ch.z);
-            child(lox.w, loy.w, loz.w, hix.w, hiy.w, hiz.w, ch.w);
+            const auto children = [&](auto guard) {
+                child(guard, lox.x, loy.x, loz.x, hix.x, hiy.x, hiz.x, ch.x);
+                child(guard, lox.y, loy.y, loz.y, hix.y, hiy.y, hiz.y, ch.y);
+                child(guard, lox.z, loy.z, loz.z, hix.z, hiy.z, hiz.z, ch.z);
+                child(guard, lox.w, loy.w, loz.w, hix.w, hiy.w, hiz.w, ch.w);
+            };
+            if (axis_parallel) children(BvhGuard<true>{}); else children(BvhGuard<false>{});
         } else {
             const int leaf = -ref - 1, first = leaf >> 3, cnt = leaf & 7;
             for (int k = 0; k < cnt; ++k) {
@@ -1284,7 +1304,7 @@ VDEV bool bvh_traverse(const DScene &S, V3 o, V3 d, float tMax, int *tri_pos, Tr
         while (next == kBvhAbsent) {
             if (sp == 0) return found;
             --sp;
-            if (ANY || !(st_t[sp] > (found ? limit * 1.00001f : limit))) next = st_ref[sp];
+            if (ANY || !(st_t[sp] > limit * 1.00001f)) next = st_ref[sp];
         }
         ref = next;
     }
