@@ -576,11 +576,12 @@ enum { SURF_INTERFACE = 1, SURF_IFACE_SHIFT = 1 };
 // on the same operands, the caller trades the two results back.  The records are walked in index order from the scene frame, so
 // each one also says how many cyclic steps (x,y,z) <- (y,z,x) lead from its predecessor's frame to its own (0..2).
 // `axes` also repeats the kind (kIsectAxisAligned): the one scalar the walk waits for before it can turn the ray and branch.
-enum { kIsectStepsMask = 3, kIsectUvSwapped = 4, kIsectAxisAligned = 8, kIsectAxisShift = 4 };
+enum { kIsectStepsMask = 3, kIsectUvSwapped = 4, kIsectAxisAligned = 8, kIsectAxisShift = 4, kIsectTwin = 64, kIsectTwinSwapped = 128 };
 struct IsectRec {
     float f[14];
     int32_t kind;   // 0 generic, 1 axis-aligned
     int32_t axes;   // steps from the previous record's frame | kIsectUvSwapped | kIsectAxisAligned | frame axis << kIsectAxisShift
+                    // | kIsectTwin | kIsectTwinSwapped (rect_twins_mark; every reader of the frame axis masks it with & 3)
 };
 // The record of one rectangle, from what build_dscene derives; `cur` is the frame axis of the record before it (0 for the first),
 // the return value this record's.  Host code (tests/test_rect_frame_bits.py compiles it stand-alone).
@@ -653,6 +654,25 @@ inline void rect_planes_build(RectPlanes *T, const IsectRec *recs, int n) {
             T->always |= 1u << pos;
             place(pos++, i);
         }
+}
+// Twin records, for the closest-hit walk (rects_closest_twins): two axis-aligned records in a row on the same frame axis whose in-plane
+// fields f[2..7] are the same bits -- two opposite walls of a box, which isect_rec_build's cyclic (u along a+1, v along a+2) order
+// stores alike whichever way their edges run -- differ in the plane coordinate f[1], the unused f[0] and kIsectUvSwapped only.  The
+// FIRST record of such a pair gets kIsectTwin, its partner's swapped bit as kIsectTwinSwapped and its partner's plane coordinate in
+// f[8] (f[8..13] are unused by axis-aligned records); the second stays complete and unchanged, and no record moves: index order
+// decides ties and is the reported rectangle.  A record belongs to one pair at most.  Host code, behind isect_rec_build wherever
+// records are built for the kernels; marking twice changes nothing.
+inline void rect_twins_mark(IsectRec *recs, int n) {
+    for (int i = 0; i + 1 < n; ++i) {
+        IsectRec &a = recs[i];
+        const IsectRec &b = recs[i + 1];
+        if (a.axes & kIsectTwin) { ++i; continue; }   // marked before: b is taken
+        if (!(a.axes & kIsectAxisAligned) || !(b.axes & kIsectAxisAligned) || (b.axes & (kIsectStepsMask | kIsectTwin))) continue;
+        if ((((a.axes ^ b.axes) >> kIsectAxisShift) & 3) || __builtin_memcmp(&a.f[2], &b.f[2], 6 * sizeof(float)) != 0) continue;
+        a.axes |= kIsectTwin | ((b.axes & kIsectUvSwapped) ? kIsectTwinSwapped : 0);
+        a.f[8] = b.f[1];
+        ++i;
+    }
 }
 // guiding field in HBM (see vspg_guiding.h): [0] surface, [1] volume; nodes == nullptr -> untrained
 struct DField {
@@ -1030,6 +1050,105 @@ VDEV bool rects_closest(const IsectRec *recs, int n, V3 o, V3 d, float tMax, flo
         bi = h ? i : bi;
         bu = h ? (swapped ? v : u) : bu;
         bv = h ? (swapped ? u : v) : bv;
+    }
+    *tBest = bt;
+    *iBest = bi;
+    *uBest = bu;
+    *vBest = bv;
+    return hit;
+}
+// rects_closest with the two walls of a twin pair (rect_twins_mark) tested in one pass (the kernels call this one; rects_closest above
+// is the plain walk it has to equal, record for record, in all five results).  Inside a box a ray moves towards exactly one wall of
+// each opposite pair, so on an incoherent wavefront both bodies of a pair ran at half lane use; one body serves both walls, since all
+// it reads past the plane coordinate is the same bits in both records.
+//   A record without kIsectTwin: the plain iteration.  With it, behind one wave-uniform branch: numA = f[1] - o.x, numB = f[8] - o.x
+// and the two pre-test masks candA, candB formed as rect_hit_uv forms `cand`, with the running bt at entry.  One vote on
+// candA & candB: if some lane is a candidate of BOTH planes (an origin outside the slab or on a plane, zeros and NaNs of equal sign)
+// the wavefront drops the pair's treatment and runs the plain iteration for this record, and the next one -- which carries no bit --
+// follows by itself.  Otherwise no lane is a candidate of both: sel = candB, num = sel ? numB : numA, cand = candA | candB, one vote,
+// one division, one (u, v) and range test, the winner's index i + sel and its (u, v) order from the selected wall's swapped bit; then
+// on to i + 2.
+//   Why every bit stays: an accepted lane divides the same num by the same denom and reads the same in-plane fields as in the plain
+// walk.  A lane that is a candidate of B only met nothing at A (cand is necessary for a hit), so its bt at B is the one at entry.  A
+// lane that is a candidate of A only is no candidate of B after A either: beyond() is monotone in tMax and bt only shrinks, and the
+// sign test does not read bt.  Order within the pair and against the other records is the index order, so the first record keeps
+// winning equal distances, at edges and corners too.  The votes never change a lane's values, and the fallback is the plain walk.
+//   The host's votes: the lane itself; with VSPG_RECT_TWIN_VOTE == 1 the `some` vote is always taken (a lane beside a candidate),
+// with VSPG_RECT_TWIN_VOTE == 2 the both-candidates vote is (every pair falls back).  VSPG_RECT_TWIN_VOTE and VSPG_RECT_TWIN_PATH (a
+// host statement per pair that names the path taken: 0 merged, 1 fallback) are for tests/test_rect_twins_bits.py alone; no device
+// build reads them.
+#if defined(__HIP_DEVICE_COMPILE__) || !defined(VSPG_RECT_TWIN_PATH)
+#undef VSPG_RECT_TWIN_PATH
+#define VSPG_RECT_TWIN_PATH(fallback)
+#endif
+// the body beside rect_hit_uv, for axis-aligned records: *second says per lane which wall the results belong to (false: this record),
+// *merged (wave-uniform) whether the next record was tested here too
+VDEV bool rect_hit_uv_twins(const IsectRec &r, V3 o, V3 d, float tMax, float *tHit, float *uHit, float *vHit, bool *second, bool *merged) {
+    const float denom = d.x;
+    float num = r.f[1] - o.x;
+    bool cand = (int32_t)(__builtin_bit_cast(uint32_t, num) ^ __builtin_bit_cast(uint32_t, denom)) >= 0;
+    cand = cand & !beyond(num, denom, tMax);
+    bool sel = false, two = false;
+    if (r.axes & kIsectTwin) {   // wave-uniform
+        const float numB = r.f[8] - o.x;
+        bool candB = (int32_t)(__builtin_bit_cast(uint32_t, numB) ^ __builtin_bit_cast(uint32_t, denom)) >= 0;
+        candB = candB & !beyond(numB, denom, tMax);
+#if defined(__HIP_DEVICE_COMPILE__)
+        const bool both = __builtin_amdgcn_ballot_w64(cand & candB) != 0ull;
+#elif VSPG_RECT_TWIN_VOTE == 2
+        const bool both = true;
+#else
+        const bool both = cand & candB;
+#endif
+        VSPG_RECT_TWIN_PATH(both);
+        if (!both) {   // wave-uniform
+            two = true;
+            sel = candB;
+            num = sel ? numB : num;
+            cand = cand | candB;
+        }
+    }
+    *second = sel;
+    *merged = two;
+#if defined(__HIP_DEVICE_COMPILE__)
+    const bool some = __builtin_amdgcn_ballot_w64(cand) != 0ull;
+#elif VSPG_RECT_TWIN_VOTE == 1
+    const bool some = true;
+#else
+    const bool some = cand;
+#endif
+    if (!some) return false;   // wave-uniform
+    const float t = num / denom;
+    cand = cand & (t > 0) & (t < tMax);
+    const float pu = o.y + d.y * t, pv = o.z + d.z * t;
+    const float u = ((pu - r.f[2]) * r.f[4]) * r.f[6];
+    const float v = ((pv - r.f[3]) * r.f[5]) * r.f[7];
+    cand = cand & !((u < 0) | (u > 1) | (v < 0) | (v > 1));   // a NaN u or v passes, as it always did
+    *tHit = t;
+    *uHit = u;
+    *vHit = v;
+    return cand;
+}
+VDEV bool rects_closest_twins(const IsectRec *recs, int n, V3 o, V3 d, float tMax, float *tBest, int *iBest, float *uBest, float *vBest) {
+    bool hit = false;
+    float bt = tMax, bu = 0, bv = 0;
+    int bi = 0;
+    V3 fo = o, fd = d;   // the ray in the current record's frame
+    for (int i = 0; i < n;) {
+        const IsectRec &r = recs[i];
+        float t, u, v;
+        bool second = false, merged = false, h;
+        rect_frame(fo, fd, r.axes);
+        if (r.axes & kIsectAxisAligned) h = rect_hit_uv_twins(r, fo, fd, bt, &t, &u, &v, &second, &merged);   // wave-uniform
+        else h = rect_hit_uv(r, fo, fd, bt, &t, &u, &v);
+        // the selected wall's swapped bit: a lane mask from `second` and two wave-uniform bits
+        const bool swapped = second ? (r.axes & kIsectTwinSwapped) != 0 : (r.axes & kIsectUvSwapped) != 0;
+        hit = hit | h;
+        bt = h ? t : bt;
+        bi = h ? i + (second ? 1 : 0) : bi;
+        bu = h ? (swapped ? v : u) : bu;
+        bv = h ? (swapped ? u : v) : bv;
+        i += merged ? 2 : 1;
     }
     *tBest = bt;
     *iBest = bi;
@@ -1446,7 +1565,7 @@ template <bool FULL = true>
 VLEAF Isect scene_intersect(const DScene &S, V3 o, V3 d, float tMax) {
     Isect best;
     float bu, bv;
-    best.hit = rects_closest(S.irec, S.n_quads, o, d, tMax, &best.t, &best.quad, &bu, &bv);
+    best.hit = rects_closest_twins(S.irec, S.n_quads, o, d, tMax, &best.t, &best.quad, &bu, &bv);
     const DQuad &q = quad_at(best.quad);  // per-lane index: LDS copy
     best.p = quad_point(q, bu, bv);
     best.n = ld3(q.n);

@@ -480,6 +480,7 @@ void build_dscene(const VspgScene &sc, const VspgIntegratorParams &prm, const Vs
         frame = isect_rec_build(&D->irec[i], q.n, q.p00, q.e1, q.e2, q.inv_l1, q.inv_l2, frame);
         if (light) D->light_quads[D->n_lights++] = i;
     }
+    rect_twins_mark(D->irec, D->n_quads);
     rect_planes_build(&D->planes, D->irec, D->n_quads);
     D->n_inf = sc.n_infinite_lights;
     for (int i = 0; i < sc.n_infinite_lights && i < VSPG_MAX_INFINITE_LIGHTS; ++i) {
