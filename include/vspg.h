@@ -75,7 +75,11 @@ typedef struct VspgQuad {
  * -- zmin / zmax / phimax -- are refused), placed by renderFromObject.  Both matrices of pbrt's Transform, row-major, as
  * for VspgMedium (vspg_transform_inverse fills the inverse).  Intersection = Sphere::BasicIntersect with its interval
  * arithmetic (shapes.h:147-229), interaction = InteractionFromIntersection + Transform::operator()(SurfaceInteraction)
- * (shapes.h:237-284, transform.cpp:229-261).  Diffuse or interface; not a light. */
+ * (shapes.h:237-284, transform.cpp:229-261).  Diffuse or interface.  A diffuse sphere becomes a DiffuseAreaLight through the tail of
+ * VspgScene (sphere_Le / sphere_two_sided, below): this record keeps its size, which sits inside VspgScene in front of fields whose
+ * offsets callers rely on.
+ * Matrices get no check beyond "affine": under a matrix with scale the light does what the reference does -- the cone branch of
+ * Sphere::Sample / PDF and Area() work with the object-space radius and ignore the scale (shapes.h:316-360). */
 #define VSPG_MAX_SPHERES 8
 typedef struct VspgSphere {
     float render_from_object[16];
@@ -226,9 +230,23 @@ typedef struct VspgScene {
      * recompiled against this header, and a caller that fills the record field by field zeroes it first (memset), which leaves
      * n_point_lights = 0.
      * The scene's LIGHT LIST, which every light sampler indexes, is: the emissive rectangles in rectangle order, then the infinite
-     * lights, then the point lights -- every index of a scene without point lights keeps its meaning. */
+     * lights, then the point lights (then the emissive spheres, below) -- every index of a scene without point lights keeps its
+     * meaning. */
     int32_t n_point_lights;
     VspgPointLight point_lights[VSPG_MAX_POINT_LIGHTS];
+    /* Sphere area lights (DiffuseAreaLight on Shape "sphere": lights.cpp:796-864, shapes.h:293-393).  THE RECORD GREW by this second
+     * tail in the same way (VSPG_ABI_VERSION stays 7); a zeroed record holds no sphere light.  Both arrays are indexed by sphere:
+     *   sphere_Le[i]         the radiance sphere i emits: the reference's `scale * L` multiplied out (RGB), the convention of VspgQuad.Le;
+     *                        all zero = not a light.  A component that is negative, NaN or infinite is VSPG_EINVAL.
+     *   sphere_two_sided[i]  DiffuseAreaLight "twosided": 0 = the side the normal points to emits (the outside, or the inside under
+     *                        reverse_orientation), 1 = both.  Any other value is VSPG_EINVAL.
+     * An emissive sphere whose material is VSPG_MATERIAL_INTERFACE is VSPG_ESCOPE: the reference allows it, the library does not, so
+     * that a shadow ray's end point never lies on a surface its chain of segments walks through.
+     * No image, no alpha, no SampleLe.
+     * The LIGHT LIST gains a fourth range: emissive rectangles, infinite lights, point lights, then the EMISSIVE SPHERES in sphere
+     * order -- every index of a scene without them keeps its meaning. */
+    float sphere_Le[VSPG_MAX_SPHERES][3];
+    int32_t sphere_two_sided[VSPG_MAX_SPHERES];
 } VspgScene;
 
 /* ---- integrator parameters: same names and defaults as
@@ -762,6 +780,19 @@ int vspg_envlight_batch(VspgRenderer *r, int infinite_light_index, int n, const 
 #define VSPG_LIGHT_SAMPLE_OUT 16
 int vspg_light_sample_batch(VspgRenderer *r, int n, const float *ctx_p /*3n*/, const float *ctx_n /*3n*/, const float *u /*3n*/,
                             float *out /*16n*/, void *stream);
+
+/* Batch driver of a light's PDF (parity tests): per element what the path kernels compute when a ray that leaves the context along
+ * wi is to be weighed against light `light_index` of the light list -- the light_sampler_pmf, the PDF_Li (light_pdf_li for a
+ * rectangle, sphere_pdf_li for a sphere), the intersection and the L the kernels call.  HOST arrays.
+ *   ctx_p     3n floats: the context point      ctx_perr  3n floats: its error bounds (Point3fi(p, pError)), NULL = exact points
+ *   ctx_n     3n floats: its normal, zeros = a medium vertex      wi  3n floats: the ray's direction (as given, not normalised here)
+ *   out       VSPG_LIGHT_PDF_OUT floats per element:
+ *   [0] PDF_Li(ctx, wi)   [1] lightSampler.PMF(ctx, light)   [2] 1 = the ray ctx.SpawnRay(wi) hits the light's shape, 0 = not
+ *   (everything after it is 0 then)   [3..5] L at the hit towards -wi   [6] the hit's distance along wi   [7] 0
+ * VSPG_EINVAL: light_index outside the light list, or an infinite or delta light (they have no shape to hit). */
+#define VSPG_LIGHT_PDF_OUT 8
+int vspg_light_pdf_batch(VspgRenderer *r, int light_index, int n, const float *ctx_p /*3n*/, const float *ctx_perr /*3n or NULL*/,
+                         const float *ctx_n /*3n*/, const float *wi /*3n*/, float *out /*8n*/, void *stream);
 
 #ifdef __cplusplus
 }

@@ -80,6 +80,7 @@ class VspgInfiniteLight(C.Structure):
 VSPG_MAX_POINT_LIGHTS = 8
 LIGHT_POINT, LIGHT_SPOT = 3, 4
 LIGHT_SAMPLE_OUT = 16  # VSPG_LIGHT_SAMPLE_OUT: floats per element of vspg_light_sample_batch
+LIGHT_PDF_OUT = 8      # VSPG_LIGHT_PDF_OUT: floats per element of vspg_light_pdf_batch
 
 
 class VspgPointLight(C.Structure):
@@ -94,7 +95,8 @@ class VspgScene(C.Structure):
                 ("n_infinite_lights", C.c_int32), ("infinite_lights", VspgInfiniteLight * VSPG_MAX_INFINITE_LIGHTS),
                 ("tri_flags", C.POINTER(C.c_int32)), ("n_spheres", C.c_int32), ("spheres", VspgSphere * VSPG_MAX_SPHERES),
                 ("camera_outside_medium", C.c_int32),
-                ("n_point_lights", C.c_int32), ("point_lights", VspgPointLight * VSPG_MAX_POINT_LIGHTS)]
+                ("n_point_lights", C.c_int32), ("point_lights", VspgPointLight * VSPG_MAX_POINT_LIGHTS),
+                ("sphere_Le", f3 * VSPG_MAX_SPHERES), ("sphere_two_sided", C.c_int32 * VSPG_MAX_SPHERES)]
 
 
 class VspgIntegratorParams(C.Structure):
@@ -307,6 +309,7 @@ SYMBOLS = [
     ("vspg_spot_light_look_at", C.c_int, [_P(VspgPointLight), f3, f3, _P(C.c_float)]),
     ("vspg_point_light_at", C.c_int, [_P(VspgPointLight), f3, _P(C.c_float)]),
     ("vspg_light_sample_batch", C.c_int, [_vp, C.c_int, _P(C.c_float), _P(C.c_float), _P(C.c_float), _P(C.c_float), _vp]),
+    ("vspg_light_pdf_batch", C.c_int, [_vp, C.c_int, C.c_int, _P(C.c_float), _P(C.c_float), _P(C.c_float), _P(C.c_float), _P(C.c_float), _vp]),
     ("vspg_renderer_get_tr_buffer", C.c_int, [_vp, _P(C.c_float), _P(C.c_int32), _vp]),
     ("vspg_renderer_set_tr_buffer", C.c_int, [_vp, _P(C.c_float), _vp]),
     ("vspg_renderer_set_guiding_field", C.c_int, [_vp, _P(VspgField), _P(VspgField), _vp]),
@@ -577,6 +580,28 @@ def add_spot_light(scene, I, from_, to, coneangle=30, conedelta=5, scale=1, powe
         return lib.vspg_spot_light_look_at(C.byref(l), f3(*[float(v) for v in from_]), f3(*[float(v) for v in to]), cp)
     keep, cp = _ctm_pointer(ctm)
     return _add_point_light(scene, LIGHT_SPOT, I, sc, fill)
+
+
+def add_sphere_light(scene, sphere_index, L, scale=1, two_sided=False, power=None):
+    """AreaLightSource "diffuse" on sphere `sphere_index` of the scene (DiffuseAreaLight::Create, lights.cpp:906-993): emitted radiance L
+    (RGB) times `scale`.  power > 0 rescales as Create does (lights.cpp:969-990): scale *= power / k_e with k_e = (two_sided ? 2 : 1) *
+    Area() * Pi, Area() = phiMax * radius * (zMax - zMin) in object space.  No photometric factor, as for the other lights here.
+    Returns the light's index among the scene's emissive spheres (so far)."""
+    import numpy as np
+    if not 0 <= sphere_index < scene.n_spheres:
+        raise ValueError("sphere_index %d outside the scene's %d spheres" % (sphere_index, scene.n_spheres))
+    f = np.float32
+    sc = f(scale)
+    if power is not None and power > 0:
+        r = f(scene.spheres[sphere_index].radius)
+        phi_max = (f(np.pi) / f(180)) * f(360)
+        area = (phi_max * r) * (r - (-r))
+        k_e = f(1) * (f(2 if two_sided else 1) * area * f(np.pi))
+        sc = sc * (f(power) / k_e)
+    for k in range(3):
+        scene.sphere_Le[sphere_index][k] = f(L[k]) * sc
+    scene.sphere_two_sided[sphere_index] = 1 if two_sided else 0
+    return sum(1 for i in range(sphere_index) if any(scene.sphere_Le[i][k] != 0 for k in range(3)))
 
 
 def set_triangles(scene, tri_p, tri_kd=None):
@@ -880,6 +905,22 @@ class Renderer:
         fp = C.POINTER(C.c_float)
         _check(self.lib, self.lib.vspg_light_sample_batch(self.h, p.shape[0], p.ctypes.data_as(fp), nn.ctypes.data_as(fp), uu.ctypes.data_as(fp),
                                                           out.ctypes.data_as(fp), None))
+        return out
+
+    def light_pdf_batch(self, light_index, ctx_p, ctx_n, wi, ctx_perr=None):
+        """Per context (point ctx_p, optional error bounds ctx_perr, normal ctx_n -- zeros = a medium vertex) and direction wi: what the path
+        kernels compute when the ray from the context along wi is weighed against light `light_index` (a rectangle or a sphere of the
+        light list; vspg_light_pdf_batch).  Returns an (n, LIGHT_PDF_OUT) float32 array: PDF_Li | PMF(ctx, light) | hit | L (3) | t | 0."""
+        import numpy as np
+        fp = C.POINTER(C.c_float)
+        arrs = [np.ascontiguousarray(np.asarray(a, dtype=np.float32).reshape(-1, 3)) for a in (ctx_p, ctx_n, wi)]
+        e = None if ctx_perr is None else np.ascontiguousarray(np.asarray(ctx_perr, dtype=np.float32).reshape(-1, 3))
+        n = arrs[0].shape[0]
+        if any(a.shape[0] != n for a in arrs) or (e is not None and e.shape[0] != n):
+            raise ValueError("light_pdf_batch: arrays of different lengths")
+        out = np.empty((n, LIGHT_PDF_OUT), dtype=np.float32)
+        _check(self.lib, self.lib.vspg_light_pdf_batch(self.h, int(light_index), n, arrs[0].ctypes.data_as(fp), None if e is None else e.ctypes.data_as(fp),
+                                                       arrs[1].ctypes.data_as(fp), arrs[2].ctypes.data_as(fp), out.ctypes.data_as(fp), None))
         return out
 
     def counters(self, stream=None):

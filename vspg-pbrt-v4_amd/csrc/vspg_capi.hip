@@ -2041,6 +2041,36 @@ int vspg_light_sample_batch(VspgRenderer *r, int n, const float *ctx_p, const fl
     return 0;
 }
 
+int vspg_light_pdf_batch(VspgRenderer *r, int light_index, int n, const float *ctx_p, const float *ctx_perr, const float *ctx_n, const float *wi,
+                         float *out, void *stream) {
+    if (!r || n < 0 || (n > 0 && (!ctx_p || !ctx_n || !wi || !out))) return fail(VSPG_EINVAL, "null argument");
+    const DScene &H = r->hscene;
+    if (light_index < 0 || light_index >= light_list_size(H)) return fail(VSPG_EINVAL, "light_index outside the scene's light list");
+    if (light_index >= H.n_lights && light_index < H.n_lights + H.n_inf + H.n_point)
+        return fail(VSPG_EINVAL, "vspg_light_pdf_batch serves lights with a shape (rectangles, spheres): an infinite or delta light has none");
+    if (n == 0) return 0;
+    HIPCHK(hipSetDevice(r->cfg.device));
+    hipStream_t s = (hipStream_t)stream;
+    DevBuf dp, de, dn, dw, dout;
+    HIPCHK(hipMalloc(&dp.p, (size_t)n * 12));
+    HIPCHK(hipMalloc(&dn.p, (size_t)n * 12));
+    HIPCHK(hipMalloc(&dw.p, (size_t)n * 12));
+    HIPCHK(hipMalloc(&dout.p, (size_t)n * VSPG_LIGHT_PDF_OUT * 4));
+    HIPCHK(hipMemcpyAsync(dp.p, ctx_p, (size_t)n * 12, hipMemcpyHostToDevice, s));
+    HIPCHK(hipMemcpyAsync(dn.p, ctx_n, (size_t)n * 12, hipMemcpyHostToDevice, s));
+    HIPCHK(hipMemcpyAsync(dw.p, wi, (size_t)n * 12, hipMemcpyHostToDevice, s));
+    if (ctx_perr) {
+        HIPCHK(hipMalloc(&de.p, (size_t)n * 12));
+        HIPCHK(hipMemcpyAsync(de.p, ctx_perr, (size_t)n * 12, hipMemcpyHostToDevice, s));
+    }
+    hipLaunchKernelGGL(k_light_pdf_batch, dim3((n + kBlock - 1) / kBlock), dim3(kBlock), 0, s, r->dscene, light_index, n, (const float *)dp.p,
+                       (const float *)de.p, (const float *)dn.p, (const float *)dw.p, (float *)dout.p);
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipMemcpyAsync(out, dout.p, (size_t)n * VSPG_LIGHT_PDF_OUT * 4, hipMemcpyDeviceToHost, s));
+    HIPCHK(hipStreamSynchronize(s));
+    return 0;
+}
+
 int vspg_renderer_training_stats(VspgRenderer *r, VspgTrainStats *out, void *stream) {
     if (!r || !out) return fail(VSPG_EINVAL, "null argument");
     memset(out, 0, sizeof *out);

@@ -689,8 +689,9 @@ struct DField {
 };
 // Light samplers beyond the uniform pick (vspg_lightsampler.h): the BVH light sampler's nodes as CompactLightBounds' accessors
 // return them, the light -> bit-trail map of its PMF, the power sampler's alias table.  Built on the host with the renderer.
-// The light list: the emissive rectangles in rectangle order, then the infinite lights, then the point and spot lights.
-constexpr int kMaxLights = VSPG_MAX_QUADS + VSPG_MAX_INFINITE_LIGHTS + VSPG_MAX_POINT_LIGHTS;
+// The light list: the emissive rectangles in rectangle order, then the infinite lights, then the point and spot lights, then the
+// emissive spheres in sphere order.
+constexpr int kMaxLights = VSPG_MAX_QUADS + VSPG_MAX_INFINITE_LIGHTS + VSPG_MAX_POINT_LIGHTS + VSPG_MAX_SPHERES;
 struct DLightNode {
     float bmin[3], bmax[3], w[3];
     float phi, cosTheta_o, cosTheta_e;
@@ -707,6 +708,7 @@ struct DLightSampler {
     float alias_p[kMaxLights], alias_q[kMaxLights];
     int32_t alias_i[kMaxLights];
     int32_t light_of_quad[VSPG_MAX_QUADS];  // rectangle -> index into the light list (-1: not a light)
+    int32_t light_of_sphere[VSPG_MAX_SPHERES];  // sphere -> index into the light list (-1: not a light)
 };
 // Triangle geometry.  DTri: the three vertices plus what Triangle::InteractionFromIntersection
 // (shapes.h:883-1010) derives from them alone -- n = Normalize(Cross(p0 - p2, p1 - p2)) and the normalised dpdu of the
@@ -777,6 +779,18 @@ struct DPointLight {
     float mi[12];
     float cosFalloffEnd, cosFalloffStart;
     float axis[3];  // host only: Normalize(renderFromLight(Vector3f(0, 0, 1))), the w of SpotLight::Bounds
+};
+// DiffuseAreaLight on a sphere (vspg_spherelight.h), one record per SPHERE (index = the sphere's): what the light adds to the
+// DSphere beside it, which keeps its size -- DSphere sits in front of fields whose offsets the rectangle-scene kernels rely on.
+// Le all zero = not a light (light = -1).  center = renderFromObject(Point3f(0, 0, 0)) and inv_area = 1 / Sphere::Area() are formed
+// on the host by the reference's arithmetic; reverse is the shape's reverseOrientation ALONE (Sphere::Sample flips by it, where the
+// hit normal's DSphere::flip also carries transformSwapsHandedness).
+struct DSphereLight {
+    float Le[3];
+    int32_t two_sided, reverse;
+    int32_t light;  // index into the light list, -1 = not a light
+    float inv_area;
+    float center[3];
 };
 struct DScene {
     int32_t n_quads, n_lights;
@@ -863,7 +877,13 @@ struct DScene {
     // them (kSimpleScene instantiations above all) read nothing here, and no field in front of lsamp moves.
     int32_t n_point;
     DPointLight point[VSPG_MAX_POINT_LIGHTS];
+    // emissive spheres: the last n_sphere_lights entries of the light list, in sphere order; sphere_light[i] belongs to spheres[i]
+    int32_t n_sphere_lights;
+    int32_t light_spheres[VSPG_MAX_SPHERES];  // k-th emissive sphere -> sphere index (as light_quads for rectangles)
+    DSphereLight sphere_light[VSPG_MAX_SPHERES];
 };
+// the length of the scene's light list (full-scene kernels): one line per light kind
+__host__ __device__ __forceinline__ int light_list_size(const DScene &S) { return S.n_lights + S.n_inf + S.n_point + S.n_sphere_lights; }
 static_assert(offsetof(DScene, lsamp) == 5556,
               "the light sampler's offset as it was before point lights enlarged it (printed from that commit): every field in front of it stays where the rectangle-scene kernels read it");
 static_assert(offsetof(DScene, planes) + sizeof(RectPlanes) <= 4096 && offsetof(DScene, shard_count) < 4096,
@@ -1522,6 +1542,31 @@ struct SphereSurf {
     P3i pi;
     V3 n, dpdu_n;
 };
+// (*renderFromObject)(Point3fi(pObj, gamma(5) * Abs(pObj))): the object-space point on the sphere with its error bounds, carried to
+// render space by Transform::operator()(Point3fi) (transform.h:133-175).  Shared by the hit (InteractionFromIntersection) and the
+// area sample (Sphere::Sample(u), shapes.cpp:38-58).
+VDEV P3i sphere_point_to_render(const DSphere &S, V3 pObj) {
+    constexpr float g5 = (5 * kMachineEps) / (1 - 5 * kMachineEps), g3 = (3 * kMachineEps) / (1 - 3 * kMachineEps);
+    const Ivl px = ivl_from_err(pObj.x, g5 * __builtin_fabsf(pObj.x)), py = ivl_from_err(pObj.y, g5 * __builtin_fabsf(pObj.y)),
+              pz = ivl_from_err(pObj.z, g5 * __builtin_fabsf(pObj.z));
+    const float x = ivl_mid(px), y = ivl_mid(py), z = ivl_mid(pz);
+    const float ex = (px.hi - px.lo) / 2, ey = (py.hi - py.lo) / 2, ez = (pz.hi - pz.lo) / 2;
+    const bool exact = (px.hi - px.lo) == 0 && (py.hi - py.lo) == 0 && (pz.hi - pz.lo) == 0;
+    float pv[3], pe[3];
+#pragma unroll
+    for (int k = 0; k < 3; ++k) {
+        const float *row = S.m + 4 * k;
+        pv[k] = (row[0] * x + row[1] * y) + (row[2] * z + row[3]);
+        const float ea = g3 * (__builtin_fabsf(row[0] * x) + __builtin_fabsf(row[1] * y) + __builtin_fabsf(row[2] * z) + __builtin_fabsf(row[3]));
+        pe[k] = exact ? ea : (g3 + 1) * (__builtin_fabsf(row[0]) * ex + __builtin_fabsf(row[1]) * ey + __builtin_fabsf(row[2]) * ez) + ea;
+    }
+    return p3i_from_err(V3{pv[0], pv[1], pv[2]}, V3{pe[0], pe[1], pe[2]});
+}
+// Normalize((*renderFromObject)(Normal3f)): the inverse transpose (transform.h:329-334), then Normalize
+VDEV V3 sphere_normal_to_render(const DSphere &S, V3 no) {
+    const float *mi = S.mi;
+    return normalize(V3{mi[0] * no.x + mi[4] * no.y + mi[8] * no.z, mi[1] * no.x + mi[5] * no.y + mi[9] * no.z, mi[2] * no.x + mi[6] * no.y + mi[10] * no.z});
+}
 template <bool WITH_DPDU = true>
 VDEV SphereSurf sphere_interaction(const DSphere &S, V3 pHit) {
     SphereSurf r;
@@ -1534,23 +1579,8 @@ VDEV SphereSurf sphere_interaction(const DSphere &S, V3 pHit) {
     const V3 dpdv = V3{dth * (pHit.z * cosPhi), dth * (pHit.z * sinPhi), dth * (-S.radius * sinTheta)};
     V3 no = normalize(cross(dpdu, dpdv));
     if (S.flip) no = -no;
-    constexpr float g5 = (5 * kMachineEps) / (1 - 5 * kMachineEps), g3 = (3 * kMachineEps) / (1 - 3 * kMachineEps);
-    const Ivl px = ivl_from_err(pHit.x, g5 * __builtin_fabsf(pHit.x)), py = ivl_from_err(pHit.y, g5 * __builtin_fabsf(pHit.y)),
-              pz = ivl_from_err(pHit.z, g5 * __builtin_fabsf(pHit.z));
-    const float x = ivl_mid(px), y = ivl_mid(py), z = ivl_mid(pz);
-    const float ex = (px.hi - px.lo) / 2, ey = (py.hi - py.lo) / 2, ez = (pz.hi - pz.lo) / 2;
-    const bool exact = (px.hi - px.lo) == 0 && (py.hi - py.lo) == 0 && (pz.hi - pz.lo) == 0;
-    float pv[3], pe[3];
-#pragma unroll
-    for (int k = 0; k < 3; ++k) {  // Transform::operator()(Point3fi) (transform.h:133-175)
-        const float *row = S.m + 4 * k;
-        pv[k] = (row[0] * x + row[1] * y) + (row[2] * z + row[3]);
-        const float ea = g3 * (__builtin_fabsf(row[0] * x) + __builtin_fabsf(row[1] * y) + __builtin_fabsf(row[2] * z) + __builtin_fabsf(row[3]));
-        pe[k] = exact ? ea : (g3 + 1) * (__builtin_fabsf(row[0]) * ex + __builtin_fabsf(row[1]) * ey + __builtin_fabsf(row[2]) * ez) + ea;
-    }
-    r.pi = p3i_from_err(V3{pv[0], pv[1], pv[2]}, V3{pe[0], pe[1], pe[2]});
-    const float *mi = S.mi;  // normals: the inverse transpose (transform.h:329-334), then Normalize
-    r.n = normalize(V3{mi[0] * no.x + mi[4] * no.y + mi[8] * no.z, mi[1] * no.x + mi[5] * no.y + mi[9] * no.z, mi[2] * no.x + mi[6] * no.y + mi[10] * no.z});
+    r.pi = sphere_point_to_render(S, pHit);
+    r.n = sphere_normal_to_render(S, no);
     if (WITH_DPDU) {
         const float *m = S.m;
         r.dpdu_n = normalize(V3{m[0] * dpdu.x + m[1] * dpdu.y + m[2] * dpdu.z, m[4] * dpdu.x + m[5] * dpdu.y + m[6] * dpdu.z, m[8] * dpdu.x + m[9] * dpdu.y + m[10] * dpdu.z});

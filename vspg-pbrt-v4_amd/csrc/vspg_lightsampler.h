@@ -2,7 +2,8 @@
 //
 // "bvh" is the reference's default light sampler (guidedvolpathvspgintegrator.cpp:1318).  The tree is built once per renderer on
 // the host (vspg_scene_build.hip: lsb::build, the reference's buildBVH restated) over the light list {emissive rectangles in rectangle
-// order, then the infinite lights, then the point and spot lights -- bounded lights like the rectangles: they enter the tree}; a
+// order, then the infinite lights, then the point and spot lights, then the emissive spheres -- bounded lights like the rectangles:
+// they enter the tree}; a
 // node record keeps what CompactLightBounds' accessors return -- the box, the cosines and the axis after their round trip through
 // the 16-bit / 15-bit / octahedral quantisation -- so the device does the float arithmetic of CompactLightBounds::Importance on
 // them and nothing else.  Scenes with a single light (every sampler picks it with pmf 1) and
@@ -52,7 +53,7 @@ VDEV float light_importance(const DLightNode &nd, V3 p, V3 n) {  // CompactLight
 // returns false for "no light"
 VDEV bool light_sampler_sample(const DScene &S, V3 p, V3 n, float u, int *lightIndex, float *pmf) {
     const DLightSampler &ls = S.lsamp;
-    const int n_all = S.n_lights + S.n_inf + S.n_point;
+    const int n_all = light_list_size(S);
     if (ls.mode == VSPG_LIGHTSAMPLER_UNIFORM) {  // lightsamplers.h:33-38
         if (n_all == 0) return false;
         const int li = (int)(u * (float)n_all);
@@ -123,7 +124,7 @@ VDEV bool light_sampler_sample(const DScene &S, V3 p, V3 n, float u, int *lightI
 // lightSampler.PMF(ctx, light)
 VDEV float light_sampler_pmf(const DScene &S, V3 p, V3 n, int lightIndex) {
     const DLightSampler &ls = S.lsamp;
-    const int n_all = S.n_lights + S.n_inf + S.n_point;
+    const int n_all = light_list_size(S);
     if (ls.mode == VSPG_LIGHTSAMPLER_UNIFORM) return n_all ? 1.f / (float)n_all : 0.f;
     if (ls.mode == VSPG_LIGHTSAMPLER_POWER) return ls.n_alias ? ls.alias_p[lightIndex] : 0.f;
     // BVHLightSampler::PMF (lightsamplers.h:344-381)

@@ -117,12 +117,22 @@ VDEV bool light_sample_li(const DQuad &q, V3 ctxp, float u0, float u1, LightLi *
     ls->nLight = n;
     return true;
 }
-// light.SampleLi(ctx, uLight, lambda, allowIncompletePDF = true) for light `lightIndex` of the scene's light list
+struct LsCtx {  // LightSampleContext
+    P3i pi;
+    V3 n;
+};
+#include "vspg_spherelight.h"  // DiffuseAreaLight on a sphere: sphere_sample_li / sphere_pdf_li / sphere_light_L
+// light.SampleLi(ctx, uLight, lambda, allowIncompletePDF = true) for light `lightIndex` of the scene's light list.  `ctxp` is ctx.p();
+// `lctx` is the whole context (error bounds and normal), which sphere lights alone read: only FULL callers fill it.
 template <bool FULL = true>
-VDEV bool sample_light(const DScene &S, int lightIndex, V3 ctxp, float u0, float u1, LightLi *ls, bool *delta_light) {
+VDEV bool sample_light(const DScene &S, int lightIndex, V3 ctxp, const LsCtx &lctx, float u0, float u1, LightLi *ls, bool *delta_light) {
     *delta_light = false;
     if (!FULL || lightIndex < S.n_lights) return light_sample_li(light_quad_at(lightIndex), ctxp, u0, u1, ls);
     const int k = lightIndex - S.n_lights;
+    if (k >= S.n_inf + S.n_point) {  // the fourth range of the light list: the emissive spheres (vspg_spherelight.h)
+        const int si = S.light_spheres[k - S.n_inf - S.n_point];
+        return sphere_sample_li(S.spheres[si], S.sphere_light[si], lctx, u0, u1, ls);
+    }
     if (k >= S.n_inf) {  // the third range of the light list: PointLight / SpotLight::SampleLi (vspg_pointlight.h)
         const DPointLight &P = S.point[k - S.n_inf];
         *delta_light = true;
@@ -144,10 +154,6 @@ VDEV bool sample_light(const DScene &S, int lightIndex, V3 ctxp, float u0, float
     *delta_light = true;
     return true;
 }
-struct LsCtx {  // LightSampleContext
-    P3i pi;
-    V3 n;
-};
 // The previous vertex's LightSampleContext, carried across a path segment in compressed form: a
 // surface vertex is {re-projected hit point, rectangle} and LightSampleContext(isect) =
 // {Point3fi(p, pError), n} is a pure function of the two; a medium vertex (quad < 0) is the exact
@@ -392,6 +398,14 @@ VDEV Spec sample_Ld_shadow(const DScene &S, const Medium &medium, const Intr &in
     return wdiv(f_hat * T_ray * ls.L, avg(r_l + r_u));
 }
 
+// The LightSampleContext of SampleLd (:1140-1152): LightSampleContext(intr) -- the interaction's point with its error bounds and,
+// at a surface, its normal -- whose pi a reflective BSDF replaces by the exact point intr.OffsetRayOrigin(wo) (= ctxp there).
+VDEV LsCtx nee_light_ctx(const Intr &intr, bool offset, V3 ctxp) {
+    LsCtx c;
+    c.pi = offset ? p3i_exact(ctxp) : intr.pi;
+    c.n = intr.is_surface ? intr.n : mk(0, 0, 0);
+    return c;
+}
 template <class Medium, class PC, class GD = GDist>
 VDEV Spec sample_Ld(const DScene &S, const Medium &medium, const Intr &intr, const Bsdf *bsdf, int ch,
                     Sampler &sampler, Spec r_p, PC &pc, const GD *gd = nullptr, bool use_gd = false) {
@@ -399,10 +413,10 @@ VDEV Spec sample_Ld(const DScene &S, const Medium &medium, const Intr &intr, con
     V3 ctxp = intr.pi.mid();
     if (intr.is_surface && bsdf->has_lobes) ctxp = offset_ray_origin(intr.pi, intr.n, intr.wo);  // :1147-1149
     float u = sampler.get1d();
-    // lightSampler.Sample(ctx, u) (:1157) over the emissive rectangles, the infinite lights, then the point lights: UniformLightSampler
+    // lightSampler.Sample(ctx, u) (:1157) over the emissive rectangles, the infinite lights, the point lights, then the emissive spheres: UniformLightSampler
     // (lightsamplers.h:33-38) inline; the power / BVH samplers of multi-light scenes (vspg_lightsampler.h) in the full-scene kernels
     constexpr bool kFull = !Medium::kSimpleScene;
-    const int n_all = kFull ? S.n_lights + S.n_inf + S.n_point : S.n_lights;
+    const int n_all = kFull ? light_list_size(S) : S.n_lights;
     bool have_light = n_all > 0;
     int lightIndex = 0;
     float lightPmf = 0;
@@ -417,7 +431,9 @@ VDEV Spec sample_Ld(const DScene &S, const Medium &medium, const Intr &intr, con
     if (!have_light) return sp(0.f);
     LightLi ls;
     bool delta_light = false;
-    if (!sample_light<kFull>(S, lightIndex, ctxp, ul0, ul1, &ls, &delta_light)) return sp(0.f);
+    LsCtx lctx{};
+    if constexpr (kFull) lctx = nee_light_ctx(intr, intr.is_surface && bsdf->has_lobes, ctxp);
+    if (!sample_light<kFull>(S, lightIndex, ctxp, lctx, ul0, ul1, &ls, &delta_light)) return sp(0.f);
     float p_l = lightPmf * ls.pdf;
 
     float scatterPDF;
@@ -759,7 +775,7 @@ VDEV int li_surface_pre(const DScene &S, PathState &st, IsgSample &isg, PC &pc, 
     VSPG_PROF(PS_SURF_PRE);
     if constexpr (kRec) pc.rec.add_transmittance_weight(tw);  // :350
     if (!si.hit) {  // :353-374: infinite light sources (this fork lists DeltaDirection lights among them, integrators.h:79)
-        const int n_all = S.n_lights + S.n_inf + S.n_point;
+        const int n_all = light_list_size(S);
         for (int k = 0; FULL && k < S.n_inf; ++k) {
             const bool image = S.inf_type[k] == VSPG_LIGHT_IMAGE_INFINITE;
             // UniformInfiniteLight::Le / DistantLight::Le (lights.cpp:1014-1017, lights.h:291-293) / ImageInfiniteLight::Le (lights.h:643-647)
@@ -784,9 +800,27 @@ VDEV int li_surface_pre(const DScene &S, PathState &st, IsgSample &isg, PC &pc, 
     }
     const bool tri_hit = FULL && (is_tri(si.quad) || is_sphere(si.quad));
     const DQuad &q = quad_at(tri_hit ? 0 : si.quad);
-    Spec Le = !tri_hit && q.is_light ? light_L(q, si.n, -st.rd) : sp(0.f);  // :377 (triangles and spheres carry no area light)
+    Spec Le = !tri_hit && q.is_light ? light_L(q, si.n, -st.rd) : sp(0.f);  // :377 (triangles carry no area light)
     float w_direct = 0.f;
-    if (nonzero(Le)) {
+    if (FULL && is_sphere(si.quad) && S.n_sphere_lights > 0) {  // an emissive sphere (vspg_spherelight.h): the block below with the sphere's L and PDF_Li
+        const int sidx = sphere_of(si.quad);
+        const DSphereLight &E = S.sphere_light[sidx];
+        if (E.light >= 0) Le = sphere_light_L(E, si.n, -st.rd);
+        if (nonzero(Le)) {
+            if (st.depth == 0 || st.specularBounce) {
+                st.L = st.L + wdiv(st.beta * Le, avg(st.r_u));
+                w_direct = 1.0f;
+            } else {
+                const LsCtx pctx = st.prevCtx.template expand<FULL>(S);
+                const float pmf = S.lsamp.mode != VSPG_LIGHTSAMPLER_UNIFORM ? light_sampler_pmf(S, pctx.pi.mid(), pctx.n, E.light) : wrcp((float)light_list_size(S));
+                const float lightPDF = pmf * sphere_pdf_li(S.spheres[sidx], E, pctx, st.rd);
+                st.r_l = st.r_l * lightPDF;
+                const float w_l = S.prm.usenee ? wrcp(avg(st.r_u + st.r_l)) : 1.0f;
+                st.L = st.L + st.beta * w_l * Le;
+                w_direct = w_l;
+            }
+        }
+    } else if (nonzero(Le)) {
         // (no branch hint: one used to order these two blocks to hold the pinned k_render_wave_wg3 and its carry twin at eight SGPRs
         //  in lanes each.  Since the rectangle walks keep one lane mask per record both hold two without it, and with it the pinned
         //  kernel holds none but its twin two -- more than the pinned one, which tests/test_wg3_carry_kernel.py does not allow --
@@ -797,7 +831,7 @@ VDEV int li_surface_pre(const DScene &S, PathState &st, IsgSample &isg, PC &pc, 
         } else {
             const LsCtx pctx = st.prevCtx.template expand<FULL>(S);
             const float pmf = FULL && S.lsamp.mode != VSPG_LIGHTSAMPLER_UNIFORM ? light_sampler_pmf(S, pctx.pi.mid(), pctx.n, S.lsamp.light_of_quad[si.quad])
-                                                                                 : wrcp((float)(FULL ? S.n_lights + S.n_inf + S.n_point : S.n_lights));
+                                                                                 : wrcp((float)(FULL ? light_list_size(S) : S.n_lights));
             float lightPDF = pmf * (FULL ? light_pdf_li(q, pctx, st.rd) : light_pdf_li_hit(q, pctx, st.rd, si.p));
             st.r_l = st.r_l * lightPDF;
             float w_l = S.prm.usenee ? wrcp(avg(st.r_u + st.r_l)) : 1.0f;

@@ -200,7 +200,7 @@ __global__ __launch_bounds__(kBlock) void k_light_sample_batch(const DScene *__r
     o[2] = light_sampler_pmf(S, p, nn, lightIndex);
     LightLi ls{};
     bool delta_light = false;
-    if (!sample_light(S, lightIndex, p, u[3 * (size_t)i + 1], u[3 * (size_t)i + 2], &ls, &delta_light)) return;
+    if (!sample_light(S, lightIndex, p, LsCtx{p3i_exact(p), nn}, u[3 * (size_t)i + 1], u[3 * (size_t)i + 2], &ls, &delta_light)) return;
     o[3] = 1.f;
     o[4] = ls.wi.x; o[5] = ls.wi.y; o[6] = ls.wi.z;
     o[7] = ls.L.r; o[8] = ls.L.g; o[9] = ls.L.b;
@@ -208,6 +208,47 @@ __global__ __launch_bounds__(kBlock) void k_light_sample_batch(const DScene *__r
     const V3 pl = ls.pLight.mid();
     o[11] = pl.x; o[12] = pl.y; o[13] = pl.z;
     o[14] = delta_light ? 1.f : 0.f;
+}
+// vspg_light_pdf_batch (include/vspg.h): for one light with a shape (a rectangle or a sphere of the light list) what li_surface_pre
+// computes when a ray from the context along wi is weighed against it -- light_sampler_pmf, light_pdf_li / sphere_pdf_li, and the
+// shape's own intersection from ctx.SpawnRay(wi) with light_L / sphere_light_L at the hit.  ctx_perr == nullptr: exact points.
+__global__ __launch_bounds__(kBlock) void k_light_pdf_batch(const DScene *__restrict__ Sp, int lightIndex, int n, const float *__restrict__ ctx_p,
+                                                            const float *__restrict__ ctx_perr, const float *__restrict__ ctx_n,
+                                                            const float *__restrict__ wi_in, float *__restrict__ out) {
+    const int i = blockIdx.x * kBlock + threadIdx.x;
+    const DScene &S = *Sp;
+    stage_scene_lds(S);
+    __syncthreads();
+    if (i >= n) return;
+    float *o = out + (size_t)VSPG_LIGHT_PDF_OUT * i;
+    for (int k = 0; k < VSPG_LIGHT_PDF_OUT; ++k) o[k] = 0.f;
+    const V3 p = ld3(ctx_p + 3 * (size_t)i), wi = ld3(wi_in + 3 * (size_t)i);
+    LsCtx ctx;
+    ctx.pi = ctx_perr ? p3i_from_err(p, ld3(ctx_perr + 3 * (size_t)i)) : p3i_exact(p);
+    ctx.n = ld3(ctx_n + 3 * (size_t)i);
+    o[1] = light_sampler_pmf(S, ctx.pi.mid(), ctx.n, lightIndex);
+    const V3 ro = offset_ray_origin(ctx.pi, ctx.n, wi);  // ctx.SpawnRay(wi)
+    float t = 0.f;
+    V3 ph;
+    Spec L = sp(0.f);
+    bool hit;
+    if (lightIndex < S.n_lights) {
+        const DQuad &q = light_quad_at(lightIndex);
+        o[0] = light_pdf_li(q, ctx, wi);
+        hit = quad_intersect(q, ro, wi, kInf, &t, &ph);
+        if (hit) L = light_L(q, ld3(q.n), -wi);
+    } else {  // (the host admits nothing else) an emissive sphere
+        const int si = S.light_spheres[lightIndex - S.n_lights - S.n_inf - S.n_point];
+        const DSphere &sph = S.spheres[si];
+        const DSphereLight &E = S.sphere_light[si];
+        o[0] = sphere_pdf_li(sph, E, ctx, wi);
+        hit = sphere_intersect(sph, ro, wi, kInf, &t, &ph);
+        if (hit) L = sphere_light_L(E, sphere_interaction<false>(sph, ph).n, -wi);
+    }
+    if (!hit) return;
+    o[2] = 1.f;
+    o[3] = L.r; o[4] = L.g; o[5] = L.b;
+    o[6] = t;
 }
 __global__ __launch_bounds__(kBlock) void k_libm_log1m(int n, const float *__restrict__ x, float *__restrict__ out) {
     int i = blockIdx.x * kBlock + threadIdx.x;

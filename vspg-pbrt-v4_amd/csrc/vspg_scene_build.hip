@@ -248,6 +248,42 @@ static lightbounds_t quad_light_bounds(const DQuad &q, int reverse_orientation) 
     return lb;
 }
 // PointLight::Bounds (lights.cpp:200-205) / SpotLight::Bounds (:1457-1467): a degenerate box at the light's position
+// DiffuseAreaLight::Bounds (lights.cpp:845-864) over a sphere: Sphere::Bounds (shapes.cpp:33-36) = the object box carried to render space
+// corner by corner (Transform::operator()(Bounds3f), transform.cpp:134-139; Point3f operator() transform.h:310-319), NormalBounds =
+// DirectionCone::EntireSphere() (shapes.h:134; w = (0, 0, 1), cosTheta = -1), phi = Lemit->MaxValue() * scale * area * Pi
+static lightbounds_t sphere_light_bounds(const DSphere &S, const DSphereLight &E) {
+    lightbounds_t lb;
+    lb.bmin = V3(INFINITY, INFINITY, INFINITY);
+    lb.bmax = V3(-INFINITY, -INFINITY, -INFINITY);
+    const float r = S.radius;
+    for (int c = 0; c < 8; ++c) {  // Bounds3::Corner: bit 0 -> x, bit 1 -> y, bit 2 -> z
+        const float x = (c & 1) ? r : -r, y = (c & 2) ? r : -r, z = (c & 4) ? r : -r;
+        float q[3];
+        for (int k = 0; k < 3; ++k) {
+            volatile float a = S.m[4 * k] * x;  // volatile: one rounding per operation, no contraction
+            volatile float b = S.m[4 * k + 1] * y;
+            volatile float c2 = S.m[4 * k + 2] * z;
+            volatile float sum = a + b;
+            sum = sum + c2;
+            sum = sum + S.m[4 * k + 3];
+            q[k] = sum;
+        }
+        const v3 p = V3(q[0], q[1], q[2]);  // (affine: wp == 1)
+        lb.bmin = v_min3(lb.bmin, p);
+        lb.bmax = v_max3(lb.bmax, p);
+    }
+    float phi = fmaxf(E.Le[0], fmaxf(E.Le[1], E.Le[2]));
+    volatile float dz = r - (-r);
+    volatile float a = S.phiMax * r;
+    a = a * dz;
+    phi *= 1.f * a * PI_F;  // scale * area * Pi
+    lb.w = V3(0, 0, 1);
+    lb.phi = phi;
+    lb.cosTheta_o = -1;
+    lb.cosTheta_e = cosf(PI_F / 2);
+    lb.twoSided = E.two_sided;
+    return lb;
+}
 static lightbounds_t point_light_bounds(const DPointLight &P) {
     lightbounds_t lb;
     lb.bmin = lb.bmax = V3(P.pos[0], P.pos[1], P.pos[2]);
@@ -273,10 +309,12 @@ static lightbounds_t point_light_bounds(const DPointLight &P) {
 void build(const VspgScene &sc, const VspgIntegratorParams &prm, DScene *D) {
     DLightSampler *ls = &D->lsamp;
     std::memset(ls, 0, sizeof *ls);
-    const int n_all = D->n_lights + D->n_inf + D->n_point, first_point = D->n_lights + D->n_inf;
+    const int n_all = light_list_size(*D), first_point = D->n_lights + D->n_inf, first_sphere = first_point + D->n_point;
     for (int i = 0; i < kMaxLights; ++i) ls->bit_trail[i] = 0xffffffffu;
     for (int i = 0; i < VSPG_MAX_QUADS; ++i) ls->light_of_quad[i] = -1;
     for (int i = 0; i < D->n_lights; ++i) ls->light_of_quad[D->light_quads[i]] = i;
+    for (int i = 0; i < VSPG_MAX_SPHERES; ++i) ls->light_of_sphere[i] = -1;
+    for (int i = 0; i < D->n_sphere_lights; ++i) ls->light_of_sphere[D->light_spheres[i]] = first_sphere + i;
     // every sampler picks a scene's only light with pmf 1: the two-line uniform pick serves (and keeps the workgroup kernels)
     ls->mode = n_all > 1 ? prm.lightsampler : VSPG_LIGHTSAMPLER_UNIFORM;
     lbvh_item_t items[LBVH_MAX_LIGHTS];
@@ -285,7 +323,8 @@ void build(const VspgScene &sc, const VspgIntegratorParams &prm, DScene *D) {
     for (int i = 0; i < n_all; ++i) {
         if (i >= D->n_lights && i < first_point) { ls->inf_light[ls->n_inf++] = i; continue; }  // Bounds() == {}
         lightbounds_t lb;
-        if (i >= first_point) lb = point_light_bounds(D->point[i - first_point]);
+        if (i >= first_sphere) lb = sphere_light_bounds(D->spheres[D->light_spheres[i - first_sphere]], D->sphere_light[D->light_spheres[i - first_sphere]]);
+        else if (i >= first_point) lb = point_light_bounds(D->point[i - first_point]);
         else {
             const int qi = D->light_quads[i];
             lb = quad_light_bounds(D->quads[qi], sc.quads[qi].reverse_orientation);
@@ -312,6 +351,14 @@ void build(const VspgScene &sc, const VspgIntegratorParams &prm, DScene *D) {
                 const DQuad &q = D->quads[D->light_quads[i]];
                 for (int c = 0; c < 3; ++c) L[c] = q.Le[c];
                 k = PI_F * (q.two_sided ? 2 : 1) * q.area;  // DiffuseAreaLight::Phi (lights.cpp:826-843)
+            } else if (i >= first_sphere) {
+                const int si = D->light_spheres[i - first_sphere];
+                const DSphereLight &E = D->sphere_light[si];
+                for (int c = 0; c < 3; ++c) L[c] = E.Le[c];
+                volatile float dz = D->spheres[si].radius - (-D->spheres[si].radius);
+                volatile float area = D->spheres[si].phiMax * D->spheres[si].radius;
+                area = area * dz;
+                k = PI_F * (E.two_sided ? 2 : 1) * area;  // DiffuseAreaLight::Phi (lights.cpp:826-843)
             } else if (i >= first_point) {
                 const DPointLight &P = D->point[i - first_point];
                 for (int c = 0; c < 3; ++c) L[c] = P.I[c];
@@ -598,6 +645,44 @@ void build_dscene(const VspgScene &sc, const VspgIntegratorParams &prm, const Vs
         }
         sp.has_lobes = lobes;
         sp.flags = surf_flags_of(in.material, in.medium_interface);
+    }
+    // DiffuseAreaLight on a sphere (vspg_spherelight.h): the emissive spheres, in sphere order, are the last range of the light list
+    D->n_sphere_lights = 0;
+    for (int i = 0; i < VSPG_MAX_SPHERES; ++i) {
+        DSphereLight &E = D->sphere_light[i];
+        std::memset(&E, 0, sizeof E);
+        E.light = -1;
+        D->light_spheres[i] = 0;
+    }
+    for (int i = 0; i < sc.n_spheres; ++i) {
+        const VspgSphere &in = sc.spheres[i];
+        DSphereLight &E = D->sphere_light[i];
+        for (int k = 0; k < 3; ++k) E.Le[k] = sc.sphere_Le[i][k];
+        E.two_sided = sc.sphere_two_sided[i] ? 1 : 0;
+        E.reverse = in.reverse_orientation ? 1 : 0;
+        {   // Area() = phiMax * radius * (zMax - zMin) (shapes.h:131), zMin = -radius, zMax = radius: object space
+            volatile float dz = in.radius - (-in.radius);  // volatile: one rounding per operation, no contraction
+            volatile float a = D->spheres[i].phiMax * in.radius;
+            a = a * dz;
+            E.inv_area = 1 / a;
+        }
+        // renderFromObject(Point3f(0, 0, 0)), Transform::operator()(Point3f) (transform.h:310-319): the sums as written, then `wp == 1`
+        const float *m = in.render_from_object;
+        float q[4];
+        for (int k = 0; k < 4; ++k) {
+            volatile float a = m[4 * k] * 0.f;
+            volatile float b = m[4 * k + 1] * 0.f;
+            volatile float c2 = m[4 * k + 2] * 0.f;
+            volatile float sum = a + b;
+            sum = sum + c2;
+            sum = sum + m[4 * k + 3];
+            q[k] = sum;
+        }
+        for (int k = 0; k < 3; ++k) E.center[k] = q[3] == 1 ? q[k] : q[k] / q[3];
+        if (E.Le[0] != 0 || E.Le[1] != 0 || E.Le[2] != 0) {
+            E.light = D->n_lights + D->n_inf + D->n_point + D->n_sphere_lights;
+            D->light_spheres[D->n_sphere_lights++] = i;
+        }
     }
     // medium boundaries: anything that makes "the medium fills the scene" false
     D->camera_in_medium = sc.medium.type != VSPG_MEDIUM_NONE && !sc.camera_outside_medium;
@@ -965,6 +1050,13 @@ int validate(const VspgScene *scene, const VspgIntegratorParams *p, const VspgRe
         const float *a = sp.render_from_object, *b = sp.object_from_render;
         if (a[12] != 0 || a[13] != 0 || a[14] != 0 || a[15] != 1 || b[12] != 0 || b[13] != 0 || b[14] != 0 || b[15] != 1)
             return fail(VSPG_EINVAL, "a sphere's renderFromObject must be affine (last row 0 0 0 1)");
+        const float *Le = scene->sphere_Le[i];
+        for (int k = 0; k < 3; ++k)
+            if (!std::isfinite(Le[k]) || Le[k] < 0) return fail(VSPG_EINVAL, "a sphere light's Le must be finite and >= 0");
+        if (scene->sphere_two_sided[i] != 0 && scene->sphere_two_sided[i] != 1) return fail(VSPG_EINVAL, "a sphere light's two_sided must be 0 or 1");
+        if ((Le[0] != 0 || Le[1] != 0 || Le[2] != 0) && sp.material == VSPG_MATERIAL_INTERFACE)
+            return fail(VSPG_ESCOPE, "an emissive sphere with Material \"interface\": the reference allows it, this library does not (a shadow ray's end "
+                                     "point would lie on a surface its segments walk through)");
     }
     if (cfg->shard_count > 1 && (cfg->shard_index < 0 || cfg->shard_index >= cfg->shard_count))
         return fail(VSPG_EINVAL, "shard_index out of range");

@@ -477,7 +477,7 @@ VDEV ShadowSetup sample_Ld_begin(const DScene &S, const Medium &medium, int ch, 
     V3 ctxp = intr.pi.mid();
     if (intr.is_surface && bsdf->has_lobes) ctxp = offset_ray_origin(intr.pi, intr.n, intr.wo);  // :1147-1149
     float u = sampler.get1d();
-    const int n_all = S.n_lights + S.n_inf + S.n_point;
+    const int n_all = light_list_size(S);
     bool have_light = n_all > 0;
     int lightIndex = 0;
     float lightPmf = 0;
@@ -491,7 +491,7 @@ VDEV ShadowSetup sample_Ld_begin(const DScene &S, const Medium &medium, int ch, 
     float ul0 = sampler.get1d(), ul1 = sampler.get1d();
     if (!have_light) return r;
     LightLi ls;
-    if (!sample_light(S, lightIndex, ctxp, ul0, ul1, &ls, &r.delta_light)) return r;
+    if (!sample_light(S, lightIndex, ctxp, nee_light_ctx(intr, intr.is_surface && bsdf->has_lobes, ctxp), ul0, ul1, &ls, &r.delta_light)) return r;
     r.p_l = lightPmf * ls.pdf;
     V3 wo = intr.wo, wi = ls.wi;
     // GuidedBSDF::PDF / GuidedPhaseFunction::PDF (guiding.h:271-289, 542-558) when the vertex is guided (sample_Ld, vspg_path.h)

@@ -452,7 +452,10 @@ class Parser {
             p.ReportUnused();
             if (!(radius > 0)) fail("sphere: radius must be positive");
             if (zmin > -radius || zmax < radius || phimax < 360.f) fail("partial spheres (zmin / zmax / phimax) are outside this build's scope");
-            if (gs.areaLight) fail("emissive spheres are outside this build's scope (emission lives on rectangles)");
+            // (The library and its binding carry sphere area lights; the reader does not accept them yet.)
+            if (gs.areaLight)
+                fail("emissive spheres are not read from scene files yet -- build the scene through the C-ABI (VspgScene.sphere_Le / sphere_two_sided; "
+                     "add_sphere_light in the Python binding)");
             if (spheres.size() >= VSPG_MAX_SPHERES) fail("more than " + std::to_string(VSPG_MAX_SPHERES) + " spheres");
             VspgSphere sp;
             std::memset(&sp, 0, sizeof sp);
