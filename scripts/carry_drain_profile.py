@@ -11,6 +11,9 @@ after every launch and prints, per launch and as medians:
   ideal     the launch's chunks priced at the steady phase's ticks per lane of their kind, spread over every wavefront at the steady
             phase's share of time spent in chunks: how long the launch would last if it ran at the steady rate from end to end
   ceiling   span - ideal: the idle lane-time of ramp + drain, the most a scheme that keeps the pools full across launches can remove
+
+and, at the end, the time per chunk of each kind in the steady phase, for the launches whose fresh chunks resolve a parked sample and for
+those right behind an update of the VSP buffer (the flush resolved them: nothing parked) apart.
 """
 import ctypes as C, os, sys
 import numpy as np
@@ -41,9 +44,13 @@ rows = []
 print("kernel: %s, %d workgroups x 8 wavefronts, tick = 10 ns" % (r.kernel_name(), BLOCKS))
 print("%4s %8s %8s %8s %8s %8s %8s %8s | %s" % ("wave", "span_us", "to_exh", "drain", "tail", "ramp", "ideal", "ceiling",
                                                  "per phase (ramp/steady/drain): chunks, mean lanes, us per chunk"))
+kinds = []   # per launch: (no parked samples to resolve?, steady-phase us per chunk of each kind [vertex, segment, fresh], steady chunks per kind)
+after_update = False
 for w in range(WARM, WARM + STEPS):
     r.render_wave(w, w + 1)
     a = read()
+    no_parked = after_update          # the update's flush resolved them: this launch's fresh chunks had none to resolve
+    after_update = r.isg_update_due(1)
     r.post_process_wave()
     t = a[..., :4]
     ran = t[..., 0] > 0
@@ -67,8 +74,20 @@ for w in range(WARM, WARM + STEPS):
     ph = " / ".join("%d, %.1f, %.2f" % (s[p, :, 0].sum(), s[p, :, 1].sum() / max(1, s[p, :, 0].sum()),
                                         s[p, :, 2].sum() / max(1, s[p, :, 0].sum()) * TICK_US) for p in range(3))
     rows.append((span, to_exh, drain, tail, ramp, ideal, span - ideal, in_chunks))
+    kinds.append((no_parked, steady[:, 2] / np.maximum(steady[:, 0], 1) * TICK_US, steady[:, 0], s[0, :, 2] / np.maximum(s[0, :, 0], 1) * TICK_US))
     print("%4d %8.1f %8.1f %8.1f %8.1f %8.1f %8.1f %8.1f | %s" % (w, span, to_exh, drain, tail, ramp, ideal, span - ideal, ph))
 m = np.median(np.array(rows), axis=0)
 print("median span %.1f us, to_exh %.1f, drain %.1f, tail %.1f, ramp %.1f, ideal %.1f, ceiling %.1f us = %.1f %% of the span; steady share of time in chunks %.3f"
       % (m[0], m[1], m[2], m[3], m[4], m[5], m[6], 100 * m[6] / m[0], m[7]))
+# time per chunk by kind, launches whose fresh chunks resolve a parked sample against those right behind an update (none parked)
+for flag, name in ((False, "with parked samples"), (True, "behind an update (none parked)")):
+    sel = [k for k in kinds if k[0] == flag]
+    if not sel:
+        continue
+    st = np.median(np.array([k[1] for k in sel]), axis=0)
+    rp = np.median(np.array([k[3] for k in sel]), axis=0)
+    print("%-32s %2d launches: steady us per chunk vertex %.2f segment %.2f fresh %.2f; ramp phase vertex %.2f segment %.2f fresh %.2f"
+          % (name, len(sel), st[0], st[1], st[2], rp[0], rp[1], rp[2]))
+    for k in sel if flag else []:
+        print("    steady fresh chunks %d at %.2f us, ramp fresh %.2f us" % (k[2][2], k[1][2], k[3][2]))
 r.close()

@@ -328,6 +328,8 @@ struct VspgRenderer {
     Wg3Launch carry_shape = {};       // the launch that wrote the pending image: instantiation, grid, window
     int carry_arith = 0;              // ... and its arithmetic mode
     unsigned long long carry_resumes = 0;  // launches that resumed from an image (vspg_debug_carry_resumes)
+    unsigned long long carry_kept = 0;     // ... that suspended nothing because an update was due behind them (vspg_debug_carry_kept)
+    bool step_post_processed = false;      // vspg_post_process_step ran since the last path launch: the caller post-processes its steps
     unsigned int *wf_lists = nullptr;   // 4 x n_items: active (even / odd iterations), walk, shadow
     hipStream_t wf_stream2 = nullptr;   // the shadow walks' stream (wf_render_pass)
     hipEvent_t wf_ev_vertex = nullptr, wf_ev_shadow = nullptr;
@@ -1141,29 +1143,46 @@ int vspg_render_window(VspgRenderer *r, int x0, int y0, int x1, int y1, int wave
         r->head_parity ^= 1u;  // (undo the toggle above: no launch used that pair)
         Wg3Launch L3{r->dscene, r->film, r->isg_stats, r->vsp, r->vsp_ready, wave_end, first, single, jump, tiles_magic, head8, ws_prev, ws_out,
                      r->counters, (unsigned)wblocks, (hipStream_t)stream, wg3_grey, wg3_null_zero, whole ? 0 : 1, win, 0, nullptr, nullptr};
+        bool update_follows = false;
         if (carry) {
             // (an image per workgroup of the largest grid a launch of this renderer can have, at the largest instantiation's size)
             const size_t img_bytes = (size_t)r->num_cus * (size_t)(kWgWavesHomog * 4 / (kWgBlockHomog / 64)) * (size_t)kWg3ImageStrideMax * sizeof(unsigned int);
             for (int k = 0; k < 2; ++k)
                 if (!r->carry_img[k]) HIPCHK(hipMalloc(&r->carry_img[k], img_bytes));
+            static_assert(kWg3ImageStrideMax % 4 == 0, "images are copied in 16-byte pieces");
+            if ((reinterpret_cast<uintptr_t>(r->carry_img[0]) | reinterpret_cast<uintptr_t>(r->carry_img[1])) & 15u)
+                return fail(VSPG_EHIP, "k_render_wave_wg3_carry: image buffers are not 16-byte aligned");
             L3.carry = 1;
             L3.resume = r->carry_pending ? r->carry_img[r->carry_cur ^ 1] : nullptr;
-            L3.suspend = r->carry_img[r->carry_cur];
+            // A step that ends in an update of the VSP buffer flushes the parked samples, and with them the carried paths: the launch of
+            // such a step suspends nothing (it resumes, takes its tiles and runs every path to its end), which saves the images, the
+            // drain launch and the empty chip between the two.  The step is the caller's: one wave, or shard_count of them under
+            // sample-index sharding (sharding.py).  Predicted only for a caller that post-processed its previous step: one that never does
+            // (wave counter 0, an update "due" for ever) keeps carrying.  Only a hint: a wrong guess either way leaves a state the drain
+            // path handles as ever.
+            // (VSPG_WG3_PREDICT=0: every carried launch suspends and the flush drains, for A/B runs and tests; read per launch)
+            const char *const pe = getenv("VSPG_WG3_PREDICT");
+            update_follows = !(pe && pe[0] == '0') && r->step_post_processed && vspg_isg_update_due(r, sc > 1 ? sc : 1) != 0;
+            L3.suspend = update_follows ? nullptr : r->carry_img[r->carry_cur];
         }
         const int lrc = wg3_launch_any(r->arith, L3);  // (wg3_launch_unguided picks the grey / null-zero instantiation, vspg_wg3.h)
         if (lrc != 0) return fail(VSPG_EHIP, std::string("k_render_wave_wg3: ") + hipGetErrorName((hipError_t)lrc));
         if (carry) {
             if (r->carry_pending) r->carry_resumes++;
-            r->carry_cur ^= 1;
-            r->carry_pending = true;
-            r->carry_shape = L3;
-            r->carry_arith = r->arith;
+            r->carry_pending = !update_follows;  // (nothing suspended: the parked plane is complete behind this launch)
+            if (update_follows) r->carry_kept++;
+            if (r->carry_pending) {
+                r->carry_cur ^= 1;
+                r->carry_shape = L3;
+                r->carry_arith = r->arith;
+            }
         }
         break;
     }
     default: return not_built();
     }
     HIPCHK(hipGetLastError());
+    r->step_post_processed = false;
     if (parks && single) {  // this launch's samples are parked in ws_out (its predecessor's, if any were, have just been resolved)
         r->ws_cur ^= 1;
         r->ws_parked = true;
@@ -1277,6 +1296,7 @@ int vspg_post_process_step(VspgRenderer *r, int n_waves, const float *isg_stats_
     if (n_waves < 1) return fail(VSPG_EINVAL, "n_waves must be >= 1");
     const bool due = isg_update_due(r, n_waves);
     r->wave_counter += n_waves;
+    r->step_post_processed = true;
     if (r->train_counters) {
         HIPCHK(hipSetDevice(r->cfg.device));
         if (r->training) {
@@ -1323,6 +1343,8 @@ int vspg_flush(VspgRenderer *r, void *stream) {
 }
 // how many launches of this renderer resumed paths their predecessor left in flight (tests: the carry path was taken)
 long long vspg_debug_carry_resumes(VspgRenderer *r) { return r ? (long long)r->carry_resumes : -1; }
+// ... and how many suspended nothing because the step's update of the VSP buffer was predicted (tests: the prediction was taken)
+long long vspg_debug_carry_kept(VspgRenderer *r) { return r ? (long long)r->carry_kept : -1; }
 int vspg_film_device_ptr(VspgRenderer *r, float **dev_ptr, size_t *n_floats) {
     if (!r || !dev_ptr || !n_floats) return fail(VSPG_EINVAL, "null argument");
     if (r->ws_parked) {  // the caller reads the film on a stream of its own: the parked samples go in, and are in, before it gets the pointer

@@ -1386,6 +1386,17 @@ VDEV void start_path(const DScene &S, const float *vsp_buf, int vsp_ready, int p
     sampler.start_pixel_sample(px, py, S.seed, jump);
     start_path_common(S, px, py, sampler, st, ch, isg);
 }
+// ... with the pixel's VSP in hand (0.5 until the buffer counts): k_render_wave_wg3 loads it beside the pixel's other reads
+VDEV void start_path(const DScene &S, float vsp0, int px, int py, int sampleIndex, Sampler &sampler, PathState &st, int *ch, IsgSample &isg) {
+    st.vsp0 = vsp0;
+    sampler.start_pixel_sample(px, py, S.seed, sampleIndex);
+    start_path_common(S, px, py, sampler, st, ch, isg);
+}
+VDEV void start_path(const DScene &S, float vsp0, int px, int py, PcgJump jump, Sampler &sampler, PathState &st, int *ch, IsgSample &isg) {
+    st.vsp0 = vsp0;
+    sampler.start_pixel_sample(px, py, S.seed, jump);
+    start_path_common(S, px, py, sampler, st, ch, isg);
+}
 VDEV void start_path_common(const DScene &S, int px, int py, Sampler &sampler, PathState &st, int *ch, IsgSample &isg) {
     float lu = sampler.get1d();
     st.lu = lu;
@@ -1470,22 +1481,21 @@ VDEV void isg_add_sample_atomic(float *st, Spec L, const IsgSample &isg) {
 // addition per channel.  Ten no-return float atomics per finished path are L2-atomic-unit bound at 1080p
 // (measured: 0.28 ms of a 0.42 ms maxdepth-0 wave, 0.12 ms of the 0.94 ms benchmark wave); the RMW moves
 // 96 B per path through the ordinary load/store path instead.
-VDEV void film_add_sample_rmw(float4 *film_px, Spec L) {
-    float4 v = *film_px;
+// (each in two halves: "given the loaded values" -- the addition and the store -- and the load in front of it)
+VDEV void film_store_sample(float4 *film_px, float4 v, Spec L) {
     v.x += L.r;
     v.y += L.g;
     v.z += L.b;
     v.w += 1.f;
     *film_px = v;
 }
-VDEV void isg_add_sample_rmw(float *st, Spec L, const IsgSample &isg) {
+VDEV void film_add_sample_rmw(float4 *film_px, Spec L) { film_store_sample(film_px, *film_px, L); }
+VDEV void isg_store_sample(float *st, float4 a, float2 b, Spec L, const IsgSample &isg) {  // a = st[0..3], b = st[4..5] as loaded
     if (!isg.valid) return;
     float c = avg(L);
     float q = isg.vsp_used >= 0.f ? isg.vsp_used : 0.5f;
-    float4 *p4 = reinterpret_cast<float4 *>(st);   // st[0..3]
-    float2 *p2 = reinterpret_cast<float2 *>(st + 4);  // st[4..5]
-    float4 a = *p4;
-    float2 b = *p2;
+    float4 *p4 = reinterpret_cast<float4 *>(st);
+    float2 *p2 = reinterpret_cast<float2 *>(st + 4);
     a.x += 1.f;
     if (isg.surface_event) {
         a.z += c;
@@ -1497,6 +1507,10 @@ VDEV void isg_add_sample_rmw(float *st, Spec L, const IsgSample &isg) {
     }
     *p4 = a;
     *p2 = b;
+}
+VDEV void isg_add_sample_rmw(float *st, Spec L, const IsgSample &isg) {
+    if (!isg.valid) return;
+    isg_store_sample(st, *reinterpret_cast<const float4 *>(st), *reinterpret_cast<const float2 *>(st + 4), L, isg);
 }
 VDEV void isg_add_sample(float *st, Spec L, const IsgSample &isg) {
     if (!isg.valid) return;

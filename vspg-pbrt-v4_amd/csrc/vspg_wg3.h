@@ -63,6 +63,23 @@ __device__ __forceinline__ void resolve_sample(float4 s, float4 *film_px, float 
     isg.vsp_used = __builtin_fabsf(s.w);
     isg_add_sample_rmw(isg_px, L, isg);
 }
+// ... given the film pixel and the statistics already loaded (a FRESH chunk loads them with the parked sample, in one round trip):
+// the additions, their operands and their order are film_add_sample_rmw's and isg_add_sample_rmw's
+__device__ __forceinline__ void resolve_sample_loaded(float4 s, float4 fpx, float4 st03, float2 st45, float4 *film_px, float *isg_px) {
+    const Spec L = Spec{s.x, s.y, s.z};
+    film_store_sample(film_px, fpx, L);
+    IsgSample isg;
+    isg.valid = s.w != 0.f;
+    isg.surface_event = s.w < 0.f;
+    isg.vsp_used = __builtin_fabsf(s.w);
+    isg_store_sample(isg_px, st03, st45, L, isg);
+}
+// Every load issued so far has arrived behind this point: the values are named as inputs, so the compiler can neither sink a load
+// into the branch that uses it (a second round trip behind the first) nor wait for them one by one.
+__device__ __forceinline__ void w3_loads_arrived(float4 a, float4 b, float4 c, float2 d, float e) {
+    asm volatile("" ::"v"(a.x), "v"(a.y), "v"(a.z), "v"(a.w), "v"(b.x), "v"(b.y), "v"(b.z), "v"(b.w), "v"(c.x), "v"(c.y), "v"(c.z), "v"(c.w), "v"(d.x),
+                 "v"(d.y), "v"(e));
+}
 // An opaque copy of a kernel argument at its point of use.  A wave-uniform flag tested inside the persistent loop is otherwise
 // turned into a 64-bit lane mask once, before the loop, and held there (one pair per test: `single_sample` took two); with more live
 // values than SGPRs those pairs are spilled to VGPR lanes and read back at every use.  The opaque copy keeps the 32-bit argument
@@ -97,6 +114,12 @@ __device__ __forceinline__ int w3_lane() {
 //     additions per pixel keep their order and the film its bits;
 //   * a workgroup suspends only once `old_live` is 0 (until then it serves every queue as ever): a path is carried at most once,
 //     whatever the frame size, and every slot in flight at the suspension belongs to this launch.
+//   * a launch whose step ends in an update of the VSP buffer (vspg_capi.hip predicts it) would be drained at once: it gets `resume`
+//     and its tiles but NO suspend buffer.  The drain bit in `old_live` keeps the carry exit from firing, resumed paths add their
+//     samples, new ones run to their ends and park, workgroups leave by the ordinary `exh && live == 0`: behind it nothing is
+//     pending and the parked plane is complete.  What tells the drain launch (no tiles) is first_sample < 0, not the missing buffer.
+// The image lies in global memory as it lies in LDS -- pool, rings, queue words -- and moves in 16-byte pieces, every load of the
+// prologue in flight before the first LDS write (profiles/wave_boundary_static.txt).
 // The free ring and the claimed-unread hazard (see the FRESH claim below): a resumed ring is no longer "full from index 0", it is a
 // ring on a later lap, which the same argument already covers -- the claimed entries are read right behind the CAS, and a sibling
 // would have to claim, run a chunk and push within those few instructions.  The queue words are rebased on resume (HEAD < NP), so
@@ -107,6 +130,8 @@ template <class LY, int NP> constexpr int kWg3ImagePool = LY::COUNT * NP;       
 template <class LY, int NP> constexpr int kWg3ImageWords = LY::COUNT * NP + Q_COUNT * NP / 2;  // ... the four rings, then the queue words
 template <class LY, int NP> constexpr int kWg3ImageStride = kWg3ImageWords<LY, NP> + 32;  // per workgroup
 static_assert(W3_COUNT <= 32, "the image's queue words");
+// piece i of an image of N 16-byte pieces, or the last one for a lane past the end: its load stays inside the image, nothing is stored
+template <int N> __device__ __forceinline__ int w3_image_piece(int i) { return i < N ? i : N - 1; }
 
 constexpr int kWg3Heads = 8, kWg3HeadSetBytes = kWg3Heads * 128;  // k_render_wave_wg3's tile cursors (see the kernel)
 // The global work head is a PAIR of counters used by alternate launches: a launch zeroes the one the NEXT launch will use
@@ -120,6 +145,7 @@ __device__ __forceinline__ void reset_sibling_head(unsigned int *work_head) {
 // LDS reads and ONE wait.  A 128-bit read is one LDS instruction: {reserved, committed, head} are a snapshot.
 typedef unsigned int w3_u32x4 __attribute__((ext_vector_type(4)));
 typedef const volatile __attribute__((address_space(3))) w3_u32x4 *w3_lds_v4;
+typedef __attribute__((address_space(1))) w3_u32x4 *w3_glb_v4;
 // Every lane hands its slot to the queue its path now belongs to (dq in [0, Q_COUNT), or -1: none): the four reservations are ONE
 // returning LDS atomic (lane q reserves for queue q), then the entries, then the four commits as one atomic.
 template <int NP>
@@ -208,8 +234,8 @@ __device__ __forceinline__ void wg3_render(
     const DScene &S = *Sp;
     const int W = S.xres, H = S.yres;
     const int tilesX = WINDOW ? win_tiles_x(win) : (W + 7) >> 3, tilesY = WINDOW ? win_tiles_y(win) : (H + 7) >> 3;
-    // (CARRY without a suspend buffer is the drain launch: no tiles, the resumed paths run to their ends)
-    const unsigned n_tiles = CARRY && w3_at_use(suspend) == nullptr ? 0u : (unsigned)(tilesX * tilesY);
+    // (CARRY with first_sample < 0 is the drain launch: no tiles, the resumed paths run to their ends)
+    const unsigned n_tiles = CARRY && w3_at_use(first_sample) < 0 ? 0u : (unsigned)(tilesX * tilesY);
     // is pixel (px, py) of a claimed tile part of the launch?  (tile padding past the frame / outside the window)
     const auto in_launch = [&](int px, int py) {
         if constexpr (WINDOW) return win_has(win, px, py);
@@ -233,8 +259,8 @@ __device__ __forceinline__ void wg3_render(
     constexpr int NF = LY::COUNT;
     static_assert(!TRAIN || GUIDED, "segment recording belongs to the guided instantiations");
     static_assert(Medium::kSingleSegment, "k_render_wave_wg3 serves homogeneous media (grid media: the wavefront pipeline)");
-    __shared__ float s_pool[NF * NP];
-    __shared__ unsigned short s_ring[Q_COUNT][NP];
+    __shared__ __attribute__((aligned(16))) float s_pool[NF * NP];                  // (16 bytes: CARRY copies both in 128-bit pieces)
+    __shared__ __attribute__((aligned(16))) unsigned short s_ring[Q_COUNT][NP];
     __shared__ __attribute__((aligned(16))) unsigned int s_w[W3_COUNT];
     const Pool P{s_pool, NP};
     const Medium medium = MediumMaker<Medium>::make(S, nullptr);
@@ -274,23 +300,31 @@ __device__ __forceinline__ void wg3_render(
     stage_scene_lds(S);
     if (threadIdx.x < CNT_COUNT) s_counters[threadIdx.x] = 0;
     constexpr int kImgPool = kWg3ImagePool<LY, NP>, kImgWords = kWg3ImageWords<LY, NP>, kImgStride = kWg3ImageStride<LY, NP>;
+    // the image moves in 16-byte pieces, pool then rings: kImgRounds per lane, the last round partly past the end
+    constexpr int kImgPieces = kImgWords / 4, kImgRounds = (kImgPieces + kWgBlock - 1) / kWgBlock;
+    static_assert(kImgPool % 4 == 0 && (Q_COUNT * NP / 2) % 4 == 0 && kImgStride % 4 == 0, "pool, ring block and stride of an image: multiples of 16 bytes");
+    w3_u32x4 *const pool4 = reinterpret_cast<w3_u32x4 *>(s_pool), *const ring4 = reinterpret_cast<w3_u32x4 *>(&s_ring[0][0]);
+    const int img_lane = (int)threadIdx.x;
+    __builtin_assume(img_lane >= 0 && img_lane < kWgBlock);  // (the launch bounds: only the last round of the copies tests its index)
     bool resumed = false;
     if constexpr (CARRY) {
         // RESUME: the workgroup's image of the previous launch, verbatim, if it holds paths
         const unsigned int *const img = resume + (size_t)blockIdx.x * kImgStride;
         resumed = resume != nullptr && img[kImgWords + W3_LIVE] != 0u;
         if (resumed) {
-            unsigned int *const pool32 = reinterpret_cast<unsigned int *>(s_pool);
-#pragma unroll 8
-            for (int i = threadIdx.x; i < kImgPool; i += kWgBlock) pool32[i] = img[i];
-            unsigned short *const ring16 = &s_ring[0][0];
-#pragma unroll 3
-            for (int i = threadIdx.x; i < Q_COUNT * NP / 2; i += kWgBlock) {
-                const unsigned v = img[kImgPool + i];
-                ring16[2 * i] = (unsigned short)(v & 0xffffu);
-                ring16[2 * i + 1] = (unsigned short)(v >> 16);
+            // (pool and rings lie in the image as they lie in LDS: 16-byte pieces, every load in flight before the first LDS write)
+            const w3_u32x4 *const img4 = reinterpret_cast<const w3_u32x4 *>(img);
+            w3_u32x4 piece[kImgRounds];
+#pragma unroll
+            for (int k = 0; k < kImgRounds; ++k) piece[k] = img4[w3_image_piece<kImgPieces>(img_lane + k * kWgBlock)];
+            const unsigned qword = img[kImgWords + (img_lane < W3_COUNT ? img_lane : 0)];  // (the queue words, the same way)
+            asm volatile("" ::"v"(piece[kImgRounds - 1]), "v"(qword));  // (the partial round's loads leave with the others, not inside their branches)
+#pragma unroll
+            for (int k = 0; k < kImgRounds; ++k) {
+                const int i = img_lane + k * kWgBlock;
+                if (i < kImgPieces) *(i < kImgPool / 4 ? pool4 + i : ring4 + (i - kImgPool / 4)) = piece[k];
             }
-            if (threadIdx.x < W3_COUNT) s_w[threadIdx.x] = img[kImgWords + threadIdx.x];
+            if (threadIdx.x < W3_COUNT) s_w[threadIdx.x] = qword;
             __syncthreads();
             // what belongs to the launch: every resumed path is an old one, the cursors are this launch's (a drain launch has none),
             // no chunk is in flight; ring positions rebased below NP
@@ -319,7 +353,10 @@ __device__ __forceinline__ void wg3_render(
     if constexpr (CARRY) {
         __syncthreads();
         if (threadIdx.x == 0) {
-            if (suspend == nullptr) { s_w[W3_EXH] = 1u; s_w[W3_OLD] |= kCarryDrainBit; }  // the drain launch: no tiles, nothing suspended
+            // nothing is suspended: the drain launch (no tiles either), and the launch an update of the VSP buffer follows -- its
+            // tiles as ever, the resumed paths to their ends, every workgroup out by the ordinary `exh && live == 0`
+            if (suspend == nullptr) s_w[W3_OLD] |= kCarryDrainBit;
+            if (first_sample < 0) s_w[W3_EXH] = 1u;
             s_w[W3_SUSP_LO] = (unsigned)reinterpret_cast<uintptr_t>(suspend);
             s_w[W3_SUSP_HI] = (unsigned)(reinterpret_cast<uintptr_t>(suspend) >> 32);
         }
@@ -534,6 +571,7 @@ __device__ __forceinline__ void wg3_render(
                 int seg = LI_END;
                 if (primary) {
                     int px, py, smp;
+                    float vsp0 = 0.5f;  // the pixel's entry of the VSP buffer once the buffer counts (start_path)
                     if (fresh) {
                         unsigned ty = w3_at_use(tilesX) == 1 ? tile : __umulhi(tile, tiles_magic);
                         unsigned tx = tile - ty * (unsigned)tilesX;
@@ -545,11 +583,22 @@ __device__ __forceinline__ void wg3_render(
                         smp = first_sample;
                         // the PREVIOUS one-sample launch parked this pixel's sample (vspg_render_wave: deferred resolve): it enters
                         // the film now, before this launch's sample of the pixel can (same order of additions as ever)
-                        if (w3_at_use(prev_samples) != nullptr && in_launch(px, py)) {
+                        // Everything the pixel's start reads from global memory leaves together and is waited for once: the parked sample, the
+                        // film pixel and the statistics it goes into, and the pixel's VSP -- four dependent round trips before.  The loads are
+                        // speculative (the sentinel and the ISG code decide what is stored); they stay behind in_launch: a padding lane's
+                        // pixel lies outside the buffers.
+                        if (in_launch(px, py)) {
                             const size_t pidx = (size_t)py * W + px;
-                            const float4 parked = prev_samples[pidx];
-                            if (!(CARRY && carry_sentinel(parked.w)))  // (... unless its path is still in flight: it resumed in this launch)
-                                resolve_sample(parked, film + pidx, isg_stats + pidx * VSPG_ISG_STATS);
+                            if (w3_at_use(vsp_ready) & VSP_READY) vsp0 = vsp_buf[pidx];
+                            if (w3_at_use(prev_samples) != nullptr) {
+                                float *const isg_px = isg_stats + pidx * VSPG_ISG_STATS;
+                                const float4 parked = prev_samples[pidx];
+                                float4 fpx = film[pidx], st03 = *reinterpret_cast<const float4 *>(isg_px);
+                                float2 st45 = *reinterpret_cast<const float2 *>(isg_px + 4);
+                                w3_loads_arrived(parked, fpx, st03, st45, vsp0);
+                                if (!(CARRY && carry_sentinel(parked.w)))  // (... unless its path is still in flight: it resumed in this launch)
+                                    resolve_sample_loaded(parked, fpx, st03, st45, film + pidx, isg_px);
+                            }
                         }
                     } else {
                         pxy = P.i(LY::PIXEL, slot);
@@ -559,10 +608,11 @@ __device__ __forceinline__ void wg3_render(
                     }
                     valid = in_launch(px, py) && smp < wave_end;  // tile padding: the slot stays free
                     if (valid) {
+                        if (!fresh && (w3_at_use(vsp_ready) & VSP_READY)) vsp0 = vsp_buf[(size_t)py * W + px];
                         if (w3_at_use(single_sample))
-                            start_path(S, vsp_buf, w3_at_use(vsp_ready), px, py, jump, sampler, st, &ch, isg);
+                            start_path(S, vsp0, px, py, jump, sampler, st, &ch, isg);
                         else
-                            start_path(S, vsp_buf, w3_at_use(vsp_ready), px, py, smp, sampler, st, &ch, isg);
+                            start_path(S, vsp0, px, py, smp, sampler, st, &ch, isg);
                         P.i(LY::PIXEL, slot) = pxy;
                         P.i(LY::SAMPLE, slot) = smp;
                         if constexpr (TRAIN) { (void)rec_bind(pxy); pc.rec.reset(); }
@@ -636,12 +686,22 @@ __device__ __forceinline__ void wg3_render(
         unsigned int *const susp = reinterpret_cast<unsigned int *>((uintptr_t)s_w[W3_SUSP_LO] | ((uintptr_t)s_w[W3_SUSP_HI] << 32));
         if (susp != nullptr) {
             unsigned int *const img = susp + (size_t)blockIdx.x * kImgStride;
-            if (threadIdx.x < W3_COUNT) img[kImgWords + threadIdx.x] = s_w[threadIdx.x];
+            if (threadIdx.x < W3_COUNT) ((__attribute__((address_space(1))) unsigned int *)img)[kImgWords + threadIdx.x] = s_w[threadIdx.x];
             if (s_w[W3_LIVE] != 0u) {
-                const unsigned int *const pool32 = reinterpret_cast<const unsigned int *>(s_pool);
-                for (int i = threadIdx.x; i < kImgPool; i += kWgBlock) img[i] = pool32[i];
-                const unsigned short *const ring16 = &s_ring[0][0];
-                for (int i = threadIdx.x; i < Q_COUNT * NP / 2; i += kWgBlock) img[kImgPool + i] = (unsigned)ring16[2 * i] | ((unsigned)ring16[2 * i + 1] << 16);
+                // (the address came back from LDS as two integers: said to be global memory here, or the stores are flat ones, which
+                //  count as LDS traffic too and wait for each other's reads)
+                const w3_glb_v4 img4 = (w3_glb_v4)img;
+                w3_u32x4 piece[kImgRounds];
+#pragma unroll
+                for (int k = 0; k < kImgRounds; ++k) {
+                    const int i = w3_image_piece<kImgPieces>(img_lane + k * kWgBlock);
+                    piece[k] = *(i < kImgPool / 4 ? pool4 + i : ring4 + (i - kImgPool / 4));
+                }
+#pragma unroll
+                for (int k = 0; k < kImgRounds; ++k) {
+                    const int i = img_lane + k * kWgBlock;
+                    if (i < kImgPieces) img4[i] = piece[k];
+                }
                 for (int q = 0; q < Q_F; ++q) {
                     const unsigned h = s_w[q * QC_STRIDE + QC_HEAD], n = s_w[q * QC_STRIDE + QC_COM] - h;
                     for (unsigned i = threadIdx.x; i < n && i < (unsigned)NP; i += kWgBlock) {
