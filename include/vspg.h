@@ -102,6 +102,10 @@ typedef struct VspgCamera {
 } VspgCamera;
 
 enum { VSPG_MEDIUM_NONE = 0, VSPG_MEDIUM_HOMOGENEOUS = 1, VSPG_MEDIUM_GRID = 2, VSPG_MEDIUM_NANOVDB = 3 };
+/* RGBGridMedium ("rgbgrid", src/pbrt/media.h:391-467, media.cpp:369-484): per-voxel RGB sigma_a / sigma_s / Le grids.  Of this record it
+ * reads type, g, nx / ny / nz, the bounds and the transform; its grids and scales travel in the tail of VspgScene (rgb_*, below), and
+ * sigma_a / sigma_s / Le / density here are ignored. */
+#define VSPG_MEDIUM_RGBGRID 4
 
 /* The scene's one medium.  Without medium boundaries (no transition surface, camera_outside_medium == 0) it fills the
  * scene -- ray.medium for every ray, rounds 1-3 -- otherwise a ray is in it or in no medium at all, as the camera and
@@ -247,6 +251,27 @@ typedef struct VspgScene {
      * order -- every index of a scene without them keeps its meaning. */
     float sphere_Le[VSPG_MAX_SPHERES][3];
     int32_t sphere_two_sided[VSPG_MAX_SPHERES];
+    /* RGB grid medium (medium.type == VSPG_MEDIUM_RGBGRID; RGBGridMedium, media.h:391-467, media.cpp:369-484 in the RGB rendering build:
+     * RGBUnboundedSpectrum / RGBIlluminantSpectrum hold an RGB, Sample() returns it, MaxValue() is its largest component).  THE RECORD
+     * GREW by this third tail in the same way (VSPG_ABI_VERSION stays 7); a zeroed record holds no RGB grid.
+     *   rgb_sigma_a, rgb_sigma_s, rgb_Le   HOST pointers, 3 * nx * ny * nz floats each (medium.nx / ny / nz), voxel-major with x fastest,
+     *                                      R, G, B per voxel; copied at create time.  NULL = absent: an absent sigma grid counts as the
+     *                                      constant 1 in SamplePoint and in the majorant (media.h:424-429, media.cpp:404-406).
+     *   rgb_sigma_scale                    "scale" (sigmaScale): multiplies both looked-up coefficients and the majorant
+     *   rgb_le_scale                       "Lescale": Le(p) = rgb_le_scale * Lookup(Le grid, p) when there is an Le grid and the scale is > 0
+     * Lookup is SampledGrid::Lookup(p, convert) (util/containers.h:784-801): trilinear per channel, Lerp(t, a, b) = (1 - t) a + t b over
+     * x, then y, then z, voxels outside the grid = 0.  The 16^3 majorant grid holds ONE scalar per cell for all three channels:
+     * rgb_sigma_scale * (MaxValue(sigma_a box) + MaxValue(sigma_s box)), the maximum over voxels and channels taken per grid, then summed.
+     * VSPG_EINVAL at create: both sigma grids NULL; rgb_Le without rgb_sigma_a (media.cpp:386-387, :433-434); a value in any grid that is
+     * negative, NaN or infinite; nx, ny or nz < 1; a scale that is NaN or infinite; medium.temperature set.
+     * Limits: dense storage only; vspg_renderer_update_grid and vspg_brick_info / _read return VSPG_EINVAL and
+     * vspg_renderer_set_arithmetic to a tolerance mode VSPG_ESCOPE, each with the renderer unchanged; VSPG_KERNEL=wg falls through to
+     * the per-lane kernel; one medium per scene, as ever. */
+    const float *rgb_sigma_a;
+    const float *rgb_sigma_s;
+    const float *rgb_Le;
+    float rgb_sigma_scale;
+    float rgb_le_scale;
 } VspgScene;
 
 /* ---- integrator parameters: same names and defaults as
@@ -691,11 +716,18 @@ int vspg_brick_read(VspgRenderer *r, int32_t *index, float *octets, void *stream
 #define VSPG_MEM_HOST   0
 #define VSPG_MEM_DEVICE 1
 int vspg_renderer_update_grid(VspgRenderer *r, int which, const float *values, size_t n_floats, int memory, void *stream);
-/* Read-back of the majorant grid the kernels read (test + diagnostics), x fastest: res^3 floats with res = 16 for a GRID medium,
+/* Read-back of the majorant grid the kernels read (test + diagnostics), x fastest: res^3 floats with res = 16 for a GRID or RGBGRID medium,
  * 64 for NANOVDB semantics.  host_out: n_floats == res^3 floats (HOST array); res (may be NULL) receives the resolution.
  * VSPG_EINVAL for other media or a wrong n_floats (res is still reported for a grid medium, so a caller can size its array).
  * Synchronises `stream`. */
 int vspg_majorant_read(VspgRenderer *r, float *host_out, size_t n_floats, int32_t *res, void *stream);
+/* Batch driver of a grid medium's point query (parity tests), as the path kernels evaluate it: per element i, for the render-space
+ * point p[3i..], out[10i..] = {sigma_a (3), sigma_s (3), Le (3)} of SamplePoint(p) -- Le as MediumProperties holds it, 0 for a
+ * blackbody medium, whose emission needs the path's wavelengths -- then the value of the majorant-grid cell that holds p (the cell the
+ * DDA starts in: floor(Offset(p) * res) per axis; 0 where p lies outside the bounds).  HOST arrays.  Serves GRID, NANOVDB and RGBGRID;
+ * VSPG_EINVAL for other media. */
+#define VSPG_MEDIUM_POINT_OUT 10
+int vspg_medium_point_batch(VspgRenderer *r, int n, const float *p /*3n*/, float *out /*10n*/, void *stream);
 
 /* Primitive batch (bit-exact layer): for each i computes on device
  *   hash[i]   = Hash(f[i])                      (src/pbrt/util/hash.h:100)

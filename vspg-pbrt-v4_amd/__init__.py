@@ -19,6 +19,8 @@ VSPG_MAX_QUADS = 16
 VSPG_ISG_STATS = 8
 
 MEDIUM_NONE, MEDIUM_HOMOGENEOUS, MEDIUM_GRID, MEDIUM_NANOVDB = 0, 1, 2, 3
+MEDIUM_RGBGRID = 4      # VSPG_MEDIUM_RGBGRID: per-voxel RGB sigma_a / sigma_s / Le grids in the tail of VspgScene (set_rgb_grid_medium)
+MEDIUM_POINT_OUT = 10   # VSPG_MEDIUM_POINT_OUT: floats per element of vspg_medium_point_batch
 GUIDE_MIS, GUIDE_RIS = 0, 1
 VSP_CONTRIBUTION, VSP_VARIANCE = 0, 1
 VSP_RESAMPLING, VSP_NDS = 0, 1
@@ -96,7 +98,9 @@ class VspgScene(C.Structure):
                 ("tri_flags", C.POINTER(C.c_int32)), ("n_spheres", C.c_int32), ("spheres", VspgSphere * VSPG_MAX_SPHERES),
                 ("camera_outside_medium", C.c_int32),
                 ("n_point_lights", C.c_int32), ("point_lights", VspgPointLight * VSPG_MAX_POINT_LIGHTS),
-                ("sphere_Le", f3 * VSPG_MAX_SPHERES), ("sphere_two_sided", C.c_int32 * VSPG_MAX_SPHERES)]
+                ("sphere_Le", f3 * VSPG_MAX_SPHERES), ("sphere_two_sided", C.c_int32 * VSPG_MAX_SPHERES),
+                ("rgb_sigma_a", C.POINTER(C.c_float)), ("rgb_sigma_s", C.POINTER(C.c_float)), ("rgb_Le", C.POINTER(C.c_float)),
+                ("rgb_sigma_scale", C.c_float), ("rgb_le_scale", C.c_float)]
 
 
 class VspgIntegratorParams(C.Structure):
@@ -295,6 +299,7 @@ SYMBOLS = [
     ("vspg_brick_read", C.c_int, [_vp, _P(C.c_int32), _P(C.c_float), _vp]),
     ("vspg_renderer_update_grid", C.c_int, [_vp, C.c_int, _vp, C.c_size_t, C.c_int, _vp]),
     ("vspg_majorant_read", C.c_int, [_vp, _P(C.c_float), C.c_size_t, _P(C.c_int32), _vp]),
+    ("vspg_medium_point_batch", C.c_int, [_vp, C.c_int, _P(C.c_float), _P(C.c_float), _vp]),
     ("vspg_primitives_batch", C.c_int, [_vp, C.c_int, _P(C.c_float), _P(C.c_float), _P(C.c_uint64), _P(C.c_uint32), _P(C.c_float), _vp]),
     ("vspg_renderer_training_stats", C.c_int, [_vp, _P(VspgTrainStats), _vp]),
     ("vspg_train_samples_read", C.c_int, [_vp, _P(VspgTrainSample), C.c_size_t, _P(C.c_size_t), _vp]),
@@ -495,6 +500,40 @@ def cloud_scene(xres, yres, n=256, sigma_t=8.0, albedo=0.99, g=0.877, seed=5, sh
     add_infinite_light(s, LIGHT_DISTANT, (6.0, 5.5, 5.0), (0.4, 0.8, -0.3))
     add_infinite_light(s, LIGHT_UNIFORM_INFINITE, (0.25, 0.35, 0.5))
     return s
+
+
+def set_rgb_grid_medium(scene, sigma_a=None, sigma_s=None, Le=None, p0=(0, 0, 0), p1=(1, 1, 1), g=0.0, scale=1.0, Lescale=1.0):
+    """Makes the scene's medium an RGBGridMedium ("rgbgrid"; parameter names and defaults of RGBGridMedium::Create,
+    src/pbrt/media.cpp:411-484).  sigma_a / sigma_s / Le: arrays of shape (nz, ny, nx, 3) -- x fastest, R G B per voxel -- or None
+    (absent: an absent sigma grid counts as the constant 1); all of one shape.  The arrays are kept alive on the scene."""
+    import numpy as np
+    grids = {}
+    shape = None
+    for name, a in (("sigma_a", sigma_a), ("sigma_s", sigma_s), ("Le", Le)):
+        if a is None:
+            continue
+        a = np.ascontiguousarray(a, dtype=np.float32)
+        if a.ndim != 4 or a.shape[3] != 3:
+            raise ValueError("%s must have shape (nz, ny, nx, 3)" % name)
+        if shape is not None and a.shape != shape:
+            raise ValueError("Different number of samples provided for the grids of an RGB grid medium")
+        shape = a.shape
+        grids[name] = a
+    m = scene.medium
+    m.type = MEDIUM_RGBGRID
+    m.g = g
+    if shape is not None:
+        m.nz, m.ny, m.nx = shape[:3]
+    m.bounds_min[:] = p0
+    m.bounds_max[:] = p1
+    null = C.POINTER(C.c_float)()
+    scene.rgb_sigma_a = grids["sigma_a"].ctypes.data_as(C.POINTER(C.c_float)) if "sigma_a" in grids else null
+    scene.rgb_sigma_s = grids["sigma_s"].ctypes.data_as(C.POINTER(C.c_float)) if "sigma_s" in grids else null
+    scene.rgb_Le = grids["Le"].ctypes.data_as(C.POINTER(C.c_float)) if "Le" in grids else null
+    scene.rgb_sigma_scale = scale
+    scene.rgb_le_scale = Lescale
+    scene._rgb_keepalive = grids
+    return scene
 
 
 def set_medium_transform(scene, m):
@@ -997,13 +1036,22 @@ class Renderer:
         self._update_grid(GRID_TEMPERATURE, values, stream)
 
     def majorant(self, stream=None):
-        """The majorant grid the kernels read (vspg_majorant_read): [R, R, R] float32 indexed z, y, x; R = 16 (GRID) or 64 (NANOVDB)."""
+        """The majorant grid the kernels read (vspg_majorant_read): [R, R, R] float32 indexed z, y, x; R = 16 (GRID, RGBGRID) or 64 (NANOVDB)."""
         import numpy as np
         R = 64 if self.scene.medium.type == MEDIUM_NANOVDB else 16
         out = np.empty((R, R, R), dtype=np.float32)
         res = C.c_int32(0)
         _check(self.lib, self.lib.vspg_majorant_read(self.h, out.ctypes.data_as(_P(C.c_float)), out.size, C.byref(res), _vp(stream or 0)))
         assert res.value == R
+        return out
+
+    def medium_point_batch(self, p):
+        """[n, 10] float32 per render-space point of p [n, 3]: sigma_a, sigma_s, Le (3 each) of SamplePoint(p) and the value of the
+        majorant cell that holds p, 0 outside the bounds (vspg_medium_point_batch); grid media."""
+        import numpy as np
+        p = np.ascontiguousarray(p, dtype=np.float32).reshape(-1, 3)
+        out = np.zeros((len(p), MEDIUM_POINT_OUT), dtype=np.float32)
+        _check(self.lib, self.lib.vspg_medium_point_batch(self.h, len(p), p.ctypes.data_as(_P(C.c_float)), out.ctypes.data_as(_P(C.c_float)), _vp(0)))
         return out
 
     def primitives_batch(self, f, g):

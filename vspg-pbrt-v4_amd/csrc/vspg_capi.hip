@@ -32,6 +32,7 @@
 #ifdef VSPG_SINGLE_TU  // diagnostic builds that read device-side globals of the pipeline kernels (VSPG_WF_STATS, VSPG_PROFILE, VSPG_WF_DEBUG)
 #include "vspg_wf_grid.hip"
 #include "vspg_wf_nvdb.hip"
+#include "vspg_wf_rgbgrid.hip"
 #include "vspg_wg3_exact.hip"
 #endif
 
@@ -305,6 +306,8 @@ struct VspgRenderer {
     float *le_scale = nullptr;  // emissive GridMedium: LeScale grid
     float *temperature = nullptr;  // temperature grid (raw samples)
     float *majorant = nullptr;  // 16^3 majorant grid
+    float4 *rgb_oct[2] = {nullptr, nullptr};  // RGB grid medium: the octets of the sigma_a / sigma_s grid (vspg_rgbgrid.h), null = absent
+    float *rgb_Le = nullptr;                  // ... its Le grid, raw
     float *env_buf[VSPG_MAX_INFINITE_LIGHTS] = {nullptr, nullptr, nullptr, nullptr};  // image infinite lights: one allocation per light (DEnvLight's arrays)
     DTri *tris = nullptr;          // triangle soup in BVH leaf order + the BVH (depth-first, skip links)
     DBvh4Node *bvh = nullptr;
@@ -489,6 +492,7 @@ static int wf_render_pass(VspgRenderer *r, const KernelChoice &c, const PixelWin
     // (tolerance modes: vspg_renderer_set_arithmetic accepted the renderer only if vspg_fast.hip holds its instantiation)
     const int rc = r->arith == VSPG_ARITH_FAST_WEIGHTS ? vspg_arith1_wf_grid(&L, grey ? 1 : 0)
                    : r->arith == VSPG_ARITH_FAST     ? vspg_arith2_wf_grid(&L, grey ? 1 : 0)
+                   : c.medium == MediumInst::RgbGrid ? wf_dispatch_rgbgrid(L, guided, train)
                    : nvdb                            ? wf_dispatch_nvdb(L, guided, train, grey)
                                                      : wf_dispatch_grid(L, guided, train, grey);
     if (rc == WF_E_NOT_DRAINED)
@@ -526,6 +530,30 @@ struct RoctxRange {
     explicit RoctxRange(const char *name) { if (g_roctx.push) g_roctx.push(name); }
     ~RoctxRange() { if (g_roctx.pop) g_roctx.pop(); }
 };
+// vspg_medium_point_batch (include/vspg.h): SamplePoint as the path kernels call it, and the majorant cell that holds the point
+template <class Medium>
+__global__ __launch_bounds__(kBlock) void k_medium_point_batch(const DScene *__restrict__ Sp, int n, const float *__restrict__ p, float *__restrict__ out) {
+    const DScene &S = *Sp;
+    stage_scene_lds(S);
+    __syncthreads();
+    const int i = blockIdx.x * kBlock + threadIdx.x;
+    if (i >= n) return;
+    const Medium medium = MediumMaker<Medium>::make(S, S.majorant);
+    const V3 pr = ld3(p + 3 * (size_t)i);
+    const MediumProps mp = medium.sample_point(pr);
+    const V3 o = medium.offset(medium.to_medium(pr));
+    constexpr int R = Medium::kRes;
+    float maj = 0.f;
+    if (o.x >= 0.f && o.x <= 1.f && o.y >= 0.f && o.y <= 1.f && o.z >= 0.f && o.z <= 1.f) {  // Inside(p, bounds); the cell as the DDA's set-up clamps it
+        auto cell = [](float v) { return (int)(v < 0 ? 0.f : (v > (float)(R - 1) ? (float)(R - 1) : v)); };
+        maj = S.majorant[cell(o.x * R) + R * (cell(o.y * R) + R * cell(o.z * R))];
+    }
+    float *q = out + (size_t)i * VSPG_MEDIUM_POINT_OUT;
+    q[0] = mp.sigma_a.r; q[1] = mp.sigma_a.g; q[2] = mp.sigma_a.b;
+    q[3] = mp.sigma_s.r; q[4] = mp.sigma_s.g; q[5] = mp.sigma_s.b;
+    q[6] = mp.Le.r; q[7] = mp.Le.g; q[8] = mp.Le.b;
+    q[9] = maj;
+}
 // A kernel instantiation as a value: what vspg_render_window's launch lambdas are handed.  Only the tuples named there are built -- each
 // further one costs minutes of compile time.
 template <class M, bool G = false, bool T = false, int NP = 0, int BLK = 0, int WV = 0>
@@ -562,7 +590,7 @@ int vspg_renderer_create(const VspgScene *scene, const VspgIntegratorParams *par
     {
         auto same = [](const float *v) { return std::memcmp(&v[0], &v[1], 4) == 0 && std::memcmp(&v[1], &v[2], 4) == 0; };
         const VspgMedium &m = r->scene.medium;
-        r->medium_grey = m.type != VSPG_MEDIUM_NONE && same(m.sigma_a) && same(m.sigma_s) && same(m.Le) && !m.temperature && !getenv("VSPG_NO_GREY");
+        r->medium_grey = m.type != VSPG_MEDIUM_NONE && m.type != VSPG_MEDIUM_RGBGRID && same(m.sigma_a) && same(m.sigma_s) && same(m.Le) && !m.temperature && !getenv("VSPG_NO_GREY");
         r->surfaces_grey = !getenv("VSPG_NO_GREY_KD");
         r->null_zero = m.type == VSPG_MEDIUM_HOMOGENEOUS && !getenv("VSPG_NO_NULLZERO");
         for (int k = 0; k < 3; ++k) r->null_zero = r->null_zero && !(r->hscene.sigma_n_raw[k] > 0) && r->hscene.sigma_n_raw[k] == r->hscene.sigma_n_raw[k];
@@ -657,6 +685,32 @@ int vspg_renderer_create(const VspgScene *scene, const VspgIntegratorParams *par
         }
         r->scene.medium.le_scale = nullptr;
         r->scene.medium.temperature = nullptr;  // (the host array belongs to the caller)
+    }
+    if (scene->medium.type == VSPG_MEDIUM_RGBGRID) {  // majorants and the storage image are the host's (vspg_scene_build.hip); dense, no index
+        const VspgMedium &m = scene->medium;
+        const std::vector<float> maj = build_majorant_grid_rgb(*scene);
+        CK(hipMalloc(&r->majorant, maj.size() * sizeof(float)));
+        CK(hipMemcpy(r->majorant, maj.data(), maj.size() * sizeof(float), hipMemcpyHostToDevice));
+        r->hscene.majorant = r->majorant;
+        int bnx, bny, bnz;
+        rgb_brick_counts(m, &bnx, &bny, &bnz);
+        r->hscene.bnx = bnx; r->hscene.bny = bny; r->hscene.bnz = bnz;
+        const float *src[2] = {scene->rgb_sigma_a, scene->rgb_sigma_s};
+        for (int k = 0; k < 2; ++k)
+            if (src[k]) {
+                const std::vector<float> img = build_rgb_octets(src[k], m);
+                CK(hipMalloc(&r->rgb_oct[k], img.size() * sizeof(float)));
+                CK(hipMemcpy(r->rgb_oct[k], img.data(), img.size() * sizeof(float), hipMemcpyHostToDevice));
+            }
+        r->hscene.rgb_oct_a = r->rgb_oct[0];
+        r->hscene.rgb_oct_s = r->rgb_oct[1];
+        if (scene->rgb_Le) {
+            const size_t n3 = (size_t)m.nx * m.ny * m.nz * 3;
+            CK(hipMalloc(&r->rgb_Le, n3 * sizeof(float)));
+            CK(hipMemcpy(r->rgb_Le, scene->rgb_Le, n3 * sizeof(float), hipMemcpyHostToDevice));
+            r->hscene.rgb_Le = r->rgb_Le;
+        }
+        r->scene.rgb_sigma_a = r->scene.rgb_sigma_s = r->scene.rgb_Le = nullptr;  // (the host arrays belong to the caller)
     }
     if (scene->n_triangles > 0) {
         std::vector<DTri> sorted;
@@ -821,6 +875,8 @@ int vspg_renderer_destroy(VspgRenderer *r) {
     if (r->le_scale) (void)hipFree(r->le_scale);
     if (r->temperature) (void)hipFree(r->temperature);
     if (r->majorant) (void)hipFree(r->majorant);
+    for (int k = 0; k < 2; ++k) if (r->rgb_oct[k]) (void)hipFree(r->rgb_oct[k]);
+    if (r->rgb_Le) (void)hipFree(r->rgb_Le);
     for (int k = 0; k < VSPG_MAX_INFINITE_LIGHTS; ++k) if (r->env_buf[k]) (void)hipFree(r->env_buf[k]);
     if (r->fe_ref) (void)hipFree(r->fe_ref);
     if (r->fe_partials) (void)hipFree(r->fe_partials);
@@ -1079,6 +1135,7 @@ int vspg_render_window(VspgRenderer *r, int x0, int y0, int x1, int y1, int wave
         case MediumInst::NanoDense: launch_guided_or_not(KernelInst<NanoDenseMedium>{}); break;
         case MediumInst::Grid: launch_guided_or_not(KernelInst<GridMedium>{}); break;
         case MediumInst::GridGrey: launch(KernelInst<GridMediumGrey>{}); break;
+        case MediumInst::RgbGrid: launch_guided_or_not(KernelInst<RgbGridMedium>{}); break;
         case MediumInst::Homogeneous: launch_guided_or_not(KernelInst<HomogeneousMedium>{}); break;
         case MediumInst::HomogeneousGreySceneNullZero:  // (guided renders only)
             if (c.train) launch(KernelInst<NullZero, true, true>{});
@@ -1595,6 +1652,10 @@ int vspg_trace_paths(VspgRenderer *r, int n, const int32_t *pixel_xy, const int3
         const TraceLaunch T{r->dscene, r->vsp, r->vsp_ready | VSP_NO_FEED, n, (const int32_t *)dp.p, (const int32_t *)ds.p, (float *)dl.p, (int32_t *)dg.p, s, grid ? 1 : 0};
         const int trc = r->arith == VSPG_ARITH_FAST_WEIGHTS ? vspg_arith1_trace(&T) : vspg_arith2_trace(&T);
         if (trc != 0) return fail(VSPG_EHIP, std::string("k_trace_paths: ") + hipGetErrorName((hipError_t)trc));
+    } else if (r->scene.medium.type == VSPG_MEDIUM_RGBGRID) {  // (the kernel lives in vspg_wf_rgbgrid.hip)
+        const TraceLaunch T{r->dscene, r->vsp, r->vsp_ready | VSP_NO_FEED, n, (const int32_t *)dp.p, (const int32_t *)ds.p, (float *)dl.p, (int32_t *)dg.p, s, 0};
+        const int trc = trace_launch_rgbgrid(T, guided);
+        if (trc != 0) return fail(VSPG_EHIP, std::string("k_trace_paths: ") + hipGetErrorName((hipError_t)trc));
     } else
     if (nvdb && guided) VSPG_LAUNCH_TRACE(NanoDenseMedium, true);
     else if (nvdb) VSPG_LAUNCH_TRACE(NanoDenseMedium, false);
@@ -1644,6 +1705,9 @@ int vspg_sample_tmaj_batch(VspgRenderer *r, int variant, int n, const VspgTmajQu
                            (const VspgTmajQuery *)dq.p, (VspgTmajResult *)dr.p);
     else if (r->scene.medium.type == VSPG_MEDIUM_GRID)
         hipLaunchKernelGGL(k_tmaj_batch<GridMedium>, dim3((n + kBlock - 1) / kBlock), dim3(kBlock), 0, s, r->dscene, variant, n,
+                           (const VspgTmajQuery *)dq.p, (VspgTmajResult *)dr.p);
+    else if (r->scene.medium.type == VSPG_MEDIUM_RGBGRID)
+        hipLaunchKernelGGL(k_tmaj_batch<RgbGridMedium>, dim3((n + kBlock - 1) / kBlock), dim3(kBlock), 0, s, r->dscene, variant, n,
                            (const VspgTmajQuery *)dq.p, (VspgTmajResult *)dr.p);
     else
         hipLaunchKernelGGL(k_tmaj_batch<HomogeneousMedium>, dim3((n + kBlock - 1) / kBlock), dim3(kBlock), 0, s, r->dscene, variant, n,
@@ -1709,9 +1773,30 @@ int vspg_brick_read(VspgRenderer *r, int32_t *index, float *octets, void *stream
     return 0;
 }
 
+int vspg_medium_point_batch(VspgRenderer *r, int n, const float *p, float *out, void *stream) {
+    if (!r || n < 0 || (n > 0 && (!p || !out))) return fail(VSPG_EINVAL, "bad arguments");
+    const int type = r->scene.medium.type;
+    if (type != VSPG_MEDIUM_GRID && type != VSPG_MEDIUM_NANOVDB && type != VSPG_MEDIUM_RGBGRID) return fail(VSPG_EINVAL, "renderer has no grid medium");
+    if (n == 0) return 0;
+    HIPCHK(hipSetDevice(r->cfg.device));
+    hipStream_t s = (hipStream_t)stream;
+    DevBuf dp, dout;
+    HIPCHK(hipMalloc(&dp.p, (size_t)n * 3 * sizeof(float)));
+    HIPCHK(hipMalloc(&dout.p, (size_t)n * VSPG_MEDIUM_POINT_OUT * sizeof(float)));
+    HIPCHK(hipMemcpyAsync(dp.p, p, (size_t)n * 3 * sizeof(float), hipMemcpyHostToDevice, s));
+    const dim3 grid((unsigned)((n + kBlock - 1) / kBlock)), block(kBlock);
+    if (type == VSPG_MEDIUM_RGBGRID) hipLaunchKernelGGL(k_medium_point_batch<RgbGridMedium>, grid, block, 0, s, r->dscene, n, (const float *)dp.p, (float *)dout.p);
+    else if (type == VSPG_MEDIUM_NANOVDB) hipLaunchKernelGGL(k_medium_point_batch<NanoDenseMedium>, grid, block, 0, s, r->dscene, n, (const float *)dp.p, (float *)dout.p);
+    else hipLaunchKernelGGL(k_medium_point_batch<GridMedium>, grid, block, 0, s, r->dscene, n, (const float *)dp.p, (float *)dout.p);
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipMemcpyAsync(out, dout.p, (size_t)n * VSPG_MEDIUM_POINT_OUT * sizeof(float), hipMemcpyDeviceToHost, s));
+    HIPCHK(hipStreamSynchronize(s));
+    return 0;
+}
+
 int vspg_majorant_read(VspgRenderer *r, float *host_out, size_t n_floats, int32_t *res, void *stream) {
     if (!r || !host_out) return fail(VSPG_EINVAL, "null argument");
-    if (!has_bricks(r)) return fail(VSPG_EINVAL, "renderer has no grid medium");
+    if (!has_bricks(r) && r->scene.medium.type != VSPG_MEDIUM_RGBGRID) return fail(VSPG_EINVAL, "renderer has no grid medium");
     const int R = majorant_res(r->scene.medium);
     if (res) *res = R;
     if (n_floats != (size_t)R * R * R) return fail(VSPG_EINVAL, "n_floats is not the majorant grid's resolution cubed");

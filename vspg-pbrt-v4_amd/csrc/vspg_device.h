@@ -881,6 +881,13 @@ struct DScene {
     int32_t n_sphere_lights;
     int32_t light_spheres[VSPG_MAX_SPHERES];  // k-th emissive sphere -> sphere index (as light_quads for rectangles)
     DSphereLight sphere_light[VSPG_MAX_SPHERES];
+    // RGB grid medium (RgbGridMediumT, vspg_rgbgrid.h; medium_type == VSPG_MEDIUM_RGBGRID): per sigma grid the "RGB octets" of every base
+    // voxel in the brick order of `octets` above (bnx, bny, bnz), null = the grid is absent (the constant 1); the Le grid is the
+    // caller's raw array (3 floats per voxel), null = not emissive.  nx, ny, nz, the bounds, minv, g and `majorant` are shared with the
+    // scalar grid media.  Behind everything else: no kernel of another medium reads here.
+    const float4 *rgb_oct_a, *rgb_oct_s;
+    const float *rgb_Le;
+    float rgb_sigma_scale, rgb_le_scale;
 };
 // the length of the scene's light list (full-scene kernels): one line per light kind
 __host__ __device__ __forceinline__ int light_list_size(const DScene &S) { return S.n_lights + S.n_inf + S.n_point + S.n_sphere_lights; }

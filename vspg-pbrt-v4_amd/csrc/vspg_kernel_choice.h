@@ -45,7 +45,9 @@ enum class Family { Lane, Wg, Wg2, Wg3, WfWalk, WfSegmentVertex };
 // HomogeneousMediumT<0,false>: rectangle scenes with area lights only; HomogeneousGrey = <1,false>: sigma_a, sigma_s, Le bitwise grey, the
 // broadcast-spectrum instantiation; HomogeneousGreyScene = <2,false>: ... and every Kd bitwise grey, beta is grey by construction too;
 // HomogeneousGreySceneNullZero = <2,true>: ... and the null-collision coefficient is exactly 0.  NanoDenseGrey: the pipeline only.
-enum class MediumInst { Homogeneous, HomogeneousSimple, HomogeneousGrey, HomogeneousGreyScene, HomogeneousGreySceneNullZero, Grid, GridGrey, NanoDense, NanoDenseGrey };
+// RgbGrid: RgbGridMediumT (vspg_rgbgrid.h), the pipeline and the per-lane kernel; it has no grey layout, no workgroup kernel and no
+// tolerance-mode instantiation.
+enum class MediumInst { Homogeneous, HomogeneousSimple, HomogeneousGrey, HomogeneousGreyScene, HomogeneousGreySceneNullZero, Grid, GridGrey, NanoDense, NanoDenseGrey, RgbGrid };
 
 struct KernelChoice {
     Family family = Family::Lane;
@@ -62,6 +64,7 @@ struct KernelChoice {
 // The only place that decides.
 inline KernelChoice choose_kernel(const ChoiceFacts &f, const ChoiceEnv &env) {
     const bool hom = f.medium_type == VSPG_MEDIUM_HOMOGENEOUS, grid = f.medium_type == VSPG_MEDIUM_GRID, nvdb = f.medium_type == VSPG_MEDIUM_NANOVDB;
+    const bool rgbgrid = f.medium_type == VSPG_MEDIUM_RGBGRID;
     const bool k_unset = env.kernel.empty(), k_wg = env.kernel == "wg", k_wf = env.kernel == "wf";
     // a scene of rectangles and area lights only, one medium filling it: what the workgroup kernel's specialised instantiations are built for
     // (HomogeneousMediumT::kSimpleScene).  Triangle hits carry a per-hit error bound the LDS pool record has no room for; medium boundaries,
@@ -79,10 +82,10 @@ inline KernelChoice choose_kernel(const ChoiceFacts &f, const ChoiceEnv &env) {
     // "wf" = the wavefront pipeline: heterogeneous media.  Default for those; VSPG_KERNEL=lane|wg selects the single-kernel schedulers
     // instead (kept as cross-checks).  Guided builds too, training passes included (segment recording in the dense kernels), guided
     // Russian roulette (round 3: the vertex kernel reads the pixel's contribution estimate) and, in its own shape, NDS / NDS+.
-    if ((grid || nvdb) && (k_unset || k_wf)) {
+    if ((grid || nvdb || rgbgrid) && (k_unset || k_wf)) {
         c.family = f.resampling ? Family::WfWalk : Family::WfSegmentVertex;
         const bool grey = !f.guided && f.medium_grey;
-        c.medium = nvdb ? (grey ? MediumInst::NanoDenseGrey : MediumInst::NanoDense) : (grey ? MediumInst::GridGrey : MediumInst::Grid);
+        c.medium = rgbgrid ? MediumInst::RgbGrid : nvdb ? (grey ? MediumInst::NanoDenseGrey : MediumInst::NanoDense) : (grey ? MediumInst::GridGrey : MediumInst::Grid);
         // both walks of an iteration as ONE kernel where the job lists are short or a third kernel sits in the chain (boundary scenes,
         // guided pipelines); side by side on two streams for dense unguided clouds (k_wf_walk, vspg_wavefront.h: measured both ways).
         // VSPG_WF_MERGED=0|1 overrides.
@@ -121,7 +124,7 @@ inline KernelChoice choose_kernel(const ChoiceFacts &f, const ChoiceEnv &env) {
     // per wave).  VSPG_KERNEL=wg|lane overrides (unguided builds only).  Not for a grid with a TrBuffer (its running mean needs a pixel's
     // samples in order: the per-lane kernel owns a pixel per launch) or with a temperature grid (blackbody emission needs the path's
     // wavelength sample, which k_render_wave_wg's pool record does not carry).
-    if (simple && !f.guided && !nvdb && (k_wg || (k_unset && !grid)) && !(grid && (f.has_temperature || f.tr_calc))) {
+    if (simple && !f.guided && !nvdb && !rgbgrid && (k_wg || (k_unset && !grid)) && !(grid && (f.has_temperature || f.tr_calc))) {
         // Which scheduler: k_render_wave_wg2 serves every homogeneous configuration since round 3 -- with the shared
         // tile head it beat k_render_wave_wg on the unguided workload too (0.776 against 0.808 ms); VSPG_WG_SCHED=1 selects k_render_wave_wg
         // for the unguided instantiations, grid media (under VSPG_KERNEL=wg only) stay on it.  Round 5: the barrier-free k_render_wave_wg3
@@ -135,8 +138,10 @@ inline KernelChoice choose_kernel(const ChoiceFacts &f, const ChoiceEnv &env) {
         c.arith_covered = !cross_check && !f.tr_calc;
         return c;
     }
-    // the per-lane kernel: everything else
-    c.medium = nvdb                             ? MediumInst::NanoDense
+    // the per-lane kernel: everything else -- an RGB grid medium under VSPG_KERNEL=wg included (no workgroup kernel is built for it: the
+    // branch above leaves it out)
+    c.medium = rgbgrid                          ? MediumInst::RgbGrid
+               : nvdb                           ? MediumInst::NanoDense
                : grid                           ? (!f.guided && f.medium_grey ? MediumInst::GridGrey : MediumInst::Grid)
                : f.guided && guided_grey_simple ? MediumInst::HomogeneousGreySceneNullZero
                                                 : MediumInst::Homogeneous;
@@ -148,7 +153,7 @@ inline std::string kernel_name(const KernelChoice &c) {
     // the pipeline is named by its walk kernel: k_wf_dist_walk (beside k_wf_shadow_walk), or k_wf_walk where one kernel runs both
     static const char *const family[] = {"k_render_wave", "k_render_wave_wg", "k_render_wave_wg2", "k_render_wave_wg3", "k_wf_dist_walk", "k_wf_segment_vertex"};
     static const char *const medium[] = {"HomogeneousMedium", "HomogeneousMediumT<0,false>", "HomogeneousMediumT<1,false>", "HomogeneousMediumT<2,false>",
-                                         "HomogeneousMediumT<2,true>", "GridMedium", "GridMediumGrey", "NanoDenseMedium", "NanoDenseMediumGrey"};
+                                         "HomogeneousMediumT<2,true>", "GridMedium", "GridMediumGrey", "NanoDenseMedium", "NanoDenseMediumGrey", "RgbGridMedium"};
     // (the guided workgroup kernel over a non-grey scene has always been reported under the full-scene medium's name)
     const MediumInst m = c.medium == MediumInst::HomogeneousSimple && c.guided ? MediumInst::Homogeneous : c.medium;
     return std::string(c.family == Family::WfWalk && c.wf_merged ? "k_wf_walk" : family[(int)c.family]) + "<" + medium[(int)m] + (c.guided ? ",guided" : "") +

@@ -6,6 +6,7 @@
 
 #include "vspg_device.h"
 #include "vspg_lightsampler.h"
+#include "vspg_rgbgrid.h"
 
 #pragma GCC visibility push(hidden)  // shared between the library's units, not part of its ABI
 namespace vspg_host {
@@ -50,6 +51,12 @@ int majorant_res(const VspgMedium &m);
 std::vector<int2> majorant_axis_ranges(const VspgMedium &m);
 std::vector<float> build_majorant_grid(const VspgMedium &m);
 std::vector<float> build_majorant_grid_nvdb(const VspgMedium &m);
+// RGBGridMedium (VSPG_MEDIUM_RGBGRID, vspg_rgbgrid.h): the refusals of create (validate calls it), the 16^3 majorants, and the device
+// image of one RGB grid -- bnx * bny * bnz bricks of 512 octets of 8 float4 (32 floats)
+int validate_rgb_grid(const VspgScene &sc);
+std::vector<float> build_majorant_grid_rgb(const VspgScene &sc);
+void rgb_brick_counts(const VspgMedium &m, int *bnx, int *bny, int *bnz);
+std::vector<float> build_rgb_octets(const float *rgb, const VspgMedium &m);
 
 // ---- image infinite light: the host side of vspg_envlight.h ----------------------------------------------------------------
 // The arrays of one DEnvLight, laid out in one buffer: texels | func | cdf | mfunc | mcdf

@@ -727,6 +727,11 @@ void build_dscene(const VspgScene &sc, const VspgIntegratorParams &prm, const Vs
     D->seed = cfg.seed;
     D->shard_index = cfg.shard_index;
     D->shard_count = cfg.shard_count < 1 ? 1 : cfg.shard_count;
+    // RGB grid medium: the scales; create points the grids at their device storage
+    D->rgb_oct_a = D->rgb_oct_s = nullptr;
+    D->rgb_Le = nullptr;
+    D->rgb_sigma_scale = sc.medium.type == VSPG_MEDIUM_RGBGRID ? sc.rgb_sigma_scale : 0.f;
+    D->rgb_le_scale = sc.medium.type == VSPG_MEDIUM_RGBGRID ? sc.rgb_le_scale : 0.f;
     lsb::build(sc, prm, D);  // LightSampler::Create(prm.lightsampler, lights) (lightsamplers.cpp:49-64)
 }
 
@@ -1038,6 +1043,95 @@ std::vector<float> build_majorant_grid_nvdb(const VspgMedium &m) {
             }
     return maj;
 }
+
+// ---- RGBGridMedium ("rgbgrid", media.h:391-467): what create derives on the host -- the refusals, the majorants, the storage image.
+// Create's error triggers (media.cpp:418-445) as far as they survive in a record of pointers: the sample counts are nx * ny * nz by
+// contract, so what is left is "sigma_a and/or sigma_s" (:418-420) and "sigma_a if Le" (:433-434, the constructor's CHECK :386-387).
+int validate_rgb_grid(const VspgScene &sc) {
+    const VspgMedium &m = sc.medium;
+    if (m.nx <= 0 || m.ny <= 0 || m.nz <= 0) return fail(VSPG_EINVAL, "RGB grid medium needs nx, ny, nz > 0");
+    if ((long long)m.nx * m.ny * m.nz > (1ll << 31)) return fail(VSPG_EINVAL, "RGB grid too large");
+    if (!sc.rgb_sigma_a && !sc.rgb_sigma_s) return fail(VSPG_EINVAL, "RGB grid requires \"sigma_a\" and/or \"sigma_s\" parameter values.");
+    if (sc.rgb_Le && !sc.rgb_sigma_a) return fail(VSPG_EINVAL, "RGB grid requires \"sigma_a\" if \"Le\" value provided.");
+    if (m.temperature) return fail(VSPG_EINVAL, "an RGB grid medium has no temperature grid");
+    if (!std::isfinite(sc.rgb_sigma_scale) || !std::isfinite(sc.rgb_le_scale)) return fail(VSPG_EINVAL, "RGB grid medium: \"scale\" / \"Lescale\" is not finite");
+    for (int k = 0; k < 3; ++k)
+        if (!(m.bounds_max[k] > m.bounds_min[k])) return fail(VSPG_EINVAL, "grid medium bounds must have positive extent");
+    if (m.has_transform) {
+        const float *a = m.render_from_medium, *b = m.medium_from_render;
+        if (a[12] != 0 || a[13] != 0 || a[14] != 0 || a[15] != 1 || b[12] != 0 || b[13] != 0 || b[14] != 0 || b[15] != 1)
+            return fail(VSPG_EINVAL, "renderFromMedium must be affine (last row 0 0 0 1)");
+        for (int k = 0; k < 16; ++k)
+            if (!(a[k] == a[k]) || !(b[k] == b[k])) return fail(VSPG_EINVAL, "renderFromMedium holds a NaN");
+    }
+    const size_t n3 = (size_t)m.nx * m.ny * m.nz * 3;
+    const float *grids[3] = {sc.rgb_sigma_a, sc.rgb_sigma_s, sc.rgb_Le};
+    const char *names[3] = {"sigma_a", "sigma_s", "Le"};
+    for (int gk = 0; gk < 3; ++gk)
+        if (grids[gk])
+            for (size_t i = 0; i < n3; ++i)
+                if (!std::isfinite(grids[gk][i]) || grids[gk][i] < 0)
+                    return fail(VSPG_EINVAL, std::string("RGB grid medium: \"") + names[gk] + "\" holds a value that is negative or not finite");
+    return 0;
+}
+
+// RGBGridMedium constructor, "Initialize majorantGrid" (media.cpp:395-408): per cell sigmaScale * (MaxValue(sigma_a box, max) +
+// MaxValue(sigma_s box, max)) with SampledGrid::MaxValue(bounds, convert) (containers.h:837-854) -- maxValue starts at Lookup(pi[0])
+// and the box is GridMedium's (majorant_axis_ranges) -- convert = the largest of R, G, B; an absent grid counts as 1.
+std::vector<float> build_majorant_grid_rgb(const VspgScene &sc) {
+    const VspgMedium &m = sc.medium;
+    const int R = kMajRes;
+    std::vector<float> maj((size_t)R * R * R);
+    const std::vector<int2> ranges = majorant_axis_ranges(m);
+    auto at = [&](const float *g, int x, int y, int z) -> float {  // Lookup(Point3i, convert): RGB{} outside the grid
+        if (x < 0 || y < 0 || z < 0 || x >= m.nx || y >= m.ny || z >= m.nz) return 0.f;
+        const float *v = g + (((size_t)z * m.ny + y) * m.nx + x) * 3;
+        return std::max(std::max(v[0], v[1]), v[2]);  // RGBUnboundedSpectrum::MaxValue in the RGB build
+    };
+    auto max_value = [&](const float *g, int2 rx, int2 ry, int2 rz) -> float {
+        float mx = at(g, rx.x, ry.x, rz.x);
+        for (int zz = rz.x; zz <= rz.y; ++zz)
+            for (int yy = ry.x; yy <= ry.y; ++yy)
+                for (int xx = rx.x; xx <= rx.y; ++xx) mx = std::max(mx, at(g, xx, yy, zz));
+        return mx;
+    };
+    for (int z = 0; z < R; ++z)
+        for (int y = 0; y < R; ++y)
+            for (int x = 0; x < R; ++x) {
+                const int2 rx = ranges[x], ry = ranges[R + y], rz = ranges[2 * R + z];
+                const float ma = sc.rgb_sigma_a ? max_value(sc.rgb_sigma_a, rx, ry, rz) : 1.f;
+                const float ms = sc.rgb_sigma_s ? max_value(sc.rgb_sigma_s, rx, ry, rz) : 1.f;
+                volatile float sum = ma + ms;  // volatile: one rounding per operation, as the kernels' flags give
+                maj[x + R * (y + R * z)] = sc.rgb_sigma_scale * sum;
+            }
+    return maj;
+}
+
+// The device image of one RGB grid (vspg_rgbgrid.h): per base voxel in [-1, n - 1]^3 its eight RGB corners as float4, in brick order;
+// bn = (n + 8) / 8 bricks per axis, every brick stored, zeros outside the grid and in a brick's unused slots.
+void rgb_brick_counts(const VspgMedium &m, int *bnx, int *bny, int *bnz) {
+    *bnx = (m.nx + 1 + 7) / 8;
+    *bny = (m.ny + 1 + 7) / 8;
+    *bnz = (m.nz + 1 + 7) / 8;
+}
+std::vector<float> build_rgb_octets(const float *rgb, const VspgMedium &m) {
+    int bnx, bny, bnz;
+    rgb_brick_counts(m, &bnx, &bny, &bnz);
+    std::vector<float> img((size_t)bnx * bny * bnz * 512u * 32u, 0.f);
+    for (int oz = 0; oz <= m.nz; ++oz)
+        for (int oy = 0; oy <= m.ny; ++oy)
+            for (int ox = 0; ox <= m.nx; ++ox) {
+                float *o = img.data() + rgb_octet_slot(ox, oy, oz, bnx, bny) * 32u;
+                for (int c = 0; c < 8; ++c) {
+                    const int x = ox - 1 + (c & 1), y = oy - 1 + ((c >> 1) & 1), z = oz - 1 + (c >> 2);
+                    if (x < 0 || y < 0 || z < 0 || x >= m.nx || y >= m.ny || z >= m.nz) continue;
+                    const float *v = rgb + (((size_t)z * m.ny + y) * m.nx + x) * 3;
+                    o[4 * c] = v[0]; o[4 * c + 1] = v[1]; o[4 * c + 2] = v[2];
+                }
+            }
+    return img;
+}
+
 int validate(const VspgScene *scene, const VspgIntegratorParams *p, const VspgRenderConfig *cfg) {
     if (!scene || !p || !cfg) return fail(VSPG_EINVAL, "null argument");
     if (cfg->xres <= 0 || cfg->yres <= 0) return fail(VSPG_EINVAL, "film resolution must be positive");
@@ -1091,6 +1185,8 @@ int validate(const VspgScene *scene, const VspgIntegratorParams *p, const VspgRe
         if (m.type == VSPG_MEDIUM_GRID && (m.temperature || m.Le[0] != 0 || m.Le[1] != 0 || m.Le[2] != 0))
             if (m.le_scale && (m.le_nx <= 0 || m.le_ny <= 0 || m.le_nz <= 0 || (long long)m.le_nx * m.le_ny * m.le_nz > (1ll << 31)))
                 return fail(VSPG_EINVAL, "emissive grid medium: bad Lescale grid size");
+    } else if (scene->medium.type == VSPG_MEDIUM_RGBGRID) {
+        if (const int rc = validate_rgb_grid(*scene)) return rc;
     } else if (scene->medium.type != VSPG_MEDIUM_NONE && scene->medium.type != VSPG_MEDIUM_HOMOGENEOUS)
         return fail(VSPG_EINVAL, "unknown medium type");
     if (scene->n_triangles < 0 || scene->n_triangles > (1 << 27)) return fail(VSPG_EINVAL, "n_triangles out of range");

@@ -1,9 +1,10 @@
 // vspg_wf_launch.h -- the host side of one wavefront-pipeline pass: the kernel launches of vspg_wavefront.h in order.
 //
 // The pipeline's kernels are the bulk of the library's device code (dense kernels x {medium layout, grey, guided, training,
-// medium boundaries}): they are instantiated in translation units of their own -- vspg_wf_grid.hip (GridMedium) and
-// vspg_wf_nvdb.hip (NanoVDB semantics) -- which `make -j` compiles beside vspg_capi.hip.  vspg_capi.hip prepares a pass (buffers,
-// grid sizes, streams) as a plain WfLaunch and calls wf_dispatch_grid / wf_dispatch_nvdb; those pick the instantiation and run
+// medium boundaries}): they are instantiated in translation units of their own -- vspg_wf_grid.hip (GridMedium), vspg_wf_nvdb.hip
+// (NanoVDB semantics) and vspg_wf_rgbgrid.hip (RGBGridMedium, vspg_rgbgrid.h) -- which `make -j` compiles beside vspg_capi.hip.
+// vspg_capi.hip prepares a pass (buffers, grid sizes, streams) as a plain WfLaunch and calls wf_dispatch_grid / wf_dispatch_nvdb /
+// wf_dispatch_rgbgrid; those pick the instantiation and run
 // wf_run_pass below.  Return value: 0, a hipError_t, or WF_E_NOT_DRAINED.
 #pragma once
 #include <hip/hip_runtime.h>
@@ -29,6 +30,10 @@ constexpr int WF_E_NOT_DRAINED = -1000;
 
 int wf_dispatch_grid(const WfLaunch &L, bool guided, bool train, bool grey);
 int wf_dispatch_nvdb(const WfLaunch &L, bool guided, bool train, bool grey);
+// RGBGridMedium (vspg_wf_rgbgrid.hip): the pipeline, and the replay of vspg_trace_paths (its kernel lives in that unit too)
+int wf_dispatch_rgbgrid(const WfLaunch &L, bool guided, bool train);
+struct TraceLaunch;
+int trace_launch_rgbgrid(const TraceLaunch &T, bool guided);
 
 #define WFCHK(expr)                               \
     do {                                          \

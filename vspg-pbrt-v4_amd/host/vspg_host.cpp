@@ -23,6 +23,7 @@ ParameterDictionary &ParameterDictionary::RGB(const std::string &n, float r, flo
 ParameterDictionary &ParameterDictionary::Point3(const std::string &n, float x, float y, float z) { Value v; v.type = 'p'; v.f[0] = x; v.f[1] = y; v.f[2] = z; values[n] = v; return *this; }
 ParameterDictionary &ParameterDictionary::IntArray(const std::string &n, std::vector<int> a) { Value v; v.type = 'I'; v.iarr = std::move(a); values[n] = v; return *this; }
 ParameterDictionary &ParameterDictionary::Point3Array(const std::string &n, std::vector<float> a) { Value v; v.type = 'P'; v.arr = std::move(a); values[n] = v; return *this; }
+ParameterDictionary &ParameterDictionary::RGBArray(const std::string &n, std::vector<float> a) { Value v; v.type = 'C'; v.arr = std::move(a); values[n] = v; return *this; }
 ParameterDictionary &ParameterDictionary::FloatArray(const std::string &n, std::vector<float> a) { Value v; v.type = 'a'; v.arr = std::move(a); values[n] = v; return *this; }
 
 ParameterDictionary ParameterDictionary::Parse(const std::string &text) {
@@ -90,6 +91,10 @@ ParameterDictionary ParameterDictionary::Parse(const std::string &text) {
             if (toks.size() % 3) throw Error("parameter \"" + name + "\": point3 values come in threes");
             std::vector<float> a; for (auto &t : toks) a.push_back(num(t));
             d.Point3Array(name, std::move(a));
+        } else if (type == "rgb" && toks.size() > 3) {
+            if (toks.size() % 3) throw Error("parameter \"" + name + "\": rgb values come in threes");
+            std::vector<float> a; for (auto &t : toks) a.push_back(num(t));
+            d.RGBArray(name, std::move(a));
         } else if (type == "rgb" || type == "point3") {
             if (toks.size() != 3) throw Error("parameter \"" + name + "\": " + type + " needs three values");
             if (type == "rgb") d.RGB(name, num(toks[0]), num(toks[1]), num(toks[2]));
@@ -146,6 +151,13 @@ std::vector<float> ParameterDictionary::GetPoint3Array(const std::string &n) con
     if (it == values.end()) return {};
     if (it->second.type == 'p') { it->second.lookedUp = true; return {it->second.f[0], it->second.f[1], it->second.f[2]}; }
     auto v = find(n, 'P');
+    return v->arr;
+}
+std::vector<float> ParameterDictionary::GetRGBArray(const std::string &n) const {
+    auto it = values.find(n);
+    if (it == values.end()) return {};
+    if (it->second.type == 'c') { it->second.lookedUp = true; return {it->second.f[0], it->second.f[1], it->second.f[2]}; }
+    auto v = find(n, 'C');
     return v->arr;
 }
 void ParameterDictionary::ReportUnused() const {
@@ -285,14 +297,66 @@ static VspgMedium CreateNanoVdbMedium(const ParameterDictionary &p, std::vector<
     return m;
 }
 
-VspgMedium CreateMedium(const std::string &name, const ParameterDictionary &p, std::vector<float> *densityStorage,
-                        std::vector<float> *leScaleStorage, std::vector<float> *temperatureStorage) {
+void RgbGridStorage::Attach(VspgScene *scene) const {
+    scene->rgb_sigma_a = sigma_a.empty() ? nullptr : sigma_a.data();
+    scene->rgb_sigma_s = sigma_s.empty() ? nullptr : sigma_s.data();
+    scene->rgb_Le = Le.empty() ? nullptr : Le.data();
+    scene->rgb_sigma_scale = scale;
+    scene->rgb_le_scale = Lescale;
+}
+
+static VspgMedium CreateRgbGridMedium(const ParameterDictionary &p, RgbGridStorage *rgb) {
+    // RGBGridMedium::Create (media.cpp:411-484); sizes are counted in RGB triples, as GetRGBArray's vectors are
     VspgMedium m;
     std::memset(&m, 0, sizeof m);
+    std::vector<float> sigma_a = p.GetRGBArray("sigma_a"), sigma_s = p.GetRGBArray("sigma_s"), Le = p.GetRGBArray("Le");
+    if (sigma_a.empty() && sigma_s.empty()) throw Error("RGB grid requires \"sigma_a\" and/or \"sigma_s\" parameter values.");
+    size_t nDensity;
+    if (!sigma_a.empty()) {
+        nDensity = sigma_a.size() / 3;
+        if (!sigma_s.empty() && nDensity != sigma_s.size() / 3)
+            throw Error("Different number of samples (" + std::to_string(nDensity) + " vs " + std::to_string(sigma_s.size() / 3) +
+                        ") provided for \"sigma_a\" and \"sigma_s\".");
+    } else
+        nDensity = sigma_s.size() / 3;
+    if (!Le.empty() && sigma_a.empty()) throw Error("RGB grid requires \"sigma_a\" if \"Le\" value provided.");
+    if (!Le.empty() && nDensity != Le.size() / 3)
+        throw Error("Expected " + std::to_string(nDensity) + " values for \"Le\" parameter but were given " + std::to_string(Le.size() / 3) + ".");
+    const int nx = p.GetOneInt("nx", 1), ny = p.GetOneInt("ny", 1), nz = p.GetOneInt("nz", 1);
+    if ((long long)nDensity != (long long)nx * ny * nz)
+        throw Error("RGB grid medium has " + std::to_string(nDensity) + " density values; expected nx*ny*nz = " + std::to_string((long long)nx * ny * nz));
+    float p0[3] = {0.f, 0.f, 0.f}, p1[3] = {1.f, 1.f, 1.f};
+    p.GetOnePoint3("p0", p0);
+    p.GetOnePoint3("p1", p1);
+    const float LeScale = p.GetOneFloat("Lescale", 1.f);
+    const float g = p.GetOneFloat("g", 0.f);
+    const float sigmaScale = p.GetOneFloat("scale", 1.f);
+    p.ReportUnused();
+    if (!rgb) throw Error("CreateMedium(\"rgbgrid\") needs an RgbGridStorage to own the grids");
+    rgb->sigma_a = std::move(sigma_a);
+    rgb->sigma_s = std::move(sigma_s);
+    rgb->Le = std::move(Le);
+    rgb->scale = sigmaScale;
+    rgb->Lescale = LeScale;
+    m.type = VSPG_MEDIUM_RGBGRID;
+    for (int i = 0; i < 3; ++i) {
+        m.bounds_min[i] = p0[i];
+        m.bounds_max[i] = p1[i];
+    }
+    m.g = g;
+    m.nx = nx; m.ny = ny; m.nz = nz;
+    return m;
+}
+
+VspgMedium CreateMedium(const std::string &name, const ParameterDictionary &p, std::vector<float> *densityStorage,
+                        std::vector<float> *leScaleStorage, std::vector<float> *temperatureStorage, RgbGridStorage *rgbStorage) {
+    VspgMedium m;
+    std::memset(&m, 0, sizeof m);
+    if (name == "rgbgrid") return CreateRgbGridMedium(p, rgbStorage);
     if (name == "uniformgrid") return CreateGridMedium(p, densityStorage, leScaleStorage, temperatureStorage);
     if (name == "nanovdb") return CreateNanoVdbMedium(p, densityStorage, temperatureStorage ? temperatureStorage : leScaleStorage);
     if (name != "homogeneous")
-        throw Error("medium \"" + name + "\": only \"homogeneous\", \"uniformgrid\" and \"nanovdb\" are inside this build's scope");
+        throw Error("medium \"" + name + "\": only \"homogeneous\", \"uniformgrid\", \"rgbgrid\" and \"nanovdb\" are inside this build's scope");
     // HomogeneousMedium::Create (media.cpp:167-206)
     if (!p.GetOneString("preset", "").empty()) throw Error("medium \"preset\" tables are outside this build's scope");
     float sa[3] = {1.f, 1.f, 1.f}, ss[3] = {1.f, 1.f, 1.f}, le[3] = {0, 0, 0};  // defaults: ConstantSpectrum(1)

@@ -38,11 +38,12 @@ class ParameterDictionary {
     ParameterDictionary &FloatArray(const std::string &n, std::vector<float> v);
     ParameterDictionary &IntArray(const std::string &n, std::vector<int> v);
     ParameterDictionary &Point3Array(const std::string &n, std::vector<float> xyz);
+    ParameterDictionary &RGBArray(const std::string &n, std::vector<float> rgb);   // r g b r g b ... ("rgb name" [ several triples ])
     // The reference's scene-file parameter-list syntax ("type name" value | [ values ]), e.g. the block
     // cmd/nanovdb2pbrt.cpp:97-126 prints for a grid:
     //   "integer nx" 64 "integer ny" 64 "integer nz" 32 "point3 p0" [ -1 -1 0 ] "point3 p1" [ 1 1 1 ] "float density" [ ... ]
     // Types: integer (several -> IntArray), float (one value -> Float, several -> FloatArray), bool, string, rgb,
-    // point3 (several points -> Point3Array); point2 / vector3 / normal3 arrays are kept as float arrays under their name.
+    // point3 (several points -> Point3Array; several rgb triples -> RGBArray); point2 / vector3 / normal3 arrays are kept as float arrays under their name.
     static ParameterDictionary Parse(const std::string &text);
 
     int GetOneInt(const std::string &n, int def) const;
@@ -55,13 +56,14 @@ class ParameterDictionary {
     std::vector<float> GetFloatArray(const std::string &n) const;  // a single "float" value is a 1-element array
     std::vector<int> GetIntArray(const std::string &n) const;      // a single "integer" value is a 1-element array
     std::vector<float> GetPoint3Array(const std::string &n) const; // x y z x y z ...; a single "point3" is one point
+    std::vector<float> GetRGBArray(const std::string &n) const;    // r g b r g b ...; a single "rgb" is one triple (paramdict.h GetRGBArray)
     bool Has(const std::string &n) const { return values.count(n) != 0; }
     // paramdict.cpp:642-664: any parameter that was never looked up is a fatal error
     void ReportUnused() const;
 
   private:
     struct Value {
-        char type;  // i f b s c p a(rray) I(nt array) P(oint array)
+        char type;  // i f b s c p a(rray) I(nt array) P(oint array) C(olour array)
         int i = 0;
         std::vector<int> iarr;
         float f[3] = {0, 0, 0};
@@ -77,10 +79,17 @@ class ParameterDictionary {
 // (GridMedium::Create :272-361; the density array is copied into *densityStorage, which must outlive the
 // renderer creation -- VspgMedium.density points into it; likewise the "Lescale" and "temperature" grids); "nanovdb"
 // (NanoVDBMedium::Create :683-734; its temperature grid goes to temperatureStorage, or to leScaleStorage when that is all the caller
-// passed); other names -> Error: outside scope
+// passed); "rgbgrid" (RGBGridMedium::Create :411-484: its grids live in the tail of VspgScene, not in VspgMedium -- they are copied into
+// *rgbStorage, which must outlive the renderer creation and whose Attach() points a scene record at them); other names -> Error:
+// outside scope
+struct RgbGridStorage {
+    std::vector<float> sigma_a, sigma_s, Le;   // 3 * nx * ny * nz floats each, R G B per voxel, x fastest; empty = absent
+    float scale = 1.f, Lescale = 1.f;          // "scale" (sigmaScale), "Lescale"
+    void Attach(VspgScene *scene) const;       // fills rgb_sigma_a / rgb_sigma_s / rgb_Le / rgb_sigma_scale / rgb_le_scale
+};
 VspgMedium CreateMedium(const std::string &name, const ParameterDictionary &parameters,
                         std::vector<float> *densityStorage = nullptr, std::vector<float> *leScaleStorage = nullptr,
-                        std::vector<float> *temperatureStorage = nullptr);
+                        std::vector<float> *temperatureStorage = nullptr, RgbGridStorage *rgbStorage = nullptr);
 
 struct Image;  // vspg_image.h: pbrt's Image by file extension (PFM, OpenEXR)
 

@@ -65,6 +65,9 @@ int main(int argc, char **argv) {
                 std::printf("; %d spheres, %d interface-material surfaces, %d medium transitions, camera %s the medium", sd->scene.n_spheres, n_interface, n_transition,
                             sd->scene.camera_outside_medium ? "outside" : "in");
         }
+        if (sd->scene.medium.type == VSPG_MEDIUM_RGBGRID)
+            std::printf("; RGB grid %d x %d x %d:%s%s%s, scale %g, Lescale %g", sd->scene.medium.nx, sd->scene.medium.ny, sd->scene.medium.nz, sd->scene.rgb_sigma_a ? " sigma_a" : "",
+                        sd->scene.rgb_sigma_s ? " sigma_s" : "", sd->scene.rgb_Le ? " Le" : "", sd->scene.rgb_sigma_scale, sd->scene.rgb_le_scale);
         if (sd->scene.medium.temperature) std::printf("; temperature grid (blackbody emission under \"vspsamplingmethod\" \"nds\")");
         std::printf("\n");
         std::printf("pixel bounds: [ (%d, %d) - (%d, %d) ]\n", sd->boundsX0, sd->boundsY0, sd->boundsX1, sd->boundsY1);

@@ -14,7 +14,7 @@
 // (L, scale; or "filename": an equal-area octahedral environment map, .exr / .pfm, square, with R, G, B -- the CTM in effect is the
 // light's transform; no "portal", no "illuminance") / "distant" (L, scale, from, to) / "point" (I, scale, power, from under the CTM: a
 // VspgPointLight filled by vspg_point_light_at; LightSource "spot" is still REFUSED by name here -- the library, its binding and
-// vspg_spot_light_look_at carry everything it needs, the reader's few lines are a follow-up), MakeNamedMedium ("homogeneous", "uniformgrid"), MediumInterface,
+// vspg_spot_light_look_at carry everything it needs, the reader's few lines are a follow-up), MakeNamedMedium ("homogeneous", "uniformgrid", "rgbgrid", "nanovdb"), MediumInterface,
 // Include (as a directive, and -- beyond pbrt -- inside a parameter list, for the block the reference's nanovdb2pbrt prints),
 // Shape "bilinearmesh" (one patch: a parallelogram becomes a rectangle, anything else two triangles) / "trianglemesh"
 // (P, indices) / "sphere" (radius; full spheres).  Anything else is an Error naming the directive: nothing is silently dropped.
@@ -38,6 +38,7 @@ struct SceneDescription {
     VspgScene scene;                     // pointers inside refer to the vectors below: keep the description alive while creating
     std::vector<float> density, leScale, temperature, triP, triKd;
     std::vector<int32_t> triFlags;       // VSPG_TRI_* per triangle (material, MediumInterface, orientation)
+    RgbGridStorage rgb;                  // MakeNamedMedium "string type" "rgbgrid": the grids scene.rgb_* point at
     // LightSource "infinite" "string filename": the image of infinite light `light` (R, G, B interleaved, top row first) and the
     // rows of its renderFromLight (the CTM at the directive).  CreateIntegrator hands them to the renderer it creates
     // (Integrator::SetEnvironmentImage -> vspg_renderer_set_environment_image); a host that creates the renderer itself does the same.
