@@ -264,6 +264,7 @@ typedef struct VspgScene {
      * rgb_sigma_scale * (MaxValue(sigma_a box) + MaxValue(sigma_s box)), the maximum over voxels and channels taken per grid, then summed.
      * VSPG_EINVAL at create: both sigma grids NULL; rgb_Le without rgb_sigma_a (media.cpp:386-387, :433-434); a value in any grid that is
      * negative, NaN or infinite; nx, ny or nz < 1; a scale that is NaN or infinite; medium.temperature set.
+     * In-place update: vspg_renderer_update_rgb_grids (below); read-back of the device image: vspg_rgb_octets_read.
      * Limits: dense storage only; vspg_renderer_update_grid and vspg_brick_info / _read return VSPG_EINVAL and
      * vspg_renderer_set_arithmetic to a tolerance mode VSPG_ESCOPE, each with the renderer unchanged; VSPG_KERNEL=wg falls through to
      * the per-lane kernel; one medium per scene, as ever. */
@@ -716,6 +717,30 @@ int vspg_brick_read(VspgRenderer *r, int32_t *index, float *octets, void *stream
 #define VSPG_MEM_HOST   0
 #define VSPG_MEM_DEVICE 1
 int vspg_renderer_update_grid(VspgRenderer *r, int which, const float *values, size_t n_floats, int memory, void *stream);
+/* The same for an RGB grid medium (VSPG_MEDIUM_RGBGRID): replaces the values of its sigma_a, sigma_s and / or Le grid in place.  ONE
+ * call takes the three grids, because the majorant grid depends on both sigma grids and is rebuilt once; a NULL pointer means "keep
+ * this grid".  Every given grid holds n_floats = 3 * nx * ny * nz floats (R, G, B per voxel, x fastest, as at create); `memory`
+ * (VSPG_MEM_HOST / VSPG_MEM_DEVICE) holds for all given pointers: a device source is read where it lies, a host source is staged.
+ * Dimensions, bounds, transform, rgb_sigma_scale and rgb_le_scale stay create's.  Afterwards the renderer computes, bit for bit, what a
+ * renderer created with the new values computes (the sign of a majorant that is a zero apart): the octet image of each given sigma grid
+ * is rebuilt on the device (one workgroup per 8^3 brick, every byte of the image written), the majorant grid by one workgroup per cell --
+ * over the new values of a grid that is given and over the stored octets of one that is kept --, and the Le grid is a plain copy.
+ * Order and what persists are vspg_renderer_update_grid's: every refusal, then parked samples and suspended paths are finished on
+ * `stream` (under the old values), the rebuild, and `stream` is synchronised before the call returns; film, statistics, VSP buffer,
+ * TrBuffer, guiding fields, training state, counters, reference image and error log stay.
+ * VSPG_EINVAL, with majorants, octets, Le, film, counters and parked samples exactly as they were: a null renderer; a medium that is
+ * not RGBGRID; all three pointers NULL; n_floats != 3*nx*ny*nz; an unknown `memory`; a grid the renderer was created without (an absent
+ * grid has no storage: the kernels branch the constant in); a value in a given grid that is negative, NaN or infinite (-0.0 passes, as
+ * at create) -- checked on the host for a host source and by one read pass on the device for a device source, before anything of the
+ * renderer is written; the message names the grid. */
+int vspg_renderer_update_rgb_grids(VspgRenderer *r, const float *sigma_a, const float *sigma_s, const float *Le,
+                                   size_t n_floats /* 3*nx*ny*nz, per given grid */, int memory, void *stream);
+/* Read-back of the device image of one sigma grid of an RGB grid medium (test + diagnostics): which = 0 sigma_a, 1 sigma_s.  host_out:
+ * n_floats == bnx * bny * bnz * 512 * 32 floats (HOST array), bn = (n + 8) / 8 bricks per axis, brick number = (bz * bny + by) * bnx + bx;
+ * a brick holds 8 x 8 x 8 octets (x fastest) of base voxels 8b - 1 .. 8b + 6, an octet the eight corners (x fastest, then y, then z) of its
+ * base voxel as R, G, B, 0 each; zero outside the grid and in the octets behind base voxel n - 1.  VSPG_EINVAL for another medium, a
+ * grid the renderer was created without, another `which` or a wrong size.  Synchronises `stream`. */
+int vspg_rgb_octets_read(VspgRenderer *r, int which /* 0 sigma_a, 1 sigma_s */, float *host_out, size_t n_floats, void *stream);
 /* Read-back of the majorant grid the kernels read (test + diagnostics), x fastest: res^3 floats with res = 16 for a GRID or RGBGRID medium,
  * 64 for NANOVDB semantics.  host_out: n_floats == res^3 floats (HOST array); res (may be NULL) receives the resolution.
  * VSPG_EINVAL for other media or a wrong n_floats (res is still reported for a grid medium, so a caller can size its array).

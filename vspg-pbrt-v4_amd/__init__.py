@@ -298,6 +298,8 @@ SYMBOLS = [
     ("vspg_brick_info", C.c_int, [_vp, _P(VspgBrickInfo)]),
     ("vspg_brick_read", C.c_int, [_vp, _P(C.c_int32), _P(C.c_float), _vp]),
     ("vspg_renderer_update_grid", C.c_int, [_vp, C.c_int, _vp, C.c_size_t, C.c_int, _vp]),
+    ("vspg_renderer_update_rgb_grids", C.c_int, [_vp, _vp, _vp, _vp, C.c_size_t, C.c_int, _vp]),
+    ("vspg_rgb_octets_read", C.c_int, [_vp, C.c_int, _P(C.c_float), C.c_size_t, _vp]),
     ("vspg_majorant_read", C.c_int, [_vp, _P(C.c_float), C.c_size_t, _P(C.c_int32), _vp]),
     ("vspg_medium_point_batch", C.c_int, [_vp, C.c_int, _P(C.c_float), _P(C.c_float), _vp]),
     ("vspg_primitives_batch", C.c_int, [_vp, C.c_int, _P(C.c_float), _P(C.c_float), _P(C.c_uint64), _P(C.c_uint32), _P(C.c_float), _vp]),
@@ -720,6 +722,21 @@ def grid_update_source(n_voxels, values, device):
     raise ValueError("grid values must be a NumPy array or a torch tensor, not %s" % type(values).__name__)
 
 
+def rgb_update_sources(n_voxels, sigma_a, sigma_s, Le, device):
+    """What vspg_renderer_update_rgb_grids is handed: ([address or None] * 3, memory kind, stream or None).  Each given grid passes
+    grid_update_source with 3 * n_voxels elements (R, G, B per voxel); None keeps a grid.  Raises ValueError -- here, before the
+    library is called -- when nothing is given or when NumPy arrays and torch tensors are mixed (one memory kind per call)."""
+    given = [g for g in (sigma_a, sigma_s, Le) if g is not None]
+    if not given:
+        raise ValueError("update_rgb needs at least one of sigma_a, sigma_s, Le")
+    src = [None if g is None else grid_update_source(3 * n_voxels, g, device) for g in (sigma_a, sigma_s, Le)]
+    kinds = {s[1] for s in src if s is not None}
+    if len(kinds) != 1:
+        raise ValueError("update_rgb takes NumPy arrays (host) or torch tensors (device), not both in one call")
+    stream = next((s[2] for s in src if s is not None and s[2] is not None), None)
+    return [None if s is None else s[0] for s in src], kinds.pop(), stream
+
+
 class Renderer:
     """Thin RAII wrapper over the vspg_renderer_* entry points."""
 
@@ -1034,6 +1051,28 @@ class Renderer:
     def update_temperature(self, values, stream=None):
         """Replace the temperature grid's values (a renderer created with one), as update_density takes them."""
         self._update_grid(GRID_TEMPERATURE, values, stream)
+
+    def update_rgb(self, sigma_a=None, sigma_s=None, Le=None, stream=None):
+        """Replace an RGB grid medium's sigma_a / sigma_s / Le values in place (vspg_renderer_update_rgb_grids): float32 NumPy arrays
+        (host path) or float32 torch tensors on the renderer's device (device path, read where they lie), 3*nx*ny*nz elements each,
+        R, G, B per voxel, x fastest; None keeps a grid.  Octets and majorants are rebuilt on the device; film, statistics, VSP
+        buffer, guiding fields and counters stay."""
+        m = self.scene.medium
+        n = int(m.nx) * int(m.ny) * int(m.nz)
+        ptrs, memory, cur = rgb_update_sources(n, sigma_a, sigma_s, Le, int(self.cfg.device))
+        if stream is None:
+            stream = cur  # (a device source: torch's current stream, the one its producer ran on)
+        _check(self.lib, self.lib.vspg_renderer_update_rgb_grids(self.h, _vp(ptrs[0]), _vp(ptrs[1]), _vp(ptrs[2]), 3 * n, memory, _vp(stream or 0)))
+
+    def rgb_octets(self, which):
+        """The device image of an RGB grid medium's sigma_a (which = 0) or sigma_s (1) grid (vspg_rgb_octets_read):
+        [bnz, bny, bnx, 8, 8, 8, 8, 4] float32 -- brick z, y, x; octet z, y, x in the brick; corner; R, G, B, 0."""
+        import numpy as np
+        m = self.scene.medium
+        bn = [(int(v) + 8) // 8 for v in (m.nx, m.ny, m.nz)]
+        out = np.empty((bn[2], bn[1], bn[0], 8, 8, 8, 8, 4), dtype=np.float32)
+        _check(self.lib, self.lib.vspg_rgb_octets_read(self.h, int(which), out.ctypes.data_as(_P(C.c_float)), out.size, _vp(0)))
+        return out
 
     def majorant(self, stream=None):
         """The majorant grid the kernels read (vspg_majorant_read): [R, R, R] float32 indexed z, y, x; R = 16 (GRID, RGBGRID) or 64 (NANOVDB)."""

@@ -249,6 +249,7 @@ __global__ __launch_bounds__(kBlock) void k_film_resolve(int W, PixelWindow win,
 }  // namespace
 
 #include "vspg_probe_kernels.h"  // the parity probes' kernels; the brick and majorant builders
+#include "vspg_rgb_update_kernels.h"  // the RGB grid medium's storage rebuilt on the device (vspg_renderer_update_rgb_grids)
 
 // =======================================================================================
 // host side
@@ -1916,6 +1917,102 @@ int vspg_renderer_update_grid(VspgRenderer *r, int which, const float *values, s
     if (rc) (void)hipStreamSynchronize(s);
     for (void *p : tmp) (void)hipFree(p);
     return rc;
+}
+
+// The RGB grid medium's update (vspg_rgbgrid.h; kernels: vspg_rgb_update_kernels.h).  One call for the three grids: the majorant grid
+// depends on both sigma grids and is rebuilt once.  A sigma grid that stays lends the majorant kernel its octets (corner 0 of octet
+// (x + 1, y + 1, z + 1) is voxel (x, y, z)); create's host builders are not used here -- they are what this path is compared with.
+int vspg_renderer_update_rgb_grids(VspgRenderer *r, const float *sigma_a, const float *sigma_s, const float *Le, size_t n_floats, int memory,
+                                   void *stream) {
+    // every refusal comes before anything of the renderer changes -- parked samples included
+    if (!r) return fail(VSPG_EINVAL, "null renderer");
+    if (r->scene.medium.type != VSPG_MEDIUM_RGBGRID) return fail(VSPG_EINVAL, "renderer has no RGB grid medium");
+    if (!sigma_a && !sigma_s && !Le) return fail(VSPG_EINVAL, "no grid given (sigma_a, sigma_s and Le are all NULL)");
+    const VspgMedium &m = r->scene.medium;
+    const int nx = m.nx, ny = m.ny, nz = m.nz;
+    const size_t n3 = (size_t)nx * ny * nz * 3;
+    if (n_floats != n3) return fail(VSPG_EINVAL, "n_floats is not 3 * nx * ny * nz of the grids the renderer was created with");
+    if (memory != VSPG_MEM_HOST && memory != VSPG_MEM_DEVICE) return fail(VSPG_EINVAL, "unknown memory kind (VSPG_MEM_HOST / VSPG_MEM_DEVICE)");
+    const float *given[3] = {sigma_a, sigma_s, Le};
+    const void *have[3] = {r->rgb_oct[0], r->rgb_oct[1], r->rgb_Le};
+    for (int k = 0; k < 3; ++k)
+        if (given[k] && !have[k])
+            return fail(VSPG_EINVAL, std::string("the renderer was created without a \"") + (k == 0 ? "sigma_a" : k == 1 ? "sigma_s" : "Le") +
+                                         "\" grid (its kernels branch the constant in and hold no storage for one)");
+    const int R = majorant_res(m);
+    const std::vector<int2> ranges = majorant_axis_ranges(m);
+    {
+        const int n[3] = {nx, ny, nz};
+        for (int k = 0; k < 3; ++k)
+            for (int c = 0; c < R; ++c) {  // (what the majorant kernel indexes with: inside the grid, or empty)
+                const int2 q = ranges[(size_t)k * R + c];
+                if (q.y >= q.x && (q.x < 0 || q.y > n[k] - 1)) return fail(VSPG_EINVAL, "majorant cell footprint outside the RGB grid");
+            }
+    }
+    HIPCHK(hipSetDevice(r->cfg.device));
+    hipStream_t s = (hipStream_t)stream;
+    if (memory == VSPG_MEM_HOST) {
+        for (int k = 0; k < 3; ++k)
+            if (given[k])
+                if (const int rc = check_rgb_grid_values(given[k], n3, k)) return rc;
+    } else {  // one read pass per given grid; the flags come back before anything of the renderer is written
+        DevBuf dflags;
+        int flags[3] = {0, 0, 0};
+        HIPCHK(hipMalloc(&dflags.p, sizeof flags));
+        HIPCHK(hipMemsetAsync(dflags.p, 0, sizeof flags, s));
+        const unsigned blocks = (unsigned)std::min<size_t>((n3 + kBlock - 1) / kBlock, 4096);
+        for (int k = 0; k < 3; ++k)
+            if (given[k]) hipLaunchKernelGGL(k_rgb_validate, dim3(blocks), dim3(kBlock), 0, s, given[k], n3, (int *)dflags.p + k);
+        HIPCHK(hipGetLastError());
+        HIPCHK(hipMemcpyAsync(flags, dflags.p, sizeof flags, hipMemcpyDeviceToHost, s));
+        HIPCHK(hipStreamSynchronize(s));
+        for (int k = 0; k < 3; ++k)
+            if (flags[k]) return rgb_grid_value_refusal(k);
+    }
+    if (const int rc = flush_parked_samples(r, s)) return rc;  // (paths in flight end under the medium they started in)
+    HIPCHK(hipStreamSynchronize(s));  // no launch may still read the old grids
+    // a host source of a sigma grid is staged on the device for the builders; a device source is read where it lies
+    DevBuf staged[2], dranges;
+    const float *d[2] = {sigma_a, sigma_s};
+    if (memory == VSPG_MEM_HOST)
+        for (int k = 0; k < 2; ++k)
+            if (d[k]) {
+                HIPCHK(hipMalloc(&staged[k].p, n3 * sizeof(float)));
+                HIPCHK(hipMemcpyAsync(staged[k].p, d[k], n3 * sizeof(float), hipMemcpyHostToDevice, s));
+                d[k] = (const float *)staged[k].p;
+            }
+    const int bnx = r->hscene.bnx, bny = r->hscene.bny, bnz = r->hscene.bnz;
+    if (d[0] || d[1]) {
+        HIPCHK(hipMalloc(&dranges.p, ranges.size() * sizeof(int2)));
+        HIPCHK(hipMemcpyAsync(dranges.p, ranges.data(), ranges.size() * sizeof(int2), hipMemcpyHostToDevice, s));
+        RgbMajSource src[2];
+        for (int k = 0; k < 2; ++k) src[k] = RgbMajSource{d[k], d[k] ? nullptr : r->rgb_oct[k]};  // new values | its own octets | absent
+        hipLaunchKernelGGL(k_majorant_build_rgb, dim3((unsigned)(R * R * R)), dim3(kMajBlock), 0, s, src[0], src[1], nx, ny, nz, bnx, bny, R,
+                           (const int2 *)dranges.p, r->scene.rgb_sigma_scale, r->majorant);
+        HIPCHK(hipGetLastError());
+        const size_t nb = (size_t)bnx * bny * bnz;
+        for (int k = 0; k < 2; ++k)
+            if (d[k]) {
+                hipLaunchKernelGGL(k_rgb_octet_build, dim3((unsigned)nb), dim3(512), 0, s, d[k], nx, ny, nz, bnx, bny, r->rgb_oct[k]);
+                HIPCHK(hipGetLastError());
+            }
+    }
+    if (Le) HIPCHK(hipMemcpyAsync(r->rgb_Le, Le, n3 * sizeof(float), memory == VSPG_MEM_HOST ? hipMemcpyHostToDevice : hipMemcpyDeviceToDevice, s));
+    HIPCHK(hipStreamSynchronize(s));  // as create: the storage is complete, the sources and the temporaries may go
+    return 0;
+}
+
+int vspg_rgb_octets_read(VspgRenderer *r, int which, float *host_out, size_t n_floats, void *stream) {
+    if (!r || !host_out) return fail(VSPG_EINVAL, "null argument");
+    if (r->scene.medium.type != VSPG_MEDIUM_RGBGRID) return fail(VSPG_EINVAL, "renderer has no RGB grid medium");
+    if (which != 0 && which != 1) return fail(VSPG_EINVAL, "unknown grid (0 sigma_a, 1 sigma_s)");
+    if (!r->rgb_oct[which]) return fail(VSPG_EINVAL, "the renderer was created without that grid");
+    const size_t n = (size_t)r->hscene.bnx * r->hscene.bny * r->hscene.bnz * 512u * 32u;
+    if (n_floats != n) return fail(VSPG_EINVAL, "n_floats is not bnx * bny * bnz * 512 * 32 (bn = (n + 8) / 8 per axis)");
+    HIPCHK(hipSetDevice(r->cfg.device));
+    HIPCHK(hipMemcpyAsync(host_out, r->rgb_oct[which], n * sizeof(float), hipMemcpyDeviceToHost, (hipStream_t)stream));
+    HIPCHK(hipStreamSynchronize((hipStream_t)stream));
+    return 0;
 }
 
 // A field that upload_field can take: absent / empty (the field is cleared), or arrays with children after their parent,

@@ -54,6 +54,10 @@ std::vector<float> build_majorant_grid_nvdb(const VspgMedium &m);
 // RGBGridMedium (VSPG_MEDIUM_RGBGRID, vspg_rgbgrid.h): the refusals of create (validate calls it), the 16^3 majorants, and the device
 // image of one RGB grid -- bnx * bny * bnz bricks of 512 octets of 8 float4 (32 floats)
 int validate_rgb_grid(const VspgScene &sc);
+// ... its per-value loop over one grid's n_floats HOST values (`which`: 0 sigma_a, 1 sigma_s, 2 Le -- the name in the message), which
+// vspg_renderer_update_rgb_grids reuses; rgb_grid_value_refusal sets that message alone (a device source is checked by a kernel)
+int check_rgb_grid_values(const float *values, size_t n_floats, int which);
+int rgb_grid_value_refusal(int which);
 std::vector<float> build_majorant_grid_rgb(const VspgScene &sc);
 void rgb_brick_counts(const VspgMedium &m, int *bnx, int *bny, int *bnz);
 std::vector<float> build_rgb_octets(const float *rgb, const VspgMedium &m);

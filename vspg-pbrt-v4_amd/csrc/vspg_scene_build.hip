@@ -1047,6 +1047,16 @@ std::vector<float> build_majorant_grid_nvdb(const VspgMedium &m) {
 // ---- RGBGridMedium ("rgbgrid", media.h:391-467): what create derives on the host -- the refusals, the majorants, the storage image.
 // Create's error triggers (media.cpp:418-445) as far as they survive in a record of pointers: the sample counts are nx * ny * nz by
 // contract, so what is left is "sigma_a and/or sigma_s" (:418-420) and "sigma_a if Le" (:433-434, the constructor's CHECK :386-387).
+// the value check of one grid (HOST values), shared by create and vspg_renderer_update_rgb_grids: -0.0 passes (it is not < 0)
+static const char *rgb_grid_name(int which) { return which == 0 ? "sigma_a" : which == 1 ? "sigma_s" : "Le"; }
+int rgb_grid_value_refusal(int which) {
+    return fail(VSPG_EINVAL, std::string("RGB grid medium: \"") + rgb_grid_name(which) + "\" holds a value that is negative or not finite");
+}
+int check_rgb_grid_values(const float *values, size_t n_floats, int which) {
+    for (size_t i = 0; i < n_floats; ++i)
+        if (!std::isfinite(values[i]) || values[i] < 0) return rgb_grid_value_refusal(which);
+    return 0;
+}
 int validate_rgb_grid(const VspgScene &sc) {
     const VspgMedium &m = sc.medium;
     if (m.nx <= 0 || m.ny <= 0 || m.nz <= 0) return fail(VSPG_EINVAL, "RGB grid medium needs nx, ny, nz > 0");
@@ -1066,12 +1076,9 @@ int validate_rgb_grid(const VspgScene &sc) {
     }
     const size_t n3 = (size_t)m.nx * m.ny * m.nz * 3;
     const float *grids[3] = {sc.rgb_sigma_a, sc.rgb_sigma_s, sc.rgb_Le};
-    const char *names[3] = {"sigma_a", "sigma_s", "Le"};
     for (int gk = 0; gk < 3; ++gk)
         if (grids[gk])
-            for (size_t i = 0; i < n3; ++i)
-                if (!std::isfinite(grids[gk][i]) || grids[gk][i] < 0)
-                    return fail(VSPG_EINVAL, std::string("RGB grid medium: \"") + names[gk] + "\" holds a value that is negative or not finite");
+            if (const int rc = check_rgb_grid_values(grids[gk], n3, gk)) return rc;
     return 0;
 }
 

@@ -741,6 +741,18 @@ void GuidedVolPathVSPGIntegrator::SetMediumDensity(const std::vector<float> &val
 void GuidedVolPathVSPGIntegrator::SetMediumTemperature(const std::vector<float> &values) {
     if (vspg_renderer_update_grid(renderer, VSPG_GRID_TEMPERATURE, values.data(), values.size(), VSPG_MEM_HOST, nullptr) != 0) throw Error(vspg_last_error());
 }
+void GuidedVolPathVSPGIntegrator::SetMediumRgbGrids(const RgbGridStorage &grids) {
+    const std::vector<float> *g[3] = {&grids.sigma_a, &grids.sigma_s, &grids.Le};
+    size_t n = 0;
+    for (const std::vector<float> *v : g)
+        if (!v->empty()) {
+            if (n != 0 && v->size() != n) throw Error("SetMediumRgbGrids: the given grids differ in size");
+            n = v->size();
+        }
+    auto ptr = [](const std::vector<float> &v) { return v.empty() ? nullptr : v.data(); };
+    if (vspg_renderer_update_rgb_grids(renderer, ptr(grids.sigma_a), ptr(grids.sigma_s), ptr(grids.Le), n, VSPG_MEM_HOST, nullptr) != 0)
+        throw Error(vspg_last_error());
+}
 void GuidedVolPathVSPGIntegrator::ClearFilm() {
     if (vspg_film_clear(renderer, nullptr) != 0) throw Error(vspg_last_error());
     sppDone = 0;

@@ -223,6 +223,11 @@ class GuidedVolPathVSPGIntegrator : public Integrator {
     // Throw on refusal: a medium that is no grid, a wrong size, a temperature grid the scene never had.
     void SetMediumDensity(const std::vector<float> &values);
     void SetMediumTemperature(const std::vector<float> &values);
+    // The same for an "rgbgrid" medium (vspg_renderer_update_rgb_grids, host source): the sigma_a / sigma_s / Le values of `grids`
+    // replace the renderer's, 3*nx*ny*nz floats each; an EMPTY vector keeps that grid (scale and Lescale stay create's and are not
+    // read).  Octets and majorants are rebuilt on the device.  Throws on refusal: another medium, nothing given, a wrong size, a grid
+    // the scene never had, a value that is negative or not finite.
+    void SetMediumRgbGrids(const RgbGridStorage &grids);
     void ClearFilm();             // vspg_film_clear: the film to zero (statistics, VSP buffer and fields stay); Render() starts at wave 0 again
     // The film's file (RGBFilm::WriteImage, film.cpp:531-569), format by extension:
     //   .exr  the pixel bounds resolved ON THE DEVICE (vspg_film_resolve, scan-line layout) and written as they arrive: HALF channels
