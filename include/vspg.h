@@ -192,14 +192,32 @@ typedef struct VspgInfiniteLight {
  *   render_from_light  the light's Transform, row-major and affine (last row 0 0 0 1), BOTH matrices as for VspgSphere / VspgMedium
  *   light_from_render  so that ApplyInverse sees the caller's floats.  The light sits at render_from_light(0, 0, 0); a spot light
  *                      shines along render_from_light(0, 0, 1).  vspg_point_light_at / vspg_spot_light_look_at fill both.
- *   cone_angle_deg     spot lights only: "coneangle" (the whole cone's half angle) and "conedeltaangle" (the width of the smooth falloff
+ *   cone_angle_deg     spot lights (for a projection light: its field of view, below): "coneangle" (the whole cone's half angle) and "conedeltaangle" (the width of the smooth falloff
  *   cone_delta_deg     band inside it).  The library forms cosFalloffEnd = cosf(Radians(cone_angle_deg)) and cosFalloffStart =
  *                      cosf(Radians(cone_angle_deg - cone_delta_deg)) on the host, as the constructor does (lights.cpp:1438-1439).
  * A context point that coincides with the light's position divides by zero, as in the reference, which has no guard. */
 enum { VSPG_LIGHT_POINT = 3, VSPG_LIGHT_SPOT = 4 };
+/* Projection and goniometric lights (ProjectionLight, src/pbrt/lights.h:342-392, lights.cpp:319-441, :490-560; GoniometricLight,
+ * lights.h:395-455, lights.cpp:564-624, :652-734): delta lights at a position like the two above, whose intensity per direction comes
+ * from an image.  They travel in the same VspgPointLight slots; type, I and both matrices keep their meaning.
+ *   projection   a slide projector: the light looks along render_from_light(0, 0, 1) through Perspective(fov, 1e-3, 1e30); the slide (R, G, B
+ *                per texel, clamped at zero) fills the screen window [-aspect, aspect] x [-1, 1] (aspect > 1) or [-1, 1] x [-1/aspect, 1/aspect].
+ *                The field of view ("fov": the full angle of the beam across the slide's shorter axis, in degrees) is cone_angle_deg of
+ *                the slot -- a projection light has no other use for the field, and the scene record keeps its size --: valid values lie
+ *                in (0, 180), anything else (NaN included) is VSPG_EINVAL; cone_delta_deg is not read.  vspg_projection_light_at builds ctm * Scale(1, -1, 1).
+ *   goniometric  a bulb whose intensity is I times one texel (Y) of a square equal-area map (EqualAreaSphereToSquare of the direction in
+ *                light space, nearest texel, clamped at the edge).  vspg_goniometric_light_at builds ctm * swapYZ.  The linear part of
+ *                light_from_render must be orthonormal -- the mapping is defined for unit vectors and the reference hands it
+ *                ApplyInverse(-wi) unnormalised --: every entry of R R^T - 1 (R = the 3 x 3 of light_from_render, in double) must lie
+ *                within 1e-4, a hundred times what float products of rotations leave and far below any real scale; beyond it VSPG_ESCOPE.
+ * The image is not part of the scene record: a renderer created with such a slot holds a 1 x 1 image of ones (a uniform square beam; a
+ * point light) until vspg_renderer_set_light_image replaces it.  SampleLe / PDF_Le and the PiecewiseConstant2D they alone read are out
+ * of scope: Li never calls them. */
+enum { VSPG_LIGHT_PROJECTION = 5, VSPG_LIGHT_GONIOMETRIC = 6 };
+#define VSPG_LIGHT_IMAGE_MAX_RES 4096
 #define VSPG_MAX_POINT_LIGHTS 8
 typedef struct VspgPointLight {
-    int32_t type;                 /* VSPG_LIGHT_POINT | VSPG_LIGHT_SPOT */
+    int32_t type;                 /* VSPG_LIGHT_POINT | VSPG_LIGHT_SPOT | VSPG_LIGHT_PROJECTION | VSPG_LIGHT_GONIOMETRIC */
     float I[3];
     float render_from_light[16];
     float light_from_render[16];
@@ -407,6 +425,11 @@ int vspg_transform_inverse(const float m[16], float inv[16]);
 int vspg_spot_light_look_at(VspgPointLight *l, const float from[3], const float to[3], const float ctm[16] /* or NULL */);
 /* The same for a point light at `from` (PointLight::Create, lights.cpp:240-242): renderFromLight = ctm * Translate(from). */
 int vspg_point_light_at(VspgPointLight *l, const float from[3], const float ctm[16] /* or NULL */);
+/* The same for a projection light (ProjectionLight::Create, lights.cpp:555-556): renderFromLight = ctm * Scale(1, -1, 1), and for a
+ * goniometric light (GoniometricLight::Create, lights.cpp:724-726): renderFromLight = ctm * swapYZ.  Both lights sit at the origin of
+ * `ctm` (NULL = identity: the flip / the swap as it stands).  VSPG_EINVAL as above. */
+int vspg_projection_light_at(VspgPointLight *l, const float ctm[16] /* or NULL */);
+int vspg_goniometric_light_at(VspgPointLight *l, const float ctm[16] /* or NULL */);
 /* Fills `scene` with the App.-F fog box: box [-1,1]^3, Kd .73 walls, 0.5x0.5 ceiling
  * light Le (17,12,4) at y=.999, homogeneous fog sigma_a .05 sigma_s .45 g 0, camera at
  * (0,0,-.95) looking +z, fov 60. */
@@ -816,6 +839,21 @@ int vspg_blackbody_batch(VspgRenderer *r, int n, const float *u, const float *T,
 #define VSPG_ENV_MAX_RES 4096
 int vspg_renderer_set_environment_image(VspgRenderer *r, int infinite_light_index, const float *host_rgb, int res,
                                         const float *render_from_light /*12 or NULL*/, void *stream);
+/* Gives a projection or goniometric light (point-light slot `point_light_index`) its image, modelled on the call above.
+ *   host_pixels   xres*yres*channels floats (HOST array), top row first
+ *   channels      3 (R, G, B) for a projection slot, 1 (Y) for a goniometric slot
+ *   xres, yres    1 .. VSPG_LIGHT_IMAGE_MAX_RES (4096); a goniometric image must be square (lights.cpp:680-685)
+ * The host builds the device image (a projection slide as one float4 per texel, already clamped at zero, pad 0; a goniometric map as
+ * one float per texel, as given), the slide's screen window and A, the light's Phi (ProjectionLight::Phi lights.cpp:404-424 per
+ * channel of I; GoniometricLight::Phi :603-610) for the "power" alias table and its LightBounds (:426-441, :612-624; the power uses
+ * the largest component of I) for the "bvh" tree, uploads the image into one allocation of its own and swaps it in behind `stream`;
+ * the old image is released after the swap.  It finishes parked samples and suspended paths on `stream` first, synchronises `stream`
+ * before it returns, and keeps everything vspg_renderer_set_environment_image keeps.
+ * VSPG_EINVAL, with the renderer exactly as it was and before any allocation: a null argument, an index that is no point-light slot
+ * or a slot of another type, a wrong `channels` for the slot's type, a resolution out of range or a non-square goniometric image, a
+ * pixel that is NaN or infinite (lights.cpp:502-510, :669-678). */
+int vspg_renderer_set_light_image(VspgRenderer *r, int point_light_index, const float *host_pixels, int xres, int yres,
+                                  int channels, void *stream);
 /* Batch driver of the image infinite light (parity tests), as the path kernels evaluate it.  dirs: 3n floats, u: 2n floats, out:
  * VSPG_ENVLIGHT_OUT floats per element (HOST arrays):
  *   [0..2] Le(dirs[i])   [3..4] the (u, v) that Le looked up   [5] PDF_Li(dirs[i])

@@ -81,6 +81,8 @@ class VspgInfiniteLight(C.Structure):
 
 VSPG_MAX_POINT_LIGHTS = 8
 LIGHT_POINT, LIGHT_SPOT = 3, 4
+LIGHT_PROJECTION, LIGHT_GONIOMETRIC = 5, 6   # image-shaped point lights, in the same VspgPointLight slots
+LIGHT_IMAGE_MAX_RES = 4096                   # VSPG_LIGHT_IMAGE_MAX_RES
 LIGHT_SAMPLE_OUT = 16  # VSPG_LIGHT_SAMPLE_OUT: floats per element of vspg_light_sample_batch
 LIGHT_PDF_OUT = 8      # VSPG_LIGHT_PDF_OUT: floats per element of vspg_light_pdf_batch
 
@@ -315,6 +317,9 @@ SYMBOLS = [
     ("vspg_envlight_batch", C.c_int, [_vp, C.c_int, C.c_int, _P(C.c_float), _P(C.c_float), _P(C.c_float), _vp]),
     ("vspg_spot_light_look_at", C.c_int, [_P(VspgPointLight), f3, f3, _P(C.c_float)]),
     ("vspg_point_light_at", C.c_int, [_P(VspgPointLight), f3, _P(C.c_float)]),
+    ("vspg_projection_light_at", C.c_int, [_P(VspgPointLight), _P(C.c_float)]),
+    ("vspg_goniometric_light_at", C.c_int, [_P(VspgPointLight), _P(C.c_float)]),
+    ("vspg_renderer_set_light_image", C.c_int, [_vp, C.c_int, _P(C.c_float), C.c_int, C.c_int, C.c_int, _vp]),
     ("vspg_light_sample_batch", C.c_int, [_vp, C.c_int, _P(C.c_float), _P(C.c_float), _P(C.c_float), _P(C.c_float), _vp]),
     ("vspg_light_pdf_batch", C.c_int, [_vp, C.c_int, C.c_int, _P(C.c_float), _P(C.c_float), _P(C.c_float), _P(C.c_float), _P(C.c_float), _vp]),
     ("vspg_renderer_get_tr_buffer", C.c_int, [_vp, _P(C.c_float), _P(C.c_int32), _vp]),
@@ -621,6 +626,40 @@ def add_spot_light(scene, I, from_, to, coneangle=30, conedelta=5, scale=1, powe
         return lib.vspg_spot_light_look_at(C.byref(l), f3(*[float(v) for v in from_]), f3(*[float(v) for v in to]), cp)
     keep, cp = _ctm_pointer(ctm)
     return _add_point_light(scene, LIGHT_SPOT, I, sc, fill)
+
+
+def add_projection_light(scene, I, fov=90, ctm=None):
+    """LightSource "projection" (ProjectionLight::Create, lights.cpp:490-560): a slide projector at the origin of `ctm` looking along its
+    +z, I = the reference's `scale` as an RGB multiplier of the slide's texels, `fov` degrees across the slide's shorter axis.  The
+    slide is given to the renderer (Renderer.set_light_image; a 1 x 1 slide of ones until then).  No "power": its normalisation needs
+    the colour space's LuminanceVector."""
+    lib = load()
+    keep, cp = _ctm_pointer(ctm)
+    def fill(l):
+        l.cone_angle_deg = fov      # a projection slot's cone_angle_deg is its field of view (include/vspg.h)
+        return lib.vspg_projection_light_at(C.byref(l), cp)
+    return _add_point_light(scene, LIGHT_PROJECTION, I, 1, fill)
+
+
+def add_goniometric_light(scene, I, scale=1, power=None, ctm=None, image=None):
+    """LightSource "goniometric" (GoniometricLight::Create, lights.cpp:652-734): a bulb at the origin of `ctm` whose intensity is I (RGB)
+    times `scale` times a texel of a square equal-area map, given to the renderer (Renderer.set_light_image; a 1 x 1 map of ones -- a
+    point light -- until then).  power > 0 rescales as Create does: scale *= power / (4 Pi sumY / (width * height)), with the sum over
+    `image` (the [res, res] map the renderer will be given) or over the 1 x 1 map of ones."""
+    import numpy as np
+    lib = load()
+    sc = np.float32(scale)
+    if power is not None and power > 0:
+        sum_y, n = np.float32(1), 1
+        if image is not None:
+            img = np.asarray(image, dtype=np.float32).reshape(-1)
+            sum_y, n = np.float32(0), img.size
+            for v in img:
+                sum_y = sum_y + v
+        k_e = np.float32(4) * np.float32(np.pi) * sum_y / np.float32(n)
+        sc = sc * (np.float32(power) / k_e)
+    keep, cp = _ctm_pointer(ctm)
+    return _add_point_light(scene, LIGHT_GONIOMETRIC, I, sc, lambda l: lib.vspg_goniometric_light_at(C.byref(l), cp))
 
 
 def add_sphere_light(scene, sphere_index, L, scale=1, two_sided=False, power=None):
@@ -932,6 +971,18 @@ class Renderer:
         fp = _P(C.c_float)
         _check(self.lib, self.lib.vspg_renderer_set_environment_image(self.h, int(index), img.ctypes.data_as(fp), res,
                                                                      m.ctypes.data_as(fp) if m is not None else None, _vp(stream or 0)))
+
+    def set_light_image(self, index, image, stream=None):
+        """Give the projection or goniometric light in point-light slot `index` its image (vspg_renderer_set_light_image): a float32
+        NumPy array, top row first -- [yres, xres, 3] (R, G, B) for a projection light, [res, res] or [res, res, 1] (Y) for a
+        goniometric light.  The library judges everything else (the slot's type, the channels, the resolution, the pixel values).
+        Film, statistics, VSP buffer, guiding fields and counters stay."""
+        import numpy as np
+        if not isinstance(image, np.ndarray) or image.dtype != np.float32 or image.ndim not in (2, 3) or not image.flags["C_CONTIGUOUS"]:
+            raise ValueError("light image must be a C-contiguous float32 NumPy array [yres, xres] or [yres, xres, channels]")
+        channels = 1 if image.ndim == 2 else int(image.shape[2])
+        _check(self.lib, self.lib.vspg_renderer_set_light_image(self.h, int(index), image.ctypes.data_as(_P(C.c_float)), int(image.shape[1]),
+                                                               int(image.shape[0]), channels, _vp(stream or 0)))
 
     def envlight_batch(self, index, dirs, u):
         """[n, 16] float32 per (direction, variate pair): Le (3), its uv (2), PDF_Li, then SampleLi(u): valid, uv (2), wi (3), pdf,

@@ -310,6 +310,7 @@ struct VspgRenderer {
     float4 *rgb_oct[2] = {nullptr, nullptr};  // RGB grid medium: the octets of the sigma_a / sigma_s grid (vspg_rgbgrid.h), null = absent
     float *rgb_Le = nullptr;                  // ... its Le grid, raw
     float *env_buf[VSPG_MAX_INFINITE_LIGHTS] = {nullptr, nullptr, nullptr, nullptr};  // image infinite lights: one allocation per light (DEnvLight's arrays)
+    void *light_img_buf[VSPG_MAX_POINT_LIGHTS] = {};  // projection / goniometric lights: one allocation per slot (DImageLight::texels)
     DTri *tris = nullptr;          // triangle soup in BVH leaf order + the BVH (depth-first, skip links)
     DBvh4Node *bvh = nullptr;
     // wavefront pipeline (vspg_wavefront.h): path SoA, lists and per-iteration control blocks, allocated at first use
@@ -381,6 +382,23 @@ static int env_install(VspgRenderer *r, int k, const EnvTables &T, const float *
     E.mcdf = buf + T.o_mcdf;
     *old_buf = r->env_buf[k];
     r->env_buf[k] = buf;
+    return 0;
+}
+
+// The same for a projection / goniometric light's image (point-light slot k)
+static int image_light_install(VspgRenderer *r, int k, const ImageLightTables &T, hipStream_t s, void **old_buf) {
+    void *buf = nullptr;
+    HIPCHK(hipMalloc(&buf, T.buf.size() * sizeof(float)));
+    hipError_t e = hipMemcpyAsync(buf, T.buf.data(), T.buf.size() * sizeof(float), hipMemcpyHostToDevice, s);
+    if (e == hipSuccess) e = hipStreamSynchronize(s);
+    if (e != hipSuccess) {
+        (void)hipFree(buf);
+        return fail(VSPG_EHIP, std::string("uploading the light image: ") + hipGetErrorName(e));
+    }
+    image_light_apply(T, &r->hscene.image_light[k]);
+    r->hscene.image_light[k].texels = buf;
+    *old_buf = r->light_img_buf[k];
+    r->light_img_buf[k] = buf;
     return 0;
 }
 
@@ -740,6 +758,14 @@ int vspg_renderer_create(const VspgScene *scene, const VspgIntegratorParams *par
             env_matrices(nullptr, m, mi);
             if (const int erc = env_install(r, k, T, m, mi, nullptr, &old)) { vspg_renderer_destroy(r); return erc; }
         }
+    for (int k = 0; k < r->hscene.n_point; ++k)
+        if (r->hscene.point[k].type == VSPG_LIGHT_PROJECTION || r->hscene.point[k].type == VSPG_LIGHT_GONIOMETRIC) {  // the 1 x 1 image of ones
+            const float ones[3] = {1.f, 1.f, 1.f};
+            ImageLightTables T;
+            image_light_build(r->hscene.point[k].type, ones, 1, 1, scene->point_lights[k].cone_angle_deg, &T);
+            void *old = nullptr;
+            if (const int irc = image_light_install(r, k, T, nullptr, &old)) { vspg_renderer_destroy(r); return irc; }
+        }
     CK(hipMalloc(&r->dscene, sizeof(DScene)));
     CK(hipMemcpy(r->dscene, &r->hscene, sizeof(DScene), hipMemcpyHostToDevice));
     CK(hipMalloc(&r->film, r->npix * sizeof(float4)));
@@ -879,6 +905,7 @@ int vspg_renderer_destroy(VspgRenderer *r) {
     for (int k = 0; k < 2; ++k) if (r->rgb_oct[k]) (void)hipFree(r->rgb_oct[k]);
     if (r->rgb_Le) (void)hipFree(r->rgb_Le);
     for (int k = 0; k < VSPG_MAX_INFINITE_LIGHTS; ++k) if (r->env_buf[k]) (void)hipFree(r->env_buf[k]);
+    for (int k = 0; k < VSPG_MAX_POINT_LIGHTS; ++k) if (r->light_img_buf[k]) (void)hipFree(r->light_img_buf[k]);
     if (r->fe_ref) (void)hipFree(r->fe_ref);
     if (r->fe_partials) (void)hipFree(r->fe_partials);
     if (r->fe_log) (void)hipFree(r->fe_log);
@@ -2194,6 +2221,31 @@ int vspg_renderer_set_environment_image(VspgRenderer *r, int infinite_light_inde
     lsb::build(r->scene, r->prm, &r->hscene);  // the power sampler's alias table: the light's Phi changed
     // the light sampler and the environment slots are the tail of the record; the rest of the device's copy (the guiding fields a
     // training renderer updates in place) is not touched
+    const size_t tail = offsetof(DScene, lsamp);
+    HIPCHK(hipMemcpyAsync(reinterpret_cast<char *>(r->dscene) + tail, reinterpret_cast<const char *>(&r->hscene) + tail, sizeof(DScene) - tail,
+                          hipMemcpyHostToDevice, s));
+    HIPCHK(hipStreamSynchronize(s));
+    if (old) (void)hipFree(old);
+    return 0;
+}
+
+int vspg_renderer_set_light_image(VspgRenderer *r, int point_light_index, const float *host_pixels, int xres, int yres, int channels, void *stream) {
+    // every refusal comes before anything of the renderer changes and before any allocation
+    if (!r || !host_pixels) return fail(VSPG_EINVAL, "null argument");
+    const int k = point_light_index;
+    if (k < 0 || k >= r->hscene.n_point) return fail(VSPG_EINVAL, "point_light_index names no point-light slot of the scene");
+    const int type = r->hscene.point[k].type;
+    if (const int rc = image_light_refusal(type, host_pixels, xres, yres, channels)) return rc;
+    ImageLightTables T;
+    image_light_build(type, host_pixels, xres, yres, r->scene.point_lights[k].cone_angle_deg, &T);
+    HIPCHK(hipSetDevice(r->cfg.device));
+    hipStream_t s = (hipStream_t)stream;
+    if (const int rc = flush_parked_samples(r, s)) return rc;  // (paths in flight end under the image they started under)
+    HIPCHK(hipStreamSynchronize(s));  // no launch may still read the old image
+    void *old = nullptr;
+    if (const int rc = image_light_install(r, k, T, s, &old)) return rc;
+    lsb::build(r->scene, r->prm, &r->hscene);  // the alias table and the BVH: the light's Phi and LightBounds changed
+    // the light sampler and every light's slots are the tail of the record (as in vspg_renderer_set_environment_image)
     const size_t tail = offsetof(DScene, lsamp);
     HIPCHK(hipMemcpyAsync(reinterpret_cast<char *>(r->dscene) + tail, reinterpret_cast<const char *>(&r->hscene) + tail, sizeof(DScene) - tail,
                           hipMemcpyHostToDevice, s));

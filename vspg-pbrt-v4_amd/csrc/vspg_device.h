@@ -773,12 +773,29 @@ struct DEnvLight {
 // Point / spot light (vspg_pointlight.h): the position renderFromLight(0, 0, 0), I = scale * I multiplied out, rows 0..2 of mInv
 // (row-major, 3 x 4) and the SpotLight constructor's two cosines, all formed on the host.
 struct DPointLight {
-    int32_t type;  // VSPG_LIGHT_POINT | VSPG_LIGHT_SPOT
+    int32_t type;  // VSPG_LIGHT_POINT | VSPG_LIGHT_SPOT | VSPG_LIGHT_PROJECTION | VSPG_LIGHT_GONIOMETRIC (the image: DImageLight)
     float pos[3];
     float I[3];
     float mi[12];
     float cosFalloffEnd, cosFalloffStart;
     float axis[3];  // host only: Normalize(renderFromLight(Vector3f(0, 0, 1))), the w of SpotLight::Bounds
+};
+// Projection / goniometric light (vspg_imagelight.h), one record per POINT-LIGHT SLOT beside its DPointLight, which keeps its size: the
+// image (a projection slide: one float4 per texel, clamped at zero, pad 0; a goniometric map: one float per texel; top row first) and,
+// for a projection light, the constructor's screen window, rows 0, 1 and 3 of screenFromLight = Perspective(fov, hither, 1e30) -- the
+// rows Transform::operator()(Point3f) needs for ps.x, ps.y and the divide -- and hither.  Built on the host (image_light_build,
+// vspg_scene_build.hip) with the renderer and by vspg_renderer_set_light_image.
+struct DImageLight {
+    int32_t xres, yres;
+    const void *texels;
+    float sb[4];      // screenBounds: pMin.x, pMin.y, pMax.x, pMax.y
+    float sfl[12];    // screenFromLight rows 0, 1, 3
+    float hither;
+    // host only: what Phi() and Bounds() take from the image and the projection
+    float A;             // the projection's image area
+    float sum_phi[3];    // projection: per channel, ClampZero(texel) * dwdA summed in image order; goniometric: [0] = the texels' sum
+    float sum_bounds;    // projection: max(R, G, B) of the raw texels summed in image order; goniometric: the texels' sum
+    float cosTotalWidth; // projection: CosTheta of the direction through the screen window's corner
 };
 // DiffuseAreaLight on a sphere (vspg_spherelight.h), one record per SPHERE (index = the sphere's): what the light adds to the
 // DSphere beside it, which keeps its size -- DSphere sits in front of fields whose offsets the rectangle-scene kernels rely on.
@@ -888,6 +905,9 @@ struct DScene {
     const float4 *rgb_oct_a, *rgb_oct_s;
     const float *rgb_Le;
     float rgb_sigma_scale, rgb_le_scale;
+    // projection and goniometric lights: image_light[i] belongs to point[i] where that slot's type is one of the two.  Behind everything
+    // else: only sample_light<FULL> reads here, and only for such a slot.
+    DImageLight image_light[VSPG_MAX_POINT_LIGHTS];
 };
 // the length of the scene's light list (full-scene kernels): one line per light kind
 __host__ __device__ __forceinline__ int light_list_size(const DScene &S) { return S.n_lights + S.n_inf + S.n_point + S.n_sphere_lights; }

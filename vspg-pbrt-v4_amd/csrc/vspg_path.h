@@ -88,6 +88,7 @@ struct LightLi {
 };
 #include "vspg_envlight.h"  // the image infinite light: env_Le / env_sample_li / env_pdf_li (fills a LightLi)
 #include "vspg_pointlight.h"  // point and spot lights: point_sample_li / spot_sample_li (fill a LightLi)
+#include "vspg_imagelight.h"  // projection and goniometric lights: projection_sample_li / goniometric_sample_li (fill a LightLi)
 VDEV bool light_sample_li(const DQuad &q, V3 ctxp, float u0, float u1, LightLi *ls) {
     V3 p00 = ld3(q.p00), p10 = ld3(q.p10), p01 = ld3(q.p01), p11 = ld3(q.p11);
     V3 pu0 = lerp(u1, p00, p01), pu1 = lerp(u1, p10, p11);
@@ -136,6 +137,8 @@ VDEV bool sample_light(const DScene &S, int lightIndex, V3 ctxp, const LsCtx &lc
     if (k >= S.n_inf) {  // the third range of the light list: PointLight / SpotLight::SampleLi (vspg_pointlight.h)
         const DPointLight &P = S.point[k - S.n_inf];
         *delta_light = true;
+        if (P.type >= VSPG_LIGHT_PROJECTION)  // ProjectionLight / GoniometricLight::SampleLi (vspg_imagelight.h)
+            return image_light_sample_li(P, S.image_light[k - S.n_inf], ctxp, ls);
         return P.type == VSPG_LIGHT_SPOT ? spot_sample_li(P, ctxp, ls) : point_sample_li(P, ctxp, ls);
     }
     if (S.inf_type[k] == VSPG_LIGHT_IMAGE_INFINITE) {  // ImageInfiniteLight::SampleLi (lights.h:650-674); `!ls->L || ls->pdf == 0` of :1167

@@ -131,6 +131,20 @@ int vspg_point_light_at(VspgPointLight *l, const float from[3], const float ctm[
     for (int k = 0; k < 3; ++k) { t[4 * k + 3] = from[k]; ti[4 * k + 3] = -from[k]; }  // Translate (transform.cpp:38-43)
     return light_compose(l, ctm, t, ti);
 }
+// ProjectionLight::Create (lights.cpp:555-556): ctm * Scale(1, -1, 1); Scale's minv holds 1 / y = -1 (transform.cpp:35-45)
+int vspg_projection_light_at(VspgPointLight *l, const float ctm[16]) {
+    if (!l) return fail(VSPG_EINVAL, "null argument");
+    float t[16];
+    mat4_identity(t);
+    t[5] = -1.f;
+    return light_compose(l, ctm, t, t);
+}
+// GoniometricLight::Create (lights.cpp:724-726): ctm * Transform(swapYZ); the swap is its own inverse
+int vspg_goniometric_light_at(VspgPointLight *l, const float ctm[16]) {
+    if (!l) return fail(VSPG_EINVAL, "null argument");
+    const float t[16] = {1, 0, 0, 0, 0, 0, 1, 0, 0, 1, 0, 0, 0, 0, 0, 1};
+    return light_compose(l, ctm, t, t);
+}
 int vspg_spot_light_look_at(VspgPointLight *l, const float from[3], const float to[3], const float ctm[16]) {
     if (!l || !from || !to) return fail(VSPG_EINVAL, "null argument");
     for (int k = 0; k < 3; ++k)

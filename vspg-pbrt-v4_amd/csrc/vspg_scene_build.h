@@ -73,5 +73,17 @@ struct EnvTables {
 void env_build_tables(const float *rgb, int res, EnvTables *T);
 bool env_matrices(const float *m34, float *m, float *mi);
 
+// ---- projection and goniometric lights: the host side of vspg_imagelight.h ------------------------------------------------------
+// What one light's image becomes: the device image (projection: a float4 per texel, clamped at zero, pad 0; goniometric: the texels as
+// given) and the host-side fields of its DImageLight
+struct ImageLightTables {
+    int type = 0, xres = 0, yres = 0;
+    std::vector<float> buf;
+    float sb[4], sfl[12], hither = 0.f, A = 0.f, sum_phi[3], sum_bounds = 0.f, cosTotalWidth = 0.f;
+};
+int image_light_refusal(int type, const float *pixels, int xres, int yres, int channels);
+void image_light_build(int type, const float *pixels, int xres, int yres, float fov_deg, ImageLightTables *T);
+void image_light_apply(const ImageLightTables &T, DImageLight *G);
+
 }  // namespace vspg_host
 #pragma GCC visibility pop

@@ -284,12 +284,26 @@ static lightbounds_t sphere_light_bounds(const DSphere &S, const DSphereLight &E
     lb.twoSided = E.two_sided;
     return lb;
 }
-static lightbounds_t point_light_bounds(const DPointLight &P) {
+// ProjectionLight::Bounds (lights.cpp:426-441): phi = scale * sum of max(R, G, B) / (width * height), the cone of the screen window's corner
+// around Normalize(renderFromLight(Vector3f(0, 0, 1))); GoniometricLight::Bounds (:612-624): "Bound it as an isotropic point light", phi =
+// scale * Iemit->MaxValue() * 4 * Pi * sumY / (width * height).  Where the reference has a scalar scale the record has an RGB I: its
+// largest component, as PointLight::Bounds takes MaxValue.
+static lightbounds_t point_light_bounds(const DPointLight &P, const DImageLight &G) {
     lightbounds_t lb;
     lb.bmin = lb.bmax = V3(P.pos[0], P.pos[1], P.pos[2]);
     const float maxI = fmaxf(P.I[0], fmaxf(P.I[1], P.I[2]));  // scale * I->MaxValue()
     lb.twoSided = 0;
-    if (P.type == VSPG_LIGHT_SPOT) {
+    if (P.type == VSPG_LIGHT_PROJECTION) {
+        lb.w = V3(P.axis[0], P.axis[1], P.axis[2]);
+        lb.phi = maxI * G.sum_bounds / (float)(G.xres * G.yres);
+        lb.cosTheta_o = cosf(0.f);
+        lb.cosTheta_e = G.cosTotalWidth;
+    } else if (P.type == VSPG_LIGHT_GONIOMETRIC) {
+        lb.w = V3(0, 0, 1);
+        lb.phi = maxI * 4 * PI_F * G.sum_bounds / (float)(G.xres * G.yres);
+        lb.cosTheta_o = cosf(PI_F);
+        lb.cosTheta_e = cosf(PI_F / 2);
+    } else if (P.type == VSPG_LIGHT_SPOT) {
         lb.w = V3(P.axis[0], P.axis[1], P.axis[2]);
         lb.phi = maxI * 4 * PI_F;
         lb.cosTheta_o = P.cosFalloffStart;
@@ -305,7 +319,8 @@ static lightbounds_t point_light_bounds(const DPointLight &P) {
     }
     return lb;
 }
-// (called again by vspg_renderer_set_environment_image: the power sampler's table depends on an image light's Phi)
+// (called again by vspg_renderer_set_environment_image and vspg_renderer_set_light_image: the power sampler's table depends on an image
+// light's Phi, the BVH on a projection / goniometric light's LightBounds)
 void build(const VspgScene &sc, const VspgIntegratorParams &prm, DScene *D) {
     DLightSampler *ls = &D->lsamp;
     std::memset(ls, 0, sizeof *ls);
@@ -324,7 +339,7 @@ void build(const VspgScene &sc, const VspgIntegratorParams &prm, DScene *D) {
         if (i >= D->n_lights && i < first_point) { ls->inf_light[ls->n_inf++] = i; continue; }  // Bounds() == {}
         lightbounds_t lb;
         if (i >= first_sphere) lb = sphere_light_bounds(D->spheres[D->light_spheres[i - first_sphere]], D->sphere_light[D->light_spheres[i - first_sphere]]);
-        else if (i >= first_point) lb = point_light_bounds(D->point[i - first_point]);
+        else if (i >= first_point) lb = point_light_bounds(D->point[i - first_point], D->image_light[i - first_point]);
         else {
             const int qi = D->light_quads[i];
             lb = quad_light_bounds(D->quads[qi], sc.quads[qi].reverse_orientation);
@@ -367,6 +382,16 @@ void build(const VspgScene &sc, const VspgIntegratorParams &prm, DScene *D) {
                     // SpotLight::Phi (lights.cpp:1452-1455) in its order: scale * Iemit * 2 * Pi * ((1 - cosStart) + (cosStart - cosEnd) / 2)
                     const float cone = (1 - P.cosFalloffStart) + (P.cosFalloffStart - P.cosFalloffEnd) / 2;
                     for (int c = 0; c < 3; ++c) phi[c] = L[c] * 2 * PI_F * cone;
+                    have_phi = true;
+                } else if (P.type == VSPG_LIGHT_PROJECTION) {
+                    // ProjectionLight::Phi (lights.cpp:404-424) in its order: scale * A * sum / (width * height), per channel of I
+                    const DImageLight &G = D->image_light[i - first_point];
+                    for (int c = 0; c < 3; ++c) phi[c] = L[c] * G.A * G.sum_phi[c] / (float)(G.xres * G.yres);
+                    have_phi = true;
+                } else if (P.type == VSPG_LIGHT_GONIOMETRIC) {
+                    // GoniometricLight::Phi (lights.cpp:603-610) in its order: scale * Iemit * 4 * Pi * sumY / (width * height)
+                    const DImageLight &G = D->image_light[i - first_point];
+                    for (int c = 0; c < 3; ++c) phi[c] = L[c] * 4 * PI_F * G.sum_phi[0] / (float)(G.xres * G.yres);
                     have_phi = true;
                 }
             } else {
@@ -481,6 +506,113 @@ bool env_matrices(const float *m34, float *m, float *mi) {
     }
     return true;
 }
+// ---- projection and goniometric lights: the host side of vspg_imagelight.h (ImageLightTables: vspg_scene_build.h) -------------------
+// The refusals of vspg_renderer_set_light_image that need no renderer, in its order; 0 or VSPG_EINVAL with the message set
+int image_light_refusal(int type, const float *pixels, int xres, int yres, int channels) {
+    if (!pixels) return fail(VSPG_EINVAL, "null argument");
+    if (type != VSPG_LIGHT_PROJECTION && type != VSPG_LIGHT_GONIOMETRIC) return fail(VSPG_EINVAL, "the point light is neither a projection nor a goniometric light");
+    if (channels != (type == VSPG_LIGHT_PROJECTION ? 3 : 1))
+        return fail(VSPG_EINVAL, type == VSPG_LIGHT_PROJECTION ? "a projection light's image has 3 channels (R, G, B)" : "a goniometric light's image has 1 channel (Y)");
+    if (xres < 1 || xres > VSPG_LIGHT_IMAGE_MAX_RES || yres < 1 || yres > VSPG_LIGHT_IMAGE_MAX_RES)
+        return fail(VSPG_EINVAL, "light image resolution outside 1 .. VSPG_LIGHT_IMAGE_MAX_RES (4096)");
+    if (type == VSPG_LIGHT_GONIOMETRIC && xres != yres) return fail(VSPG_EINVAL, "goniometric image resolution is non-square: it's unlikely this is an equal-area environment map");
+    const size_t n = (size_t)xres * yres * channels;
+    for (size_t i = 0; i < n; ++i) {
+        if (pixels[i] != pixels[i]) return fail(VSPG_EINVAL, "light image has not-a-number pixel values and so is not suitable as a light");
+        if (std::isinf(pixels[i])) return fail(VSPG_EINVAL, "light image has infinite pixel values and so is not suitable as a light");
+    }
+    return 0;
+}
+// What the two constructors, Phi() and Bounds() derive from the image (and, for a projection light, the field of view), in the
+// reference's order of operations.  The arguments have passed image_light_refusal; fov_deg lies in (0, 180).
+void image_light_build(int type, const float *pixels, int xres, int yres, float fov_deg, ImageLightTables *T) {
+    using namespace hostmath;
+    const size_t n = (size_t)xres * yres;
+    T->type = type;
+    T->xres = xres;
+    T->yres = yres;
+    T->hither = 1e-3f;
+    T->A = 0.f;
+    T->cosTotalWidth = 0.f;
+    for (int k = 0; k < 4; ++k) T->sb[k] = 0.f;
+    for (int k = 0; k < 12; ++k) T->sfl[k] = 0.f;
+    for (int c = 0; c < 3; ++c) T->sum_phi[c] = 0.f;
+    if (type == VSPG_LIGHT_GONIOMETRIC) {
+        T->buf.assign(pixels, pixels + n);
+        float sumY = 0;  // Phi (lights.cpp:604-607) and Bounds (:613-616): the same sum, rows then columns
+        for (size_t i = 0; i < n; ++i) sumY += pixels[i];
+        T->sum_phi[0] = sumY;
+        T->sum_bounds = sumY;
+        return;
+    }
+    // the constructor (lights.cpp:334-344): the screen window, screenFromLight = Perspective(fov, hither, 1e30), its inverse, A
+    const float aspect = (float)xres / (float)yres;
+    if (aspect > 1) { T->sb[0] = -aspect; T->sb[1] = -1; T->sb[2] = aspect; T->sb[3] = 1; }
+    else { T->sb[0] = -1; T->sb[1] = -1 / aspect; T->sb[2] = 1; T->sb[3] = 1 / aspect; }
+    // Perspective (transform.cpp:119-131): persp = {1 0 0 0; 0 1 0 0; 0 0 f/(f-n) -f*n/(f-n); 0 0 1 0}, then Scale(invTanAng, invTanAng, 1) *
+    // Transform(persp).  The product accumulates by FMA from 0 (SquareMatrix::operator*): next to exact zeros and ones every entry is one
+    // factor as it stands.
+    const float nn = T->hither, ff = 1e30f;
+    const float pa = ff / (ff - nn), pb = -ff * nn / (ff - nn);
+    const float deg2rad = 3.14159265358979323846f / 180;  // Radians (math.h:261-263)
+    const float half = (deg2rad * fov_deg) / 2;
+    const float invTanAng = 1 / std::tan(half);
+    T->sfl[0] = invTanAng;   // row 0: {invTanAng, 0, 0, 0}
+    T->sfl[5] = invTanAng;   // row 1: {0, invTanAng, 0, 0}
+    T->sfl[10] = 1.f;        // row 3: {0, 0, 1, 0}
+    // Transform(persp)'s mInv = Inverse(persp) (util/math.h:1571-1624): of the 2 x 2 sub-determinants only s0 = 1 and c5 = -pb are not
+    // zero (DifferenceOfProducts is exact there), determinant = -pb, s = 1 / determinant, and the entries that are not zero are
+    //   [0][0] = [1][1] = [2][3] = s * -pb   [3][2] = s * -1   [3][3] = s * pa
+    // lightFromScreen = Inverse(screenFromLight): m = Inverse(persp) * Scale's minv = diag(1 / invTanAng, 1 / invTanAng, 1, 1).
+    const float det = -pb, si = 1 / det;
+    const float one = si * -pb;
+    const float l00 = one * (1 / invTanAng), l23 = one, l33 = si * pa;
+    // lightFromScreen(Point3f(x, y, 0)) (transform.h:310-319), then Vector3f, Normalize: the direction through a screen point
+    auto dir = [&](float x, float y) {
+        const float xp = l00 * x + 0.f * y + 0.f * 0.f + 0.f, yp = 0.f * x + l00 * y + 0.f * 0.f + 0.f, zp = 0.f * x + 0.f * y + 0.f * 0.f + l23;
+        const float wp = 0.f * x + 0.f * y + -si * 0.f + l33;
+        const H3 v = wp == 1 ? H3{xp, yp, zp} : H3{xp / wp, yp / wp, zp / wp};
+        return normv(v);
+    };
+    const float opposite = std::tan(half);
+    T->A = 4 * (opposite * opposite) * (aspect > 1 ? aspect : (1 / aspect));
+    T->cosTotalWidth = dir(T->sb[2], T->sb[3]).z;  // Bounds (lights.cpp:434-436)
+    // the device image: ClampZero(rgb) and a zero pad per texel; Phi's sum (lights.cpp:405-421) and Bounds' (:427-431) on the way
+    T->buf.assign(4 * n, 0.f);
+    float sum[3] = {0.f, 0.f, 0.f}, sum_max = 0;
+    for (int y = 0; y < yres; ++y)
+        for (int x = 0; x < xres; ++x) {
+            const float tx = (x + 0.5f) / xres, ty = (y + 0.5f) / yres;
+            // screenBounds.Lerp (vecmath.h:1228-1231): Lerp(t, a, b) = (1 - t) * a + t * b (math.h:210-212)
+            const float px = (1 - tx) * T->sb[0] + tx * T->sb[2], py = (1 - ty) * T->sb[1] + ty * T->sb[3];
+            const float c = dir(px, py).z;
+            const float dwdA = c * c * c;  // Pow<3>
+            const float *t = pixels + 3 * ((size_t)y * xres + x);
+            float *o = T->buf.data() + 4 * ((size_t)y * xres + x);
+            for (int k = 0; k < 3; ++k) {
+                o[k] = 0.f < t[k] ? t[k] : 0.f;  // ClampZero: std::max<Float>(0, v)
+                sum[k] += o[k] * dwdA;
+            }
+            float m = t[0];  // std::max({R, G, B})
+            if (m < t[1]) m = t[1];
+            if (m < t[2]) m = t[2];
+            sum_max += m;
+        }
+    for (int k = 0; k < 3; ++k) T->sum_phi[k] = sum[k];
+    T->sum_bounds = sum_max;
+}
+// ... into a slot's record; the texel pointer is the renderer's to set
+void image_light_apply(const ImageLightTables &T, DImageLight *G) {
+    G->xres = T.xres;
+    G->yres = T.yres;
+    for (int k = 0; k < 4; ++k) G->sb[k] = T.sb[k];
+    for (int k = 0; k < 12; ++k) G->sfl[k] = T.sfl[k];
+    G->hither = T.hither;
+    G->A = T.A;
+    for (int k = 0; k < 3; ++k) G->sum_phi[k] = T.sum_phi[k];
+    G->sum_bounds = T.sum_bounds;
+    G->cosTotalWidth = T.cosTotalWidth;
+}
 // SURF_* flags from the C-ABI's material / medium_interface pair: a MediumInterface only counts when it is a TRANSITION
 // (inside != outside, base/medium.h:124)
 static int32_t surf_flags_of(int material, int medium_interface) {
@@ -562,6 +694,13 @@ void build_dscene(const VspgScene &sc, const VspgIntegratorParams &prm, const Vs
         for (int k = 0; k < 12; ++k) P.mi[k] = in.light_from_render[k];
         P.cosFalloffEnd = P.cosFalloffStart = 0.f;
         P.axis[0] = P.axis[1] = 0.f; P.axis[2] = 1.f;
+        if (in.type == VSPG_LIGHT_PROJECTION || in.type == VSPG_LIGHT_GONIOMETRIC) {
+            // the 1 x 1 image of ones (include/vspg.h): the light is valid from creation on; vspg_renderer_create uploads the texel
+            const float ones[3] = {1.f, 1.f, 1.f};
+            ImageLightTables T;
+            image_light_build(in.type, ones, 1, 1, in.cone_angle_deg, &T);
+            image_light_apply(T, &D->image_light[i]);
+        }
         if (in.type == VSPG_LIGHT_SPOT) {
             // the constructor's cosines (lights.cpp:1438-1439): totalWidth = coneangle, falloffStart = coneangle - conedelta; Radians (math.h:261-263)
             volatile float start_deg = in.cone_angle_deg - in.cone_delta_deg;
@@ -569,7 +708,9 @@ void build_dscene(const VspgScene &sc, const VspgIntegratorParams &prm, const Vs
             volatile float rad_end = deg2rad * in.cone_angle_deg, rad_start = deg2rad * start_deg;
             P.cosFalloffEnd = std::cos((float)rad_end);
             P.cosFalloffStart = std::cos((float)rad_start);
-            // Normalize(renderFromLight(Vector3f(0, 0, 1))) (transform.h:351-356), the w of SpotLight::Bounds
+        }
+        if (in.type == VSPG_LIGHT_SPOT || in.type == VSPG_LIGHT_PROJECTION) {
+            // Normalize(renderFromLight(Vector3f(0, 0, 1))) (transform.h:351-356), the w of SpotLight::Bounds and of ProjectionLight::Bounds (lights.cpp:439)
             float w[3];
             for (int k = 0; k < 3; ++k) {
                 volatile float a = m[4 * k] * 0.f;
@@ -1206,7 +1347,8 @@ int validate(const VspgScene *scene, const VspgIntegratorParams *p, const VspgRe
     if (scene->n_point_lights < 0 || scene->n_point_lights > VSPG_MAX_POINT_LIGHTS) return fail(VSPG_EINVAL, "n_point_lights out of range");
     for (int i = 0; i < scene->n_point_lights; ++i) {
         const VspgPointLight &pl = scene->point_lights[i];
-        if (pl.type != VSPG_LIGHT_POINT && pl.type != VSPG_LIGHT_SPOT) return fail(VSPG_EINVAL, "unknown point light type");
+        if (pl.type != VSPG_LIGHT_POINT && pl.type != VSPG_LIGHT_SPOT && pl.type != VSPG_LIGHT_PROJECTION && pl.type != VSPG_LIGHT_GONIOMETRIC)
+            return fail(VSPG_EINVAL, "unknown point light type");
         const float *a = pl.render_from_light, *b = pl.light_from_render;
         for (int k = 0; k < 16; ++k)
             if (!std::isfinite(a[k]) || !std::isfinite(b[k])) return fail(VSPG_EINVAL, "a point light's renderFromLight is not finite");
@@ -1218,6 +1360,20 @@ int validate(const VspgScene *scene, const VspgIntegratorParams *p, const VspgRe
             if (!(pl.cone_angle_deg > 0 && pl.cone_angle_deg <= 180)) return fail(VSPG_EINVAL, "a spot light's cone_angle_deg must be in (0, 180]");
             if (!(pl.cone_delta_deg >= 0)) return fail(VSPG_EINVAL, "a spot light's cone_delta_deg must be >= 0");
             if (!(pl.cone_delta_deg <= pl.cone_angle_deg)) return fail(VSPG_EINVAL, "a spot light's cone_delta_deg exceeds cone_angle_deg");
+        }
+        if (pl.type == VSPG_LIGHT_PROJECTION) {
+            const float fov = pl.cone_angle_deg;  // a projection slot's field of view
+            if (!(fov > 0 && fov < 180)) return fail(VSPG_EINVAL, "a projection light's field of view (cone_angle_deg) must be in (0, 180)");
+        }
+        if (pl.type == VSPG_LIGHT_GONIOMETRIC) {
+            // EqualAreaSphereToSquare is defined for unit vectors, and ApplyInverse(-wi) is not normalised: R R^T = 1 within 1e-4 (include/vspg.h)
+            for (int r = 0; r < 3; ++r)
+                for (int c = 0; c < 3; ++c) {
+                    double d = 0;
+                    for (int k = 0; k < 3; ++k) d += (double)b[4 * r + k] * (double)b[4 * c + k];
+                    if (!(std::fabs(d - (r == c ? 1.0 : 0.0)) <= 1e-4))
+                        return fail(VSPG_ESCOPE, "a goniometric light's transform must be orthonormal (rotations and reflections only): the equal-area mapping takes unit vectors");
+                }
         }
     }
     int nl = scene->n_infinite_lights;

@@ -735,6 +735,10 @@ void GuidedVolPathVSPGIntegrator::SetEnvironmentImage(int light, const std::vect
     if (res < 1 || rgb.size() != (size_t)res * res * 3) throw Error("the environment image does not hold res * res * 3 values");
     if (vspg_renderer_set_environment_image(renderer, light, rgb.data(), res, renderFromLight, nullptr) != 0) throw Error(vspg_last_error());
 }
+void GuidedVolPathVSPGIntegrator::SetLightImage(int slot, const std::vector<float> &pixels, int xres, int yres, int channels) {
+    if (xres < 1 || yres < 1 || channels < 1 || pixels.size() != (size_t)xres * yres * channels) throw Error("the light image does not hold xres * yres * channels values");
+    if (vspg_renderer_set_light_image(renderer, slot, pixels.data(), xres, yres, channels, nullptr) != 0) throw Error(vspg_last_error());
+}
 void GuidedVolPathVSPGIntegrator::SetMediumDensity(const std::vector<float> &values) {
     if (vspg_renderer_update_grid(renderer, VSPG_GRID_DENSITY, values.data(), values.size(), VSPG_MEM_HOST, nullptr) != 0) throw Error(vspg_last_error());
 }

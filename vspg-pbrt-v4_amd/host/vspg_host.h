@@ -180,6 +180,9 @@ class Integrator {
     // The image of image infinite light `light` (an index into the scene's infinite lights): res * res * 3 floats, top row first, and
     // the rows of renderFromLight (12 floats) or nullptr for the identity (vspg_renderer_set_environment_image).  Throws on refusal.
     virtual void SetEnvironmentImage(int light, const std::vector<float> &rgb, int res, const float *renderFromLight) = 0;
+    // The image of the projection / goniometric light in point-light slot `slot`: xres * yres * channels floats, top row first, 3 channels
+    // (R, G, B) or 1 (Y) (vspg_renderer_set_light_image).  Throws on refusal.
+    virtual void SetLightImage(int slot, const std::vector<float> &pixels, int xres, int yres, int channels) = 0;
     // Integrator::Create: "guidedvolpathvspg"; "guidedvolpath" is accepted as an alias ONLY when
     // the dictionary carries "vspguiding" (the option BASELINE.json names), see SURVEY.md 0.1
     static std::unique_ptr<Integrator> Create(const std::string &name, const ParameterDictionary &parameters,
@@ -202,6 +205,7 @@ class GuidedVolPathVSPGIntegrator : public Integrator {
     Film GetFilm();               // the pixels of the pixel bounds (RGBFilm::WriteImage, film.cpp:541-557)
     void SetPixelBounds(int x0, int y0, int x1, int y1) override;
     void SetEnvironmentImage(int light, const std::vector<float> &rgb, int res, const float *renderFromLight) override;
+    void SetLightImage(int slot, const std::vector<float> &pixels, int xres, int yres, int channels) override;
     VspgCounters Counters();
     VspgTrainStats TrainingStats();      // guideTraining / guiding_field->GetIteration()
     GuidingCache GetGuidingCache();      // the field as it stands (trained in-loop or loaded)

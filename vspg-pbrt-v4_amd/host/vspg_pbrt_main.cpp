@@ -78,8 +78,16 @@ int main(int argc, char **argv) {
         }
         for (int i = 0; i < sd->scene.n_point_lights; ++i) {  // one line per point light: position (renderFromLight's translation) and I, %.9g round-trips a float
             const VspgPointLight &pl = sd->scene.point_lights[i];
-            std::printf("point light %d: type %d at (%.9g, %.9g, %.9g) I (%.9g, %.9g, %.9g)\n", i, pl.type, pl.render_from_light[3], pl.render_from_light[7],
+            std::printf("point light %d: type %d at (%.9g, %.9g, %.9g) I (%.9g, %.9g, %.9g)", i, pl.type, pl.render_from_light[3], pl.render_from_light[7],
                         pl.render_from_light[11], pl.I[0], pl.I[1], pl.I[2]);
+            if (pl.type == VSPG_LIGHT_PROJECTION || pl.type == VSPG_LIGHT_GONIOMETRIC) {  // ... and of a projection / goniometric light its image
+                int xres = 1, yres = 1;
+                for (const auto &l : sd->lightImages)
+                    if (l.slot == i) { xres = l.xres; yres = l.yres; }
+                std::printf(" %s image %d x %d", pl.type == VSPG_LIGHT_PROJECTION ? "projection" : "goniometric", xres, yres);
+                if (pl.type == VSPG_LIGHT_PROJECTION) std::printf(" fov %.9g", pl.cone_angle_deg);
+            }
+            std::printf("\n");
         }
         if (parseOnly) return 0;
         auto integrator = vspg::CreateIntegrator(*sd, device);

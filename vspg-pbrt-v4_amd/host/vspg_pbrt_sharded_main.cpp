@@ -51,6 +51,8 @@ int main(int argc, char **argv) {
         if (vspg_renderer_create(&sd->scene, &prm, &cfg, &r) != 0) throw vspg::Error(vspg_last_error());
         for (const auto &e : sd->envImages)  // LightSource "infinite" "string filename": every rank holds the whole image
             if (vspg_renderer_set_environment_image(r, e.light, e.rgb.data(), e.res, e.renderFromLight, nullptr) != 0) throw vspg::Error(vspg_last_error());
+        for (const auto &l : sd->lightImages)  // LightSource "projection" / "goniometric" "string filename"
+            if (vspg_renderer_set_light_image(r, l.slot, l.pixels.data(), l.xres, l.yres, l.channels, nullptr) != 0) throw vspg::Error(vspg_last_error());
         int seen = 0;
         if (vspg_rccl_ranks_seen(comm, nullptr, &seen) != 0 || seen != world) throw vspg::Error("RCCL launch check: " + std::to_string(seen) + " of " + std::to_string(world) + " ranks answered");
         if (world > 1 && vspg_rccl_enable_training_exchange(r, comm) != 0) throw vspg::Error("training exchange set-up failed");

@@ -362,8 +362,111 @@ class Parser {
         if (vspg_point_light_at(&pl, from, ctm) != 0) fail(std::string("LightSource \"point\": ") + vspg_last_error());
         sd->scene.n_point_lights++;
     }
+    void ctm16(float ctm[16]) const {
+        for (int i = 0; i < 4; ++i)
+            for (int j = 0; j < 4; ++j) ctm[4 * i + j] = gs.ctm.m[i][j];
+    }
+    // The image of a projection / goniometric light, by the host Image layer (.pfm, .exr); the checks of lights.cpp:502-510 / :669-678
+    Image light_image(const std::string &what, std::string fn) {
+        if (fn[0] != '/' && !baseDir.empty()) fn = baseDir + "/" + fn;  // ResolveFilename
+        Image img = ReadImage(fn);
+        for (float v : img.data) {
+            if (std::isinf(v)) fail(fn + ": image has infinite pixel values and so is not suitable as a light.");
+            if (v != v) fail(fn + ": image has not-a-number pixel values and so is not suitable as a light.");
+        }
+        if (img.xres > VSPG_LIGHT_IMAGE_MAX_RES || img.yres > VSPG_LIGHT_IMAGE_MAX_RES)
+            fail(fn + ": " + what + " images above " + std::to_string(VSPG_LIGHT_IMAGE_MAX_RES) + " texels a side are outside this build's scope");
+        return img;
+    }
+    // LightSource "projection" (ProjectionLight::Create, lights.cpp:490-560): scale, fov, filename under the current CTM, flipped in y by the
+    // library (vspg_projection_light_at).  The record's I is the scale as an RGB multiplier of the texels (SpectrumToPhotometric is 1
+    // under PBRT_RGB_RENDERING).  "power" is refused: its normalisation weighs the texels with the colour space's LuminanceVector, which
+    // the reference computes at run time and nothing here can pin.
+    void projection_light(ParameterDictionary &p) {
+        if (sd->scene.n_point_lights >= VSPG_MAX_POINT_LIGHTS) fail("too many point lights");
+        const int slot = sd->scene.n_point_lights;
+        VspgPointLight &pl = sd->scene.point_lights[slot];
+        std::memset(&pl, 0, sizeof pl);
+        pl.type = VSPG_LIGHT_PROJECTION;
+        const float sc = p.GetOneFloat("scale", 1.f);
+        if (p.Has("power")) fail("LightSource \"projection\": \"power\" is outside this build's scope (its normalisation needs the colour space's luminance vector; give \"scale\")");
+        const float fov = p.GetOneFloat("fov", 90.f);
+        const std::string fn = p.GetOneString("filename", "");
+        p.ReportUnused();
+        if (fn.empty()) fail("Must provide \"filename\" to \"projection\" light source");  // lights.cpp:498-499
+        if (!(fov > 0 && fov < 180)) fail("LightSource \"projection\": \"fov\" must lie in (0, 180)");
+        const Image img = light_image("projection", fn);
+        for (const char *c : {"R", "G", "B"})
+            if (img.ChannelIndex(c) < 0) fail("Image provided to \"projection\" light must have R, G, and B channels.");  // :514-517
+        SceneDescription::LightImage li;
+        li.slot = slot; li.xres = img.xres; li.yres = img.yres; li.channels = 3;
+        li.pixels = img.Gather({"R", "G", "B"}, fn);
+        sd->lightImages.push_back(std::move(li));
+        for (int k = 0; k < 3; ++k) pl.I[k] = sc;
+        float ctm[16];
+        ctm16(ctm);
+        if (vspg_projection_light_at(&pl, ctm) != 0) fail(std::string("LightSource \"projection\": ") + vspg_last_error());
+        pl.cone_angle_deg = fov;  // a projection slot's field of view (include/vspg.h)
+        sd->scene.n_point_lights++;
+    }
+    // LightSource "goniometric" (GoniometricLight::Create, lights.cpp:652-734): I, scale, power, filename under the current CTM with y and z
+    // swapped by the library (vspg_goniometric_light_at).  An RGB image is averaged to Y, a Y image is taken as it is (:687-709); without a
+    // file name the reference warns and goes on with an empty image, here with the 1 x 1 image of ones the renderer is created with.
+    void goniometric_light(ParameterDictionary &p) {
+        if (sd->scene.n_point_lights >= VSPG_MAX_POINT_LIGHTS) fail("too many point lights");
+        const int slot = sd->scene.n_point_lights;
+        VspgPointLight &pl = sd->scene.point_lights[slot];
+        std::memset(&pl, 0, sizeof pl);
+        pl.type = VSPG_LIGHT_GONIOMETRIC;
+        float I[3] = {1, 1, 1};
+        p.GetOneRGB("I", I);
+        float sc = p.GetOneFloat("scale", 1.f);
+        const float phi_v = p.GetOneFloat("power", -1.f);
+        const std::string fn = p.GetOneString("filename", "");
+        p.ReportUnused();
+        SceneDescription::LightImage li;
+        li.slot = slot; li.xres = li.yres = 1; li.channels = 1;
+        li.pixels.assign(1, 1.f);
+        if (fn.empty()) {
+            sd->warnings.push_back("No \"filename\" parameter provided for goniometric light: a 1 x 1 image of ones (a point light)");
+        } else {
+            const Image img = light_image("goniometric", fn);
+            if (img.xres != img.yres)  // lights.cpp:680-685
+                fail(fn + ": image resolution (" + std::to_string(img.xres) + ", " + std::to_string(img.yres) +
+                     ") is non-square. It's unlikely this is an equal-area environment map.");
+            const bool rgb = img.ChannelIndex("R") >= 0 && img.ChannelIndex("G") >= 0 && img.ChannelIndex("B") >= 0, y = img.ChannelIndex("Y") >= 0;
+            if (rgb && y) fail(fn + ": has both \"R\", \"G\", and \"B\" or \"Y\" channels.");
+            if (!rgb && !y) fail(fn + ": has neither \"R\", \"G\", and \"B\" or \"Y\" channels.");
+            li.xres = li.yres = img.xres;
+            if (y) {
+                li.pixels = img.Gather({"Y"}, fn);
+            } else {
+                const std::vector<float> c = img.Gather({"R", "G", "B"}, fn);
+                li.pixels.resize(c.size() / 3);
+                for (size_t i = 0; i < li.pixels.size(); ++i) {  // ImageChannelValues::Average (util/image.h:205-210)
+                    float sum = 0;
+                    for (int k = 0; k < 3; ++k) sum += c[3 * i + k];
+                    li.pixels[i] = sum / 3;
+                }
+            }
+            sd->lightImages.push_back(li);
+        }
+        if (phi_v > 0) {  // lights.cpp:714-722
+            float sumY = 0;
+            for (float v : li.pixels) sumY += v;
+            const float k_e = 4 * 3.14159265358979323846f * sumY / (float)(li.xres * li.yres);
+            sc *= phi_v / k_e;
+        }
+        for (int k = 0; k < 3; ++k) pl.I[k] = I[k] * sc;
+        float ctm[16];
+        ctm16(ctm);
+        if (vspg_goniometric_light_at(&pl, ctm) != 0) fail(std::string("LightSource \"goniometric\": ") + vspg_last_error());
+        sd->scene.n_point_lights++;
+    }
     void light_source(const std::string &type, ParameterDictionary &p) {
         if (type == "point") { point_light(p); return; }
+        if (type == "projection") { projection_light(p); return; }
+        if (type == "goniometric") { goniometric_light(p); return; }
         // (The library, its binding and vspg_spot_light_look_at carry everything a "spot" needs; the reader does not accept it yet.)
         if (type == "spot")
             fail("LightSource \"spot\": not read from scene files yet -- build the scene through the C-ABI (VspgScene.point_lights, vspg_spot_light_look_at)");
@@ -419,7 +522,7 @@ class Parser {
             for (int k = 0; k < 3; ++k) il.w_light[k] = wr[k] / l;
             il.type = VSPG_LIGHT_DISTANT;
         } else {
-            fail("LightSource \"" + type + "\": only \"infinite\", \"distant\" and \"point\" are inside this build's scope");
+            fail("LightSource \"" + type + "\": only \"infinite\", \"distant\", \"point\", \"projection\" and \"goniometric\" are inside this build's scope");
         }
         p.ReportUnused();
         for (int k = 0; k < 3; ++k) il.L[k] = L[k] * sc;
@@ -608,6 +711,7 @@ std::unique_ptr<Integrator> CreateIntegrator(const SceneDescription &sd, int dev
     auto integrator = Integrator::Create(sd.integratorName, sd.integratorParams, sd.scene, sd.xres, sd.yres, sd.pixelSamples, sd.seed, device);
     integrator->SetPixelBounds(b[0], b[1], b[2], b[3]);
     for (const SceneDescription::EnvImage &e : sd.envImages) integrator->SetEnvironmentImage(e.light, e.rgb, e.res, e.renderFromLight);
+    for (const SceneDescription::LightImage &l : sd.lightImages) integrator->SetLightImage(l.slot, l.pixels, l.xres, l.yres, l.channels);
     return integrator;
 }
 

@@ -14,7 +14,9 @@
 // (L, scale; or "filename": an equal-area octahedral environment map, .exr / .pfm, square, with R, G, B -- the CTM in effect is the
 // light's transform; no "portal", no "illuminance") / "distant" (L, scale, from, to) / "point" (I, scale, power, from under the CTM: a
 // VspgPointLight filled by vspg_point_light_at; LightSource "spot" is still REFUSED by name here -- the library, its binding and
-// vspg_spot_light_look_at carry everything it needs, the reader's few lines are a follow-up), MakeNamedMedium ("homogeneous", "uniformgrid", "rgbgrid", "nanovdb"), MediumInterface,
+// vspg_spot_light_look_at carry everything it needs, the reader's few lines are a follow-up) / "projection" (scale, fov, filename: a slide
+// with R, G, B, .exr / .pfm; "power" is refused by name) / "goniometric" (I, scale, power, filename: a square equal-area map, Y or R, G, B
+// averaged; no filename = a warning and a point light), both placed by the CTM with the reference's flip / swap, MakeNamedMedium ("homogeneous", "uniformgrid", "rgbgrid", "nanovdb"), MediumInterface,
 // Include (as a directive, and -- beyond pbrt -- inside a parameter list, for the block the reference's nanovdb2pbrt prints),
 // Shape "bilinearmesh" (one patch: a parallelogram becomes a rectangle, anything else two triangles) / "trianglemesh"
 // (P, indices) / "sphere" (radius; full spheres).  Anything else is an Error naming the directive: nothing is silently dropped.
@@ -48,6 +50,13 @@ struct SceneDescription {
         float renderFromLight[12] = {1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1, 0};
     };
     std::vector<EnvImage> envImages;
+    // LightSource "projection" / "goniometric" "string filename": the image of point-light slot `slot` (R, G, B interleaved or Y alone, top
+    // row first), handed to the renderer the same way (Integrator::SetLightImage -> vspg_renderer_set_light_image)
+    struct LightImage {
+        int slot = 0, xres = 0, yres = 0, channels = 0;
+        std::vector<float> pixels;
+    };
+    std::vector<LightImage> lightImages;
     std::string integratorName = "volpath";
     ParameterDictionary integratorParams;
     int xres = 1280, yres = 720;         // Film defaults (film.cpp)
