@@ -858,10 +858,53 @@ int vspg_renderer_set_light_image(VspgRenderer *r, int point_light_index, const 
  * VSPG_ENVLIGHT_OUT floats per element (HOST arrays):
  *   [0..2] Le(dirs[i])   [3..4] the (u, v) that Le looked up   [5] PDF_Li(dirs[i])
  *   SampleLi(ctx.p = 0, u[i]):  [6] 1 = a sample, 0 = none (everything after it is 0 then)   [7..8] its (u, v)   [9..11] wi
- *   [12] pdf   [13..15] L */
+ *   [12] pdf   [13..15] L
+ * VSPG_EINVAL for a slot that vspg_renderer_set_portal_environment_image turned into a portal light (vspg_portallight_batch serves it). */
 #define VSPG_ENVLIGHT_OUT 16
 int vspg_envlight_batch(VspgRenderer *r, int infinite_light_index, int n, const float *dirs /*3n*/, const float *u /*2n*/,
                         float *out /*16n*/, void *stream);
+
+/* Turns an image infinite light (slot `infinite_light_index`, type VSPG_LIGHT_IMAGE_INFINITE) into a PortalImageInfiniteLight
+ * (src/pbrt/lights.h:699-808, lights.cpp:1181-1345): the same equal-area map, seen through a rectangular opening.  NEE samples only the
+ * part of the map the context point sees through the portal, and an escaped ray receives radiance only where its direction, seen
+ * from its ORIGIN, passes through the portal.  Arguments as vspg_renderer_set_environment_image, plus
+ *   portal   12 floats: the four vertices of the opening in render space, in order round the rectangle
+ * The host builds, in the reference's order of operations: portalFrame = Frame::FromXY(p03, p01); the rectified res x res image
+ * (RenderFromImage at texel centres, the inverse rotation, EqualAreaSphereToSquare, Image::BilerpChannel under the octahedral wrap);
+ * d = average(R, G, B) * duv_dw(centre); the summed-area table in double, stored as float (SummedAreaTable::LookupInt returns Float);
+ * Area() and Phi's sums.  This is sequential host work (see DESIGN.md 4.13 for its cost at 1024^2 and 4096^2).  tan and atan2 are the
+ * library's own functions (csrc/vspg_trig.h), so parity with a reference build is "the same texel except within their error bound of
+ * a texel edge" -- the reference's own result depends on its platform's libm.
+ * The call keeps what vspg_renderer_set_environment_image keeps: it finishes parked samples and suspended paths on `stream`,
+ * synchronises, rebuilds the light sampler's tables with the portal light's Phi (lights.cpp:1262-1285); film, VSP buffer, guiding
+ * fields, counters and the error log persist.  The light stays LightType::Infinite with no Bounds(): under "bvh" it sits among the
+ * infinite lights as the image light does.  A later vspg_renderer_set_environment_image on the slot turns it back into a plain
+ * image light, after which the renderer computes what one that never had a portal computes.
+ * VSPG_EINVAL, with the renderer exactly as it was and before any allocation: every refusal of vspg_renderer_set_environment_image; a
+ * null `portal` or a vertex that is NaN or infinite; an edge of zero length; a quadrilateral that fails the constructor's tests
+ * (lights.cpp:1222-1228: opposite edges parallel, sides perpendicular, thresholds .001 compared in double).  The reference only prints
+ * "Infinite light portal isn't a planar quadrilateral" there and renders on with a broken frame; the library refuses.
+ * Scene files still refuse a "portal" parameter by name: the light is reached through this call (and the Python binding) only. */
+int vspg_renderer_set_portal_environment_image(VspgRenderer *r, int infinite_light_index, const float *host_rgb, int res,
+                                               const float *render_from_light /*12 or NULL*/,
+                                               const float *portal /*12: four points, render space*/, void *stream);
+/* Batch driver of the portal light (parity tests), as the path kernels evaluate it; the slot must hold a portal light.  ctx_p: 3n
+ * floats (the context point / ray origin), dirs: 3n floats, u: 2n floats, out: VSPG_PORTALLIGHT_OUT floats per element (HOST arrays):
+ *   ImageBounds(ctx_p):  [0] 1 = bounds, 0 = none   [1..4] pMin.x, pMin.y, pMax.x, pMax.y
+ *   Le(ray(ctx_p, dirs)):  [5] 1 = the direction lies inside the bounds   [6..7] the direction's (u, v) where it has one   [8..10] Le
+ *   [11] PDF_Li(ctx_p, dirs)
+ *   SampleLi(ctx_p, u):  [12] 1 = a sample, 0 = none ([13..23] and [27..29] are 0 then)   [13..14] its (u, v)   [15] mapPDF
+ *   [16] duv_dw   [17..19] wi   [20] pdf   [21..23] L   [27..29] pLight
+ *   [24] [25] the trip counts of the x and y bisections   [26] why no sample: 0 a sample, 1 no bounds, 2 zero window integral,
+ *   3 zero conditional integral, 4 a non-finite interpolation parameter, 5 duv_dw == 0   [30] [31] 0 */
+#define VSPG_PORTALLIGHT_OUT 32
+int vspg_portallight_batch(VspgRenderer *r, int infinite_light_index, int n, const float *ctx_p /*3n*/, const float *dirs /*3n*/,
+                           const float *u /*2n*/, float *out /*32n*/, void *stream);
+/* Reads a portal light's tables back as the renderer holds them (each pointer may be NULL): *res_out, the rectified image
+ * (res*res*3), func (res*res), the float summed-area table (res*res), and record20 = {portal[0], portal[2], frame x, y, z (3 each),
+ * Area(), Phi's three sums, the scene's radius (the sceneRadius of pLight = ctx.p + 2 * sceneRadius * wi)}. */
+int vspg_portallight_read(VspgRenderer *r, int infinite_light_index, int *res_out, float *image, float *func, float *table,
+                          float *record20 /*20*/, void *stream);
 
 /* Batch driver of light sampling (parity tests): per element the renderer's light sampler picks a light for the context and that
  * light is sampled -- the light_sampler_sample, light_sampler_pmf and sample_light the path kernels call, under the sampler the

@@ -73,6 +73,7 @@ VSPG_MAX_INFINITE_LIGHTS = 4
 LIGHT_UNIFORM_INFINITE, LIGHT_DISTANT, LIGHT_IMAGE_INFINITE = 0, 1, 2
 ENV_MAX_RES = 4096   # VSPG_ENV_MAX_RES
 ENVLIGHT_OUT = 16    # VSPG_ENVLIGHT_OUT: floats per element of vspg_envlight_batch
+PORTALLIGHT_OUT = 32  # VSPG_PORTALLIGHT_OUT: floats per element of vspg_portallight_batch
 
 
 class VspgInfiniteLight(C.Structure):
@@ -315,6 +316,9 @@ SYMBOLS = [
     ("vspg_blackbody_batch", C.c_int, [_vp, C.c_int, _P(C.c_float), _P(C.c_float), _P(C.c_float), _vp]),
     ("vspg_renderer_set_environment_image", C.c_int, [_vp, C.c_int, _P(C.c_float), C.c_int, _P(C.c_float), _vp]),
     ("vspg_envlight_batch", C.c_int, [_vp, C.c_int, C.c_int, _P(C.c_float), _P(C.c_float), _P(C.c_float), _vp]),
+    ("vspg_renderer_set_portal_environment_image", C.c_int, [_vp, C.c_int, _P(C.c_float), C.c_int, _P(C.c_float), _P(C.c_float), _vp]),
+    ("vspg_portallight_batch", C.c_int, [_vp, C.c_int, C.c_int, _P(C.c_float), _P(C.c_float), _P(C.c_float), _P(C.c_float), _vp]),
+    ("vspg_portallight_read", C.c_int, [_vp, C.c_int, _P(C.c_int), _P(C.c_float), _P(C.c_float), _P(C.c_float), _P(C.c_float), _vp]),
     ("vspg_spot_light_look_at", C.c_int, [_P(VspgPointLight), f3, f3, _P(C.c_float)]),
     ("vspg_point_light_at", C.c_int, [_P(VspgPointLight), f3, _P(C.c_float)]),
     ("vspg_projection_light_at", C.c_int, [_P(VspgPointLight), _P(C.c_float)]),
@@ -734,6 +738,22 @@ def environment_image_source(image, render_from_light=None):
     return image, int(image.shape[0]), m
 
 
+def portal_source(portal):
+    """What vspg_renderer_set_portal_environment_image is handed for `portal`: a C-contiguous float32 array of the four vertices,
+    [4, 3] (or 12 numbers), in render space.  Anything else raises ValueError -- here, before the library is called; the library
+    judges the quadrilateral itself."""
+    import numpy as np
+    if portal is None:
+        raise ValueError("portal must be four points (a [4, 3] array), not None")
+    try:
+        q = np.ascontiguousarray(portal, dtype=np.float32)
+    except (TypeError, ValueError):
+        raise ValueError("portal must be four points (a [4, 3] array of numbers)")
+    if q.size != 12:
+        raise ValueError("portal must be four points (a [4, 3] array), not %s" % (tuple(q.shape),))
+    return q.reshape(4, 3)
+
+
 def grid_update_source(n_voxels, values, device):
     """What vspg_renderer_update_grid is handed for `values`: (address, memory kind, stream or None).  A NumPy array is a host source
     (float32, n_voxels elements, C-contiguous); a torch tensor is a device source (float32, n_voxels elements, contiguous, on
@@ -971,6 +991,49 @@ class Renderer:
         fp = _P(C.c_float)
         _check(self.lib, self.lib.vspg_renderer_set_environment_image(self.h, int(index), img.ctypes.data_as(fp), res,
                                                                      m.ctypes.data_as(fp) if m is not None else None, _vp(stream or 0)))
+
+    def set_portal_environment_image(self, index, image, portal, render_from_light=None, stream=None):
+        """Turn image infinite light `index` into a portal image infinite light (vspg_renderer_set_portal_environment_image): the
+        image and matrix as set_environment_image takes them, portal: the opening's four vertices in render space, [4, 3].  The
+        library refuses a quadrilateral that is no rectangle.  set_environment_image on the slot makes it a plain image light again.
+        Film, statistics, VSP buffer, guiding fields and counters stay."""
+        img, res, m = environment_image_source(image, render_from_light)
+        q = portal_source(portal)
+        fp = _P(C.c_float)
+        _check(self.lib, self.lib.vspg_renderer_set_portal_environment_image(self.h, int(index), img.ctypes.data_as(fp), res,
+                                                                            m.ctypes.data_as(fp) if m is not None else None,
+                                                                            q.ctypes.data_as(fp), _vp(stream or 0)))
+
+    def portallight_batch(self, index, ctx_p, dirs, u):
+        """[n, 32] float32 per (context point, direction, variate pair) of portal light `index`, as the path kernels evaluate it
+        (vspg_portallight_batch): bounds valid, bounds (4) | inside, uv (2), Le (3) | PDF_Li | sample valid, uv (2), mapPDF, duv_dw,
+        wi (3), pdf, L (3) | trips x, trips y, why | pLight (3) | 0, 0."""
+        import numpy as np
+        p = np.ascontiguousarray(ctx_p, dtype=np.float32).reshape(-1, 3)
+        d = np.ascontiguousarray(dirs, dtype=np.float32).reshape(-1, 3)
+        uu = np.ascontiguousarray(u, dtype=np.float32).reshape(-1, 2)
+        if not p.shape[0] == d.shape[0] == uu.shape[0]:
+            raise ValueError("portallight_batch: %d points, %d directions, %d variate pairs" % (p.shape[0], d.shape[0], uu.shape[0]))
+        out = np.empty((p.shape[0], PORTALLIGHT_OUT), dtype=np.float32)
+        fp = _P(C.c_float)
+        _check(self.lib, self.lib.vspg_portallight_batch(self.h, int(index), p.shape[0], p.ctypes.data_as(fp), d.ctypes.data_as(fp),
+                                                        uu.ctypes.data_as(fp), out.ctypes.data_as(fp), _vp(0)))
+        return out
+
+    def portallight_tables(self, index):
+        """The tables of portal light `index` as the renderer holds them (vspg_portallight_read): a dict with res, image [res, res, 3],
+        func [res, res], table [res, res] (the float summed-area table), p0, p2, frame [3, 3] (rows x, y, z), area, sum_phi (3), scene_radius."""
+        import numpy as np
+        res = C.c_int(0)
+        rec = np.zeros(20, dtype=np.float32)
+        fp = _P(C.c_float)
+        _check(self.lib, self.lib.vspg_portallight_read(self.h, int(index), C.byref(res), None, None, None, rec.ctypes.data_as(fp), _vp(0)))
+        n = res.value
+        image, func, table = np.empty((n, n, 3), np.float32), np.empty((n, n), np.float32), np.empty((n, n), np.float32)
+        _check(self.lib, self.lib.vspg_portallight_read(self.h, int(index), C.byref(res), image.ctypes.data_as(fp), func.ctypes.data_as(fp),
+                                                       table.ctypes.data_as(fp), None, _vp(0)))
+        return {"res": n, "image": image, "func": func, "table": table, "p0": rec[0:3].copy(), "p2": rec[3:6].copy(),
+                "frame": rec[6:15].reshape(3, 3).copy(), "area": rec[15], "sum_phi": rec[16:19].copy(), "scene_radius": rec[19]}
 
     def set_light_image(self, index, image, stream=None):
         """Give the projection or goniometric light in point-light slot `index` its image (vspg_renderer_set_light_image): a float32

@@ -2218,6 +2218,7 @@ int vspg_renderer_set_environment_image(VspgRenderer *r, int infinite_light_inde
     HIPCHK(hipStreamSynchronize(s));  // no launch may still read the old tables
     float *old = nullptr;
     if (const int rc = env_install(r, k, T, m, mi, s, &old)) return rc;
+    r->hscene.portal[k] = DPortalLight{};  // a portal light becomes a plain image light again (its arrays lived in the old buffer)
     lsb::build(r->scene, r->prm, &r->hscene);  // the power sampler's alias table: the light's Phi changed
     // the light sampler and the environment slots are the tail of the record; the rest of the device's copy (the guiding fields a
     // training renderer updates in place) is not touched
@@ -2226,6 +2227,96 @@ int vspg_renderer_set_environment_image(VspgRenderer *r, int infinite_light_inde
                           hipMemcpyHostToDevice, s));
     HIPCHK(hipStreamSynchronize(s));
     if (old) (void)hipFree(old);
+    return 0;
+}
+
+int vspg_renderer_set_portal_environment_image(VspgRenderer *r, int infinite_light_index, const float *host_rgb, int res,
+                                               const float *render_from_light, const float *portal, void *stream) {
+    // every refusal comes before anything of the renderer changes and before any allocation
+    if (!r || !host_rgb || !portal) return fail(VSPG_EINVAL, "null argument");
+    const int k = infinite_light_index;
+    if (k < 0 || k >= r->hscene.n_inf) return fail(VSPG_EINVAL, "infinite_light_index names no infinite light of the scene");
+    if (r->hscene.inf_type[k] != VSPG_LIGHT_IMAGE_INFINITE) return fail(VSPG_EINVAL, "the infinite light is not of type VSPG_LIGHT_IMAGE_INFINITE");
+    if (res < 1 || res > VSPG_ENV_MAX_RES) return fail(VSPG_EINVAL, "environment image resolution outside 1 .. VSPG_ENV_MAX_RES (4096)");
+    const size_t n3 = (size_t)res * res * 3;
+    for (size_t i = 0; i < n3; ++i) {
+        if (host_rgb[i] != host_rgb[i]) return fail(VSPG_EINVAL, "environment image has not-a-number pixel values and so is not suitable as a light");
+        if (std::isinf(host_rgb[i])) return fail(VSPG_EINVAL, "environment image has infinite pixel values and so is not suitable as a light");
+    }
+    float m[9], mi[9];
+    if (!env_matrices(render_from_light, m, mi)) return fail(VSPG_EINVAL, "render_from_light is singular or not finite");
+    if (const int rc = portal_refusal(portal)) return rc;
+    PortalTables T;
+    portal_build_tables(host_rgb, res, mi, portal, &T);
+    HIPCHK(hipSetDevice(r->cfg.device));
+    hipStream_t s = (hipStream_t)stream;
+    if (const int rc = flush_parked_samples(r, s)) return rc;  // (paths in flight end under the sky they started under)
+    HIPCHK(hipStreamSynchronize(s));  // no launch may still read the old tables
+    float *old = nullptr;
+    if (const int rc = env_install(r, k, T.env, m, mi, s, &old)) return rc;
+    DPortalLight &P = r->hscene.portal[k];
+    P = T.rec;
+    P.image = r->env_buf[k] + T.o_image;
+    P.func = r->env_buf[k] + T.o_func;
+    P.sat = r->env_buf[k] + T.o_sat;
+    lsb::build(r->scene, r->prm, &r->hscene);  // the power sampler's alias table: the light's Phi changed
+    const size_t tail = offsetof(DScene, lsamp);  // (as in vspg_renderer_set_environment_image)
+    HIPCHK(hipMemcpyAsync(reinterpret_cast<char *>(r->dscene) + tail, reinterpret_cast<const char *>(&r->hscene) + tail, sizeof(DScene) - tail,
+                          hipMemcpyHostToDevice, s));
+    HIPCHK(hipStreamSynchronize(s));
+    if (old) (void)hipFree(old);
+    return 0;
+}
+
+int vspg_portallight_batch(VspgRenderer *r, int infinite_light_index, int n, const float *ctx_p, const float *dirs, const float *u, float *out,
+                           void *stream) {
+    if (!r || n < 0 || (n > 0 && (!ctx_p || !dirs || !u || !out))) return fail(VSPG_EINVAL, "null argument");
+    const int k = infinite_light_index;
+    if (k < 0 || k >= r->hscene.n_inf || r->hscene.inf_type[k] != VSPG_LIGHT_IMAGE_INFINITE || r->hscene.portal[k].res <= 0)
+        return fail(VSPG_EINVAL, "infinite_light_index names no portal image infinite light of the scene");
+    if (n == 0) return 0;
+    HIPCHK(hipSetDevice(r->cfg.device));
+    hipStream_t s = (hipStream_t)stream;
+    DevBuf dp, dd, du, dout;
+    HIPCHK(hipMalloc(&dp.p, (size_t)n * 12));
+    HIPCHK(hipMalloc(&dd.p, (size_t)n * 12));
+    HIPCHK(hipMalloc(&du.p, (size_t)n * 8));
+    HIPCHK(hipMalloc(&dout.p, (size_t)n * VSPG_PORTALLIGHT_OUT * 4));
+    HIPCHK(hipMemcpyAsync(dp.p, ctx_p, (size_t)n * 12, hipMemcpyHostToDevice, s));
+    HIPCHK(hipMemcpyAsync(dd.p, dirs, (size_t)n * 12, hipMemcpyHostToDevice, s));
+    HIPCHK(hipMemcpyAsync(du.p, u, (size_t)n * 8, hipMemcpyHostToDevice, s));
+    hipLaunchKernelGGL(k_portallight, dim3((n + kBlock - 1) / kBlock), dim3(kBlock), 0, s, r->dscene, k, n, (const float *)dp.p, (const float *)dd.p,
+                       (const float *)du.p, (float *)dout.p);
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipMemcpyAsync(out, dout.p, (size_t)n * VSPG_PORTALLIGHT_OUT * 4, hipMemcpyDeviceToHost, s));
+    HIPCHK(hipStreamSynchronize(s));
+    return 0;
+}
+
+int vspg_portallight_read(VspgRenderer *r, int infinite_light_index, int *res_out, float *image, float *func, float *table, float *record20,
+                          void *stream) {
+    if (!r || !res_out) return fail(VSPG_EINVAL, "null argument");
+    const int k = infinite_light_index;
+    if (k < 0 || k >= r->hscene.n_inf || r->hscene.inf_type[k] != VSPG_LIGHT_IMAGE_INFINITE || r->hscene.portal[k].res <= 0)
+        return fail(VSPG_EINVAL, "infinite_light_index names no portal image infinite light of the scene");
+    const DPortalLight &P = r->hscene.portal[k];
+    *res_out = P.res;
+    if (record20) {
+        for (int c = 0; c < 3; ++c) {
+            record20[c] = P.p0[c]; record20[3 + c] = P.p2[c]; record20[6 + c] = P.fx[c]; record20[9 + c] = P.fy[c]; record20[12 + c] = P.fz[c];
+            record20[16 + c] = P.sum_phi[c];
+        }
+        record20[15] = P.area;
+        record20[19] = r->hscene.scene_radius;
+    }
+    if (!image && !func && !table) return 0;
+    HIPCHK(hipSetDevice(r->cfg.device));
+    hipStream_t s = (hipStream_t)stream;
+    const size_t n = (size_t)P.res * P.res;
+    if (image) HIPCHK(hipMemcpyAsync(image, P.image, n * 12, hipMemcpyDeviceToHost, s));
+    if (func) HIPCHK(hipMemcpyAsync(func, P.func, n * 4, hipMemcpyDeviceToHost, s));
+    if (table) HIPCHK(hipMemcpyAsync(table, P.sat, n * 4, hipMemcpyDeviceToHost, s));
+    HIPCHK(hipStreamSynchronize(s));
     return 0;
 }
 
@@ -2259,6 +2350,8 @@ int vspg_envlight_batch(VspgRenderer *r, int infinite_light_index, int n, const 
     const int k = infinite_light_index;
     if (k < 0 || k >= r->hscene.n_inf || r->hscene.inf_type[k] != VSPG_LIGHT_IMAGE_INFINITE)
         return fail(VSPG_EINVAL, "infinite_light_index names no image infinite light of the scene");
+    if (r->hscene.portal[k].res > 0)  // (the slot's DEnvLight then holds the 1 x 1 white image only: nothing the path kernels evaluate)
+        return fail(VSPG_EINVAL, "the infinite light is a portal light: vspg_portallight_batch serves it");
     if (n == 0) return 0;
     HIPCHK(hipSetDevice(r->cfg.device));
     hipStream_t s = (hipStream_t)stream;

@@ -16,6 +16,9 @@
 #include "vspg_libm.h"
 
 #define VDEV __device__ __forceinline__
+// ... and code the host-side builders share with the kernels (pure arithmetic only: vspg_envmap.h, vspg_portalmap.h).  The helpers
+// below stay device functions; vspg_envmap.h gives the few such code needs __host__ twins (overloads on the target attribute).
+#define VHD __host__ __device__ __forceinline__
 #ifdef VSPG_WF_DEBUG  // diagnostic build only: out-of-range accesses are clamped and flagged instead of faulting
 __device__ unsigned int g_dbg_err[8];
 #define VSPG_DBG_CHECK(cond, bit) do { if (!(cond)) atomicOr(&g_dbg_err[0], 1u << (bit)); } while (0)
@@ -103,6 +106,9 @@ constexpr float kInf = __builtin_huge_valf();
 struct V3 {
     float x, y, z;
 };
+// NOTE: ld3, the operators + - *, sqr, dot, len2, len, normalize, diff_of_products, cross, fmax_, fmin_, safe_sqrt and clampf below
+// have __host__ twins in vspg_envmap.h (the host builders share code with the kernels through them; these originals keep their
+// spelling because tests cut them out of this file by it).  An edit to one copy must reach the other.
 VDEV V3 mk(float x, float y, float z) { return V3{x, y, z}; }
 VDEV V3 ld3(const float *p) { return V3{p[0], p[1], p[2]}; }
 VDEV V3 operator+(V3 a, V3 b) { return V3{a.x + b.x, a.y + b.y, a.z + b.z}; }
@@ -770,6 +776,20 @@ struct DEnvLight {
     const float *mfunc;    // res
     const float *mcdf;     // res + 1
 };
+// Portal image infinite light (vspg_portallight.h; built by vspg_renderer_set_portal_environment_image): the portal's two diagonal
+// vertices and frame, the rectified image and its WindowedPiecewiseConstant2D (util/sampling.h:894-983) -- the function and the
+// summed-area table, whose double sums the host rounds to float once each (SummedAreaTable::LookupInt returns Float: the same bits
+// for half the traffic).  res == 0: the slot is a plain image light.  The arrays share the slot's one allocation with its DEnvLight.
+struct DPortalLight {
+    int32_t res;
+    float p0[3], p2[3];            // portal[0], portal[2] (render space)
+    float fx[3], fy[3], fz[3];     // portalFrame = Frame::FromXY(p03, p01)
+    float area;                    // host only: Area()
+    float sum_phi[3];              // host only: per channel, ClampZero(texel) / duv_dw(texel centre) summed in image order
+    const float *image;            // res * res * 3, the rectified image
+    const float *func;             // res * res
+    const float *sat;              // res * res
+};
 // Point / spot light (vspg_pointlight.h): the position renderFromLight(0, 0, 0), I = scale * I multiplied out, rows 0..2 of mInv
 // (row-major, 3 x 4) and the SpotLight constructor's two cosines, all formed on the host.
 struct DPointLight {
@@ -908,6 +928,9 @@ struct DScene {
     // projection and goniometric lights: image_light[i] belongs to point[i] where that slot's type is one of the two.  Behind everything
     // else: only sample_light<FULL> reads here, and only for such a slot.
     DImageLight image_light[VSPG_MAX_POINT_LIGHTS];
+    // portal image infinite lights: portal[k].res > 0 turns infinite light k (type VSPG_LIGHT_IMAGE_INFINITE) into a
+    // PortalImageInfiniteLight (vspg_portallight.h).  Behind everything else: only FULL light code reads here.
+    DPortalLight portal[VSPG_MAX_INFINITE_LIGHTS];
 };
 // the length of the scene's light list (full-scene kernels): one line per light kind
 __host__ __device__ __forceinline__ int light_list_size(const DScene &S) { return S.n_lights + S.n_inf + S.n_point + S.n_sphere_lights; }

@@ -14,44 +14,7 @@
 // iteration of each other; each step is one dependent 4-byte load.
 #pragma once
 #include "vspg_device.h"
-
-// Transform::operator()(Vector3f) / ApplyInverse(Vector3f) (util/transform.h:206-211, 412-420): rows of m / mInv, no translation
-VDEV V3 env_xform(const float *m, V3 v) {
-    return V3{m[0] * v.x + m[1] * v.y + m[2] * v.z, m[3] * v.x + m[4] * v.y + m[5] * v.z, m[6] * v.x + m[7] * v.y + m[8] * v.z};
-}
-
-// EqualAreaSphereToSquare (util/math.cpp:317-361)
-VDEV void env_sphere_to_square(V3 d, float *pu, float *pv) {
-    const float x = __builtin_fabsf(d.x), y = __builtin_fabsf(d.y), z = __builtin_fabsf(d.z);
-    const float r = safe_sqrt(1 - z);
-    const float a = fmax_(x, y);
-    float b = fmin_(x, y);
-    b = a == 0 ? 0 : b / a;
-    // EvaluatePolynomial(b, t1..t7) (util/math.h:330-337): Horner by FMA, innermost coefficient first
-    const float t1 = 0.406758566246788489601959989e-5f, t2 = 0.636226545274016134946890922156f, t3 = 0.61572017898280213493197203466e-2f,
-                t4 = -0.247333733281268944196501420480f, t5 = 0.881770664775316294736387951347e-1f, t6 = 0.419038818029165735901852432784e-1f,
-                t7 = -0.251390972343483509333252996350e-1f;
-    float phi = __builtin_fmaf(b, t7, t6);
-    phi = __builtin_fmaf(b, phi, t5);
-    phi = __builtin_fmaf(b, phi, t4);
-    phi = __builtin_fmaf(b, phi, t3);
-    phi = __builtin_fmaf(b, phi, t2);
-    phi = __builtin_fmaf(b, phi, t1);
-    if (x < y) phi = 1 - phi;
-    float v = phi * r;
-    float u = r - v;
-    if (d.z < 0) {  // southern hemisphere -> mirror u, v
-        const float t = u;
-        u = v;
-        v = t;
-        u = 1 - u;
-        v = 1 - v;
-    }
-    u = __builtin_copysignf(u, d.x);
-    v = __builtin_copysignf(v, d.y);
-    *pu = 0.5f * (u + 1);
-    *pv = 0.5f * (v + 1);
-}
+// env_xform, env_sphere_to_square and env_remap_octahedral live in vspg_envmap.h (shared with the host builders; vspg_path.h includes it)
 
 // EqualAreaSquareToSphere (util/math.cpp:292-314)
 VDEV V3 env_square_to_sphere(float px, float py) {
@@ -75,21 +38,7 @@ VDEV Spec env_image_le(const DScene &S, int k, float u, float v) {
     const DEnvLight &E = S.env[k];
     const int res = E.res;
     int px = (int)(u * (float)res), py = (int)(v * (float)res);
-    if (px < 0) {
-        px = -px;
-        py = res - 1 - py;
-    } else if (px >= res) {
-        px = 2 * res - 1 - px;
-        py = res - 1 - py;
-    }
-    if (py < 0) {
-        px = res - 1 - px;
-        py = -py;
-    } else if (py >= res) {
-        px = res - 1 - px;
-        py = 2 * res - 1 - py;
-    }
-    if (res == 1) px = py = 0;  // "things don't go as expected for 1x1 images"
+    env_remap_octahedral(&px, &py, res);
     // (u, v) of a finite direction lie in [0, 1] and the remap lands inside the image; a NaN direction must not index outside it
     px = px < 0 ? 0 : (px > res - 1 ? res - 1 : px);
     py = py < 0 ? 0 : (py > res - 1 ? res - 1 : py);

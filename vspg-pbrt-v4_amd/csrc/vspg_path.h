@@ -7,6 +7,8 @@
 #include "vspg_guiding.h"
 #include "vspg_lightsampler.h"
 #include "vspg_train.h"
+#include "vspg_envmap.h"     // what vspg_envlight.h shares with the host builders (its own namespace block: included out here)
+#include "vspg_portalmap.h"  // ... and vspg_portallight.h
 
 VSPG_NS_BEGIN
 
@@ -89,6 +91,7 @@ struct LightLi {
 #include "vspg_envlight.h"  // the image infinite light: env_Le / env_sample_li / env_pdf_li (fills a LightLi)
 #include "vspg_pointlight.h"  // point and spot lights: point_sample_li / spot_sample_li (fill a LightLi)
 #include "vspg_imagelight.h"  // projection and goniometric lights: projection_sample_li / goniometric_sample_li (fill a LightLi)
+#include "vspg_portallight.h"  // the portal image infinite light: portal_Le / portal_sample_li / portal_pdf_li (fills a LightLi)
 VDEV bool light_sample_li(const DQuad &q, V3 ctxp, float u0, float u1, LightLi *ls) {
     V3 p00 = ld3(q.p00), p10 = ld3(q.p10), p01 = ld3(q.p01), p11 = ld3(q.p11);
     V3 pu0 = lerp(u1, p00, p01), pu1 = lerp(u1, p10, p11);
@@ -142,7 +145,8 @@ VDEV bool sample_light(const DScene &S, int lightIndex, V3 ctxp, const LsCtx &lc
         return P.type == VSPG_LIGHT_SPOT ? spot_sample_li(P, ctxp, ls) : point_sample_li(P, ctxp, ls);
     }
     if (S.inf_type[k] == VSPG_LIGHT_IMAGE_INFINITE) {  // ImageInfiniteLight::SampleLi (lights.h:650-674); `!ls->L || ls->pdf == 0` of :1167
-        if (!env_sample_li(S, k, ctxp, u0, u1, ls)) return false;
+        // ... or, behind a portal, PortalImageInfiniteLight::SampleLi (lights.cpp:1305-1329)
+        if (!(is_portal(S, k) ? portal_sample_li(S, k, ctxp, u0, u1, ls) : env_sample_li(S, k, ctxp, u0, u1, ls))) return false;
         return nonzero(ls->L) && ls->pdf != 0;
     }
     // UniformInfiniteLight::SampleLi returns {} for the incomplete PDF (lights.cpp:1019-1023): the sky is reached by escaping rays only
@@ -782,7 +786,9 @@ VDEV int li_surface_pre(const DScene &S, PathState &st, IsgSample &isg, PC &pc, 
         for (int k = 0; FULL && k < S.n_inf; ++k) {
             const bool image = S.inf_type[k] == VSPG_LIGHT_IMAGE_INFINITE;
             // UniformInfiniteLight::Le / DistantLight::Le (lights.cpp:1014-1017, lights.h:291-293) / ImageInfiniteLight::Le (lights.h:643-647)
-            Spec Le = image ? env_Le(S, k, st.rd) : lds(S.inf_L[k]);
+            // PortalImageInfiniteLight::Le (lights.cpp:1287-1294) reads the ray's origin too -- st.ro, also after an interface skip moved it
+            const bool portal = image && is_portal(S, k);
+            Spec Le = portal ? portal_Le(S, k, st.ro, st.rd) : image ? env_Le(S, k, st.rd) : lds(S.inf_L[k]);
             if (S.inf_type[k] == VSPG_LIGHT_DISTANT && st.depth != 0) Le = sp(0.f);
             if (st.depth == 0 || st.specularBounce) {
                 st.L = st.L + wdiv(st.beta * Le, avg(st.r_u));
@@ -792,7 +798,9 @@ VDEV int li_surface_pre(const DScene &S, PathState &st, IsgSample &isg, PC &pc, 
                 // incomplete PDF, the image light its compensated distribution's (lights.cpp:1113-1123)
                 const float pmf = S.lsamp.mode != VSPG_LIGHTSAMPLER_UNIFORM ? light_sampler_pmf(S, st.prevCtx.template expand<FULL>(S).pi.mid(), st.prevCtx.template expand<FULL>(S).n, S.n_lights + k)
                                                                             : wrcp((float)n_all);
-                const float lightPDF = pmf * (image ? env_pdf_li(S, k, st.rd) : 0.f);
+                // (PortalImageInfiniteLight::PDF_Li, lights.cpp:1331-1345, takes the previous context's point as well)
+                const float lightPDF = pmf * (portal ? portal_pdf_li(S, k, st.prevCtx.template expand<FULL>(S).pi.mid(), st.rd)
+                                                     : image ? env_pdf_li(S, k, st.rd) : 0.f);
                 st.r_l = st.r_l * lightPDF;
                 const float w_b = S.prm.usenee ? wrcp(avg(st.r_u + st.r_l)) : 1.f;
                 st.L = st.L + st.beta * w_b * Le;

@@ -178,6 +178,41 @@ __global__ __launch_bounds__(kBlock) void k_envlight(const DScene *__restrict__ 
     o[12] = ok ? ls.pdf : 0.f;
     o[13] = ok ? ls.L.r : 0.f; o[14] = ok ? ls.L.g : 0.f; o[15] = ok ? ls.L.b : 0.f;
 }
+// vspg_portallight_batch (include/vspg.h): ImageBounds, Le, PDF_Li and SampleLi of portal light k as the path kernels evaluate them
+__global__ __launch_bounds__(kBlock) void k_portallight(const DScene *__restrict__ Sp, int k, int n, const float *__restrict__ ctx_p,
+                                                        const float *__restrict__ dirs, const float *__restrict__ u, float *__restrict__ out) {
+    const int i = blockIdx.x * kBlock + threadIdx.x;
+    if (i >= n) return;
+    const DScene &S = *Sp;
+    float *o = out + (size_t)VSPG_PORTALLIGHT_OUT * i;
+    for (int j = 0; j < VSPG_PORTALLIGHT_OUT; ++j) o[j] = 0.f;
+    const V3 p = ld3(ctx_p + 3 * (size_t)i), d = ld3(dirs + 3 * (size_t)i);
+    float b[4];
+    if (portal_image_bounds(S.portal[k], p, b)) {
+        o[0] = 1.f;
+        for (int j = 0; j < 4; ++j) o[1 + j] = b[j];
+    }
+    float uv[2] = {0.f, 0.f}, rgb[3];
+    const bool inside = portal_radiance(S.portal[k], p, d, rgb, uv);
+    const Spec Le = portal_Le(S, k, p, d);
+    o[5] = inside ? 1.f : 0.f;
+    o[6] = uv[0]; o[7] = uv[1];
+    o[8] = Le.r; o[9] = Le.g; o[10] = Le.b;
+    o[11] = portal_pdf_li(S, k, p, d);
+    LightLi ls{};
+    PortalSample ps;
+    const bool ok = portal_sample_li(S, k, p, u[2 * (size_t)i], u[2 * (size_t)i + 1], &ls, &ps);
+    o[12] = ok ? 1.f : 0.f;
+    if (ok) {
+        o[13] = ps.u; o[14] = ps.v; o[15] = ps.mapPDF; o[16] = ps.duv_dw;
+        o[17] = ls.wi.x; o[18] = ls.wi.y; o[19] = ls.wi.z;
+        o[20] = ls.pdf;
+        o[21] = ls.L.r; o[22] = ls.L.g; o[23] = ls.L.b;
+        const V3 pl = ls.pLight.mid();
+        o[27] = pl.x; o[28] = pl.y; o[29] = pl.z;
+    }
+    o[24] = (float)ps.trips_x; o[25] = (float)ps.trips_y; o[26] = (float)ps.why;
+}
 // vspg_light_sample_batch (include/vspg.h): lightSampler.Sample, lightSampler.PMF and light.SampleLi as the path kernels call them
 __global__ __launch_bounds__(kBlock) void k_light_sample_batch(const DScene *__restrict__ Sp, int n, const float *__restrict__ ctx_p,
                                                                const float *__restrict__ ctx_n, const float *__restrict__ u, float *__restrict__ out) {

@@ -73,6 +73,20 @@ struct EnvTables {
 void env_build_tables(const float *rgb, int res, EnvTables *T);
 bool env_matrices(const float *m34, float *m, float *mi);
 
+// ---- portal image infinite light: the host side of vspg_portallight.h (PortalImageInfiniteLight's constructor, lights.cpp:1181-1260) --
+// The slot's one buffer: the DEnvLight arrays of the 1 x 1 white image (what the slot's plain image-light probes keep reading), then
+// rectified image | func | summed-area table.  `rec` holds everything of the DPortalLight but the three pointers.
+struct PortalTables {
+    EnvTables env;  // env.buf is the whole buffer
+    size_t o_image = 0, o_func = 0, o_sat = 0;
+    DPortalLight rec = {};
+};
+// The constructor's tests on the quadrilateral (lights.cpp:1218-1228, thresholds compared in double) and a finite, non-degenerate
+// outline; 0, or VSPG_EINVAL with the message set.  The reference prints an error and goes on with a broken frame: the library refuses.
+int portal_refusal(const float *portal12);
+// mi: the linear part of the inverse of render_from_light (env_matrices).  Sequential by construction (the table's running sums).
+void portal_build_tables(const float *rgb, int res, const float *mi, const float *portal12, PortalTables *T);
+
 // ---- projection and goniometric lights: the host side of vspg_imagelight.h ------------------------------------------------------
 // What one light's image becomes: the device image (projection: a float4 per texel, clamped at zero, pad 0; goniometric: the texels as
 // given) and the host-side fields of its DImageLight

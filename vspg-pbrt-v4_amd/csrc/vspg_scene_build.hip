@@ -9,7 +9,9 @@
 #include <cstring>
 #include <string>
 
+#include "vspg_envmap.h"
 #include "vspg_error.h"
+#include "vspg_portalmap.h"
 
 namespace vspg_host {
 
@@ -402,6 +404,10 @@ void build(const VspgScene &sc, const VspgIntegratorParams &prm, DScene *D) {
                     // ImageInfiniteLight::Phi (lights.cpp:1141) in its order: 4 * Pi * Pi * Sqr(sceneRadius) * scale * sumL / (width * height)
                     const DEnvLight &E = D->env[j];
                     for (int c = 0; c < 3; ++c) phi[c] = k * L[c] * E.sum_L[c] / (float)(E.res * E.res);
+                    // PortalImageInfiniteLight::Phi (lights.cpp:1284) in its order: scale * Area() * sumL / (width * height)
+                    const DPortalLight &Q = D->portal[j];
+                    if (Q.res > 0)
+                        for (int c = 0; c < 3; ++c) phi[c] = L[c] * Q.area * Q.sum_phi[c] / (float)(Q.res * Q.res);
                     have_phi = true;
                 }
             }
@@ -505,6 +511,91 @@ bool env_matrices(const float *m34, float *m, float *mi) {
         if (!std::isfinite(mi[k])) return false;
     }
     return true;
+}
+// ---- portal image infinite light: the host side of vspg_portallight.h (PortalTables: vspg_scene_build.h) ---------------------------
+int portal_refusal(const float *q) {
+    if (!q) return fail(VSPG_EINVAL, "null argument");
+    for (int i = 0; i < 12; ++i)
+        if (!std::isfinite(q[i])) return fail(VSPG_EINVAL, "a portal vertex is not finite");
+    const V3 p[4] = {ld3(q), ld3(q + 3), ld3(q + 6), ld3(q + 9)};
+    const V3 e[4] = {p[1] - p[0], p[2] - p[1], p[2] - p[3], p[3] - p[0]};
+    for (int i = 0; i < 4; ++i)
+        if (!(len2(e[i]) > 0) || !std::isfinite(len2(e[i]))) return fail(VSPG_EINVAL, "the portal has a degenerate edge");
+    // lights.cpp:1218-1228: float dot products of the normalised edges, the differences and .001 compared in double
+    const V3 p01 = normalize(e[0]), p12 = normalize(e[1]), p32 = normalize(e[2]), p03 = normalize(e[3]);
+    if (!(std::abs((double)(dot(p01, p32) - 1)) <= .001) || !(std::abs((double)(dot(p12, p03) - 1)) <= .001))
+        return fail(VSPG_EINVAL, "Infinite light portal isn't a planar quadrilateral (opposite edges are not parallel)");
+    if (!(std::abs((double)dot(p01, p12)) <= .001) || !(std::abs((double)dot(p12, p32)) <= .001) || !(std::abs((double)dot(p32, p03)) <= .001) ||
+        !(std::abs((double)dot(p03, p01)) <= .001))
+        return fail(VSPG_EINVAL, "Infinite light portal isn't a planar quadrilateral (sides are not perpendicular)");
+    return 0;
+}
+void portal_build_tables(const float *rgb, int res, const float *mi, const float *q, PortalTables *T) {
+    static const float white[3] = {1.f, 1.f, 1.f};
+    env_build_tables(white, 1, &T->env);
+    const size_t n = (size_t)res * res;
+    T->o_image = T->env.buf.size();
+    T->o_func = T->o_image + 3 * n;
+    T->o_sat = T->o_func + n;
+    T->env.buf.resize(T->o_sat + n, 0.f);
+    DPortalLight &P = T->rec;
+    P = DPortalLight{};
+    P.res = res;
+    const V3 p0 = ld3(q), p1 = ld3(q + 3), p2 = ld3(q + 6), p3 = ld3(q + 9);
+    const V3 fx = normalize(p3 - p0), fy = normalize(p1 - p0), fz = cross(fx, fy);  // Frame::FromXY(p03, p01)
+    for (int c = 0; c < 3; ++c) {
+        P.p0[c] = q[c];
+        P.p2[c] = q[6 + c];
+        P.fx[c] = (&fx.x)[c];
+        P.fy[c] = (&fy.x)[c];
+        P.fz[c] = (&fz.x)[c];
+    }
+    P.area = len(p1 - p0) * len(p3 - p0);  // Area() (lights.h:794-796)
+    float *image = T->env.buf.data() + T->o_image, *func = T->env.buf.data() + T->o_func, *sat = T->env.buf.data() + T->o_sat;
+    // the rectified image (lights.cpp:1232-1250): Image::BilerpChannel (util/image.h:279-292) of the equal-area image under the
+    // octahedral wrap; then d = Average(R, G, B) * duv_dw(centre) (Image::GetSamplingDistribution, util/image.h:450-469) and Phi's
+    // sums (lights.cpp:1262-1285), all in image order
+    float sum_phi[3] = {0.f, 0.f, 0.f};
+    for (int y = 0; y < res; ++y)
+        for (int x = 0; x < res; ++x) {
+            const float u = ((float)x + 0.5f) / (float)res, v = ((float)y + 0.5f) / (float)res;
+            float duv_dw;
+            V3 w = portal_render_from_image(P, u, v, &duv_dw);
+            w = normalize(env_xform(mi, w));
+            float ue, ve;
+            env_sphere_to_square(w, &ue, &ve);
+            const float fxp = ue * (float)res - 0.5f, fyp = ve * (float)res - 0.5f;
+            const int xi = (int)std::floor(fxp), yi = (int)std::floor(fyp);
+            const float dx = fxp - (float)xi, dy = fyp - (float)yi;
+            const float *t[4];
+            for (int j = 0; j < 4; ++j) {
+                int px = xi + (j & 1), py = yi + (j >> 1);
+                env_remap_octahedral(&px, &py, res);
+                px = px < 0 ? 0 : (px > res - 1 ? res - 1 : px);  // (a finite direction lands inside the image)
+                py = py < 0 ? 0 : (py > res - 1 ? res - 1 : py);
+                t[j] = rgb + 3 * ((size_t)py * res + px);
+            }
+            float *o = image + 3 * ((size_t)y * res + x);
+            float sum = 0.f;
+            for (int c = 0; c < 3; ++c) {
+                o[c] = (1 - dx) * (1 - dy) * t[0][c] + dx * (1 - dy) * t[1][c] + (1 - dx) * dy * t[2][c] + dx * dy * t[3][c];
+                sum += o[c];
+                sum_phi[c] += (o[c] > 0.f ? o[c] : 0.f) / duv_dw;
+            }
+            func[(size_t)y * res + x] = sum / 3 * duv_dw;
+        }
+    for (int c = 0; c < 3; ++c) P.sum_phi[c] = sum_phi[c];
+    // SummedAreaTable (util/sampling.h:834-848): double sums in its order, each rounded to float once at the end
+    std::vector<double> s(n);
+    s[0] = func[0];
+    for (int x = 1; x < res; ++x) s[x] = (double)func[x] + s[x - 1];
+    for (int y = 1; y < res; ++y) s[(size_t)y * res] = (double)func[(size_t)y * res] + s[(size_t)(y - 1) * res];
+    for (int y = 1; y < res; ++y)
+        for (int x = 1; x < res; ++x) {
+            const size_t i = (size_t)y * res + x;
+            s[i] = (double)func[i] + s[i - 1] + s[i - res] - s[i - res - 1];
+        }
+    for (size_t i = 0; i < n; ++i) sat[i] = (float)s[i];
 }
 // ---- projection and goniometric lights: the host side of vspg_imagelight.h (ImageLightTables: vspg_scene_build.h) -------------------
 // The refusals of vspg_renderer_set_light_image that need no renderer, in its order; 0 or VSPG_EINVAL with the message set
