@@ -37,13 +37,62 @@ VSPG_NS_BEGIN
 
 enum { Q_VV = 0, Q_VS = 1, Q_A = 2, Q_F = 3, Q_COUNT = 4 };
 enum { QC_RES = 0, QC_COM = 1, QC_HEAD = 2, QC_STRIDE = 4 };
-enum { W3_BUSY_S = Q_COUNT * QC_STRIDE, W3_BUSY_V, W3_EXH, W3_LIVE, W3_COUNT };  // (one 16-byte group behind the queues')
+// (one 16-byte group behind the queues'.  The order serves the chunk's tail, see ring_push_all: OLD, BUSY_S, LIVE are three words in a
+//  row and OLD, LIVE, BUSY_V three words two apart)
+enum { W3_BUSY_S = Q_COUNT * QC_STRIDE, W3_LIVE, W3_EXH, W3_BUSY_V, W3_COUNT };
 // CARRY, the spare words of the queue groups: resumed paths still in flight (+ kCarryDrainBit in a launch that suspends nothing: the
 // word then never reads 0), and the suspend buffer's address -- parked in LDS over the persistent loop, whose SGPRs are all spoken for
-enum { W3_OLD = Q_VV * QC_STRIDE + 3, W3_SUSP_LO = Q_VS * QC_STRIDE + 3, W3_SUSP_HI = Q_A * QC_STRIDE + 3 };
+enum { W3_OLD = Q_F * QC_STRIDE + 3, W3_SUSP_LO = Q_VS * QC_STRIDE + 3, W3_SUSP_HI = Q_A * QC_STRIDE + 3 };
+static_assert(W3_BUSY_S == W3_OLD + 1 && W3_LIVE == W3_OLD + 2 && W3_BUSY_V == W3_OLD + 4, "the tail's three lanes reach their words by lane << shift");
 constexpr unsigned kCarryDrainBit = 0x80000000u;
 enum { W3_NONE = 0, W3_VERTEX = 1, W3_SEGMENT = 2, W3_FRESH = 3, W3_EXIT = 4 };
 constexpr unsigned kRestartBit = 0x8000u;
+
+// ---- the policy: which chunk a wavefront takes next --------------------------------------------------------------------------------
+// Order: a FULL chunk of one kind (volume vertices, surface vertices, segments, a fresh tile) before a vertex chunk mixed from both
+// vertex queues, before partial chunks (only while their producers idle), before the exit.  A queue's `avail` is its committed
+// entries nobody has claimed, 0 while a push is between its reservation and its commit, and 0 for Q_F once the tile cursors are dry.
+// The kernel does not hold the four `avail` as scalars: lane q computes queue q's, two ballots give `full` (bit q: avail >= 64) and
+// `any` (bit q: avail > 0), and everything else is FETCHED where a branch needs it -- avail(q) only for a queue whose `any` bit is
+// set, the shared words only by the partial, exit and suspend branches.  A host test walks the same function over plain arrays
+// (tests/test_wg3_policy.py).
+struct W3Pick {
+    unsigned kind, q0, n0, n1;  // ask n0 entries of queue q0; a vertex chunk asks n1 more of the other vertex queue, q0 ^ 1
+};
+enum { W3S_BUSY_S = 0, W3S_BUSY_V, W3S_LIVE, W3S_OLD };
+template <bool CARRY, class Avail, class Shared>
+VSPG_HD W3Pick w3_policy(unsigned full, unsigned any, bool exh, Avail avail, Shared shared) {
+    // CARRY: the cursors are dry and every resumed path has ended -- the workgroup suspends what it holds (behind the loop)
+    if (CARRY && exh && shared(W3S_OLD) == 0u) return W3Pick{W3_EXIT, Q_VV, 0u, 0u};
+    // a full chunk: the queues' numbers are their rank here (Q_VV, Q_VS, Q_A, Q_F), so the lowest set bit names the one to serve
+    if (full != 0u) {
+        const unsigned q = (unsigned)__builtin_ctz(full);
+        return W3Pick{q <= (unsigned)Q_VS ? (unsigned)W3_VERTEX : q == (unsigned)Q_A ? (unsigned)W3_SEGMENT : (unsigned)W3_FRESH, q, 64u, 0u};
+    }
+    if (any & (1u << Q_VV | 1u << Q_VS)) {
+        // (both below 64 here) the larger queue first; a chunk it cannot fill takes the rest from the other one
+        const unsigned aVV = any & (1u << Q_VV) ? avail(Q_VV) : 0u, aVS = any & (1u << Q_VS) ? avail(Q_VS) : 0u;
+        if (aVV + aVS >= 64u || shared(W3S_BUSY_S) == 0u) {
+            const unsigned first = aVV >= aVS ? aVV : aVS, second = aVV >= aVS ? aVS : aVV;
+            return W3Pick{W3_VERTEX, aVV >= aVS ? (unsigned)Q_VV : (unsigned)Q_VS, first, second < 64u - first ? second : 64u - first};
+        }
+    }
+    if ((any & (1u << Q_A)) && shared(W3S_BUSY_V) == 0u) return W3Pick{W3_SEGMENT, Q_A, avail(Q_A), 0u};
+    if (exh && shared(W3S_LIVE) == 0u) return W3Pick{W3_EXIT, Q_VV, 0u, 0u};
+    return W3Pick{W3_NONE, Q_VV, 0u, 0u};
+}
+// ... from the four `avail` and the five shared words as plain values (the form a test can enumerate)
+template <bool CARRY>
+VSPG_HD W3Pick w3_policy_of(const unsigned a[Q_COUNT], unsigned busyS, unsigned busyV, bool exh, unsigned live, unsigned old_word) {
+    unsigned full = 0u, any = 0u;
+    for (int q = 0; q < Q_COUNT; ++q) {
+        const unsigned aq = q == Q_F && exh ? 0u : a[q];
+        full |= (aq >= 64u ? 1u : 0u) << q;
+        any |= (aq > 0u ? 1u : 0u) << q;
+    }
+    const unsigned words[4] = {busyS, busyV, live, old_word};
+    return w3_policy<CARRY>(full, any, exh, [&](int q) { return a[q]; }, [&](int w) { return words[w]; });
+}
 
 // ISG code of a finished sample, one float: 0 = no ISG record, +q = volume event, -q = surface event, q = the VSP the primary
 // segment used (or 0.5): q lies in [0.001, 0.999], so the sign is free and nothing is rounded
@@ -140,31 +189,64 @@ __device__ __forceinline__ void reset_sibling_head(unsigned int *work_head) {
     if (blockIdx.x == 0 && threadIdx.x == 0) *reinterpret_cast<unsigned int *>(reinterpret_cast<uintptr_t>(work_head) ^ 4u) = 0u;
 }
 
-// The scheduler's words in LDS: per queue {reserved, committed, head, -} and {segment chunks in flight, vertex chunks in flight, tile
-// head dry, slots holding a path}, each group 16 bytes: a deciding lane reads all five groups with five back-to-back 128-bit
-// LDS reads and ONE wait.  A 128-bit read is one LDS instruction: {reserved, committed, head} are a snapshot.
+// The scheduler's words in LDS: per queue {reserved, committed, head, -} and {segment chunks in flight, slots holding a path, tile
+// head dry, vertex chunks in flight}, each group 16 bytes.  A deciding wavefront reads them with TWO back-to-back 128-bit LDS reads and
+// one wait: lane q (and q + 4, ...) its queue's group, every lane the shared one.  A 128-bit read is one LDS instruction:
+// {reserved, committed, head} are a snapshot.
 typedef unsigned int w3_u32x4 __attribute__((ext_vector_type(4)));
 typedef const volatile __attribute__((address_space(3))) w3_u32x4 *w3_lds_v4;
 typedef __attribute__((address_space(1))) w3_u32x4 *w3_glb_v4;
 // Every lane hands its slot to the queue its path now belongs to (dq in [0, Q_COUNT), or -1: none): the four reservations are ONE
-// returning LDS atomic (lane q reserves for queue q), then the entries, then the four commits as one atomic.
+// returning LDS atomic (lane q reserves for queue q), then the entries, then the four commits as one atomic -- and then the chunk's
+// tail, ONE more: lanes 0-2 lower {OLD, BUSY_S, LIVE} (a segment chunk, tail_shift 0) or {OLD, LIVE, BUSY_V} (a vertex chunk,
+// tail_shift 1) by {n_old, 1, slots freed}.  The slots freed are the lanes that push to Q_F: nobody else does.
+//
+// Why the tail may be one instruction, and why it stays BEHIND the commits.  LDS serves a wavefront's instructions in order, so a
+// sibling that sees any of the tail's new values can see the commits too; but a sibling READS the queue groups before (never after)
+// the shared group, so it may pair a queue's words from before this push with counters from after it.  Each such pairing makes it
+// take less, never more:
+//   * old queue words, read before the reservation: RES == COM, every entry it counts is an older, committed one;
+//   * read between reservation and commit: RES != COM, the queue counts as empty;
+//   * BUSY_S / BUSY_V lower than the entries it sees justify: it takes a partial chunk that could have been fuller;
+//   * LIVE == 0 or OLD == 0 are seen only behind the commits of the last pushes (this order), so a wavefront that exits or
+//     suspends on them leaves no push outstanding -- its own is committed before it polls, a sibling's before that sibling
+//     lowers the word.  Words that lag (the tail's lanes need not land together) only delay the exit: all three only fall.
+// Riding in the commit atomic itself (lanes 4-6) would be as safe by the same argument but needs a per-lane select of address and
+// operand, more vector instructions than the second atomic's two.
 template <int NP>
-VDEV void ring_push_all(int dq, unsigned entry, unsigned short (*ring)[NP], unsigned int *s_w) {
+VDEV void ring_push_all(int dq, unsigned entry, unsigned short (*ring)[NP], unsigned int *s_w, unsigned n_old, int tail_shift) {
     const int lane = w3_lane();
-    const unsigned long long m0 = __ballot(dq == 0), m1 = __ballot(dq == 1), m2 = __ballot(dq == 2), m3 = __ballot(dq == 3);
-    const unsigned n0 = (unsigned)__popcll(m0), n1 = (unsigned)__popcll(m1), n2 = (unsigned)__popcll(m2), n3 = (unsigned)__popcll(m3);
-    const unsigned myn = lane == 0 ? n0 : lane == 1 ? n1 : lane == 2 ? n2 : n3;
+    const unsigned lane8 = (unsigned)lane << 3;
+    asm volatile("" : "+v"(dq));  // (one register, four compares: the compiler would otherwise rebuild each predicate from the callers' flags)
+    // (the ballot of a predicate, not of an integer: the four masks are the compares' own results, no select-and-compare in between)
+    // (a vertex chunk pushes to Q_A and Q_F only: tail_shift is a constant where this is inlined, and the vertex queues' half drops out)
+    const unsigned long long m0 = tail_shift ? 0ull : __builtin_amdgcn_ballot_w64(dq == 0), m1 = tail_shift ? 0ull : __builtin_amdgcn_ballot_w64(dq == 1);
+    const unsigned long long m2 = __builtin_amdgcn_ballot_w64(dq == 2), m3 = __builtin_amdgcn_ballot_w64(dq == 3);
+    // the four counts (<= 64 each) in the bytes of one scalar: lane q picks its own with one bit-field extract.  A queue that gets
+    // nothing is reserved and committed by 0 -- the atomics run for four lanes either way, and `myn > 0` was a compare and a mask more.
+    const unsigned n3 = (unsigned)__popcll(m3);
+    const unsigned counts = (unsigned)__popcll(m0) | (unsigned)__popcll(m1) << 8 | (unsigned)__popcll(m2) << 16 | n3 << 24;
+    const unsigned myn = __builtin_amdgcn_ubfe(counts, lane8, 8u);
     unsigned base = 0;
-    if (lane < Q_COUNT && myn > 0u) base = atomicAdd(s_w + lane * QC_STRIDE + QC_RES, myn);
-    const unsigned b0 = (unsigned)__builtin_amdgcn_readlane((int)base, 0), b1 = (unsigned)__builtin_amdgcn_readlane((int)base, 1);
-    const unsigned b2 = (unsigned)__builtin_amdgcn_readlane((int)base, 2), b3 = (unsigned)__builtin_amdgcn_readlane((int)base, 3);
-    if (dq >= 0) {
-        const unsigned long long m = dq == 0 ? m0 : dq == 1 ? m1 : dq == 2 ? m2 : m3;
-        const unsigned b = dq == 0 ? b0 : dq == 1 ? b1 : dq == 2 ? b2 : b3;
-        ring[dq][(b + (unsigned)__popcll(m & ((1ull << lane) - 1ull))) % (unsigned)NP] = (unsigned short)entry;
+    if (lane < Q_COUNT) base = atomicAdd(s_w + lane * QC_STRIDE + QC_RES, myn);
+    // reserved base + the lane's rank among its queue's lanes: v_mbcnt takes the ballot from scalar registers and the base as its addend,
+    // two instructions per queue; the lane's own queue picks one of the four sums (the ballots again, as the selects' masks)
+    const auto at = [&](unsigned long long m, int q) {
+        const unsigned b = (unsigned)__builtin_amdgcn_readlane((int)base, q);
+        return __builtin_amdgcn_mbcnt_hi((unsigned)(m >> 32), __builtin_amdgcn_mbcnt_lo((unsigned)m, b));
+    };
+    const unsigned p2 = at(m2, 2), p3 = at(m3, 3);
+    unsigned pos = dq == 2 ? p2 : p3;
+    if (!tail_shift) {
+        const unsigned p0 = at(m0, 0), p1 = at(m1, 1);
+        pos = dq == 0 ? p0 : dq == 1 ? p1 : pos;
     }
+    if (dq >= 0) (&ring[0][0])[__umul24((unsigned)dq, (unsigned)NP) + pos % (unsigned)NP] = (unsigned short)entry;  // ring[dq][pos % NP]
     __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");  // the entries (and the pool records behind them) before the commits
-    if (lane < Q_COUNT && myn > 0u) atomicAdd(s_w + lane * QC_STRIDE + QC_COM, myn);
+    if (lane < Q_COUNT) atomicAdd(s_w + lane * QC_STRIDE + QC_COM, myn);
+    const unsigned tail = tail_shift ? n_old | n3 << 8 | 1u << 16 : n_old | 1u << 8 | n3 << 16;
+    // (a subtracting atomic by name: atomicSub adds the negated operand, one more instruction)
+    if (lane < 3) (void)__hip_atomic_fetch_sub(s_w + W3_OLD + (lane << tail_shift), __builtin_amdgcn_ubfe(tail, lane8, 8u), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
 }
 
 #ifndef VSPG_WG3_IDLE_SLEEP
@@ -387,60 +469,71 @@ __device__ __forceinline__ void wg3_render(
         VSPG_PROF_ACC_BEGIN(prof_decide);
         VSPG_PROF_ACC_BEGIN(prof_idle);
         // ---- this wavefront's next chunk -----------------------------------------------------------------
-        // Every lane reads the same five 16-byte groups (an LDS broadcast) and readfirstlane makes scalars of them: the whole
-        // decision is SALU work -- the kernel is bound by vector issue, and a wavefront polls here while its siblings compute.
-        // Lane 0 performs the claims.  Order: a FULL chunk of one kind (volume vertices, surface vertices, segments, a fresh
-        // tile) before a vertex chunk mixed from both vertex queues, before partial chunks (only while their producers idle).
+        // Lane q reads queue q's 16-byte group and every lane the shared one: two LDS reads, one wait.  Lane q computes its queue's
+        // `avail` in vector code, two ballots turn the four into two 4-bit scalar masks, and the policy (w3_policy, above) is scalar
+        // bit tests -- the kernel is bound by vector issue, and a wavefront polls here while its siblings compute.  Making scalars of
+        // all seventeen words first was sixteen v_readfirstlane a poll; now the policy fetches what its branch needs.
+        // Lane 0 performs the claims.
         unsigned kind = W3_NONE, pos0 = 0, n0 = 0, pos1 = 0, n1 = 0, q0 = Q_VV, tile = 0;
         unsigned fresh_entry = 0;  // a FRESH chunk's free-ring entry of this lane
         {
             const auto U = [](unsigned v) { return (unsigned)__builtin_amdgcn_readfirstlane((int)v); };
             const w3_lds_v4 qw = (w3_lds_v4)(s_w);
-            const w3_u32x4 wVV = qw[Q_VV], wVS = qw[Q_VS], wA = qw[Q_A], wF = qw[Q_F], wM = qw[Q_COUNT];
-            const unsigned hVV = U(wVV.z), hVS = U(wVS.z), hA = U(wA.z), hF = U(wF.z);
-            const unsigned busyS = U(wM.x), busyV = U(wM.y), live = U(wM.w);
-            const unsigned old_word = CARRY ? U(wVV.w) : 1u;
+            const auto L = [](unsigned v, unsigned l) { return (unsigned)__builtin_amdgcn_readlane((int)v, (int)l); };
+            // (both addresses in registers before the first read: built behind it, the second one landed in a register of the first read's
+            //  result and waited for it -- two round trips)
+            w3_lds_v4 pq = qw + (lane & 3), pm = qw + Q_COUNT;
+            asm volatile("" : "+v"(pq), "+v"(pm));
+            const w3_u32x4 wq = *pq, wM = *pm;  // (the queue groups BEFORE the shared one: ring_push_all's argument rests on it)
             const bool exh = U(wM.z) != 0u;
             VSPG_W3T(if (exh) tl.enter(2u, W3T_EXH));
-            const auto avail = [&](w3_u32x4 q, unsigned head) {  // committed entries nobody has claimed; 0 while a push is between its reservation and its commit
-                const unsigned r = U(q.x), c = U(q.y);
-                const int a = (int)(c - head);
-                return r == c && a > 0 ? a : 0;
-            };
-            const int aVV = avail(wVV, hVV), aVS = avail(wVS, hVS), aA = avail(wA, hA), aF = exh ? 0 : avail(wF, hF);
+            // lane q: queue q's committed entries nobody has claimed; they count only while no push stands between its reservation and
+            // its commit.  Q_F is not served once the tile cursors are dry.
+            // (one select, then each ballot is ONE compare's own mask: a ballot of `whole && ...` is built from a 0 / 1 value instead)
+            const int a = wq.x == wq.y ? (int)(wq.y - wq.z) : 0;
+            const unsigned served = exh ? (1u << Q_F) - 1u : (1u << Q_COUNT) - 1u;
+            const unsigned full = (unsigned)__builtin_amdgcn_ballot_w64(a >= 64) & served;
+            const unsigned any = (unsigned)__builtin_amdgcn_ballot_w64(a > 0) & served;
+            const W3Pick pick = w3_policy<CARRY>(
+                full, any, exh, [&](int q) { return L((unsigned)a, (unsigned)q); },
+                [&](int w) { return w == W3S_OLD ? L(wq.w, Q_F) : U(w == W3S_BUSY_S ? wM.x : w == W3S_BUSY_V ? wM.w : wM.y); });
             const auto claim = [&](unsigned q, unsigned head, unsigned n) {  // compare-and-swap on the queue's head: this wavefront owns [head, head + n)
                 unsigned old = head + 1u;
                 if (w3_lane() == 0) old = atomicCAS(s_w + q * QC_STRIDE + QC_HEAD, head, head + n);
                 return U(old) == head;
             };
             const auto bump = [&](int w, int d) { if (w3_lane() == 0) atomicAdd(s_w + w, (unsigned)d); };
-            const auto claim_vertex = [&](int a_first, unsigned h_first, unsigned q_first, int a_second, unsigned h_second, unsigned q_second) {
-                // the larger queue first; a chunk it cannot fill takes the rest from the other one
+            // a fresh claim's two words, BUSY_S by 1 and LIVE by 64, neighbours in LDS: one atomic with two lanes, either way
+            const auto bump_fresh = [&](bool up) {
+                const int l = w3_lane();
+                if (l < 2) {
+                    const unsigned d = __umul24((unsigned)l, 63u) + 1u;  // 1, 64
+                    if (up) atomicAdd(s_w + W3_BUSY_S + l, d);
+                    else atomicSub(s_w + W3_BUSY_S + l, d);
+                }
+            };
+            // (only the chosen queue's head becomes a scalar: the claims' compare value and the chunk's ring position)
+            if (pick.kind == W3_EXIT) {
+                kind = W3_EXIT;
+            } else if (pick.kind == W3_VERTEX) {
                 bump(W3_BUSY_V, 1);
-                const unsigned na = (unsigned)(a_first < 64 ? a_first : 64);
-                if (na > 0u && claim(q_first, h_first, na)) {
-                    kind = W3_VERTEX; q0 = q_first; pos0 = h_first; n0 = na;
-                    const unsigned nb = (unsigned)(a_second < 64 - (int)na ? a_second : 64 - (int)na);
-                    if (nb > 0u && claim(q_second, h_second, nb)) { pos1 = h_second; n1 = nb; }
+                // (both vertex heads from constant lanes and a scalar select: a lane index held in a register goes through a VGPR)
+                const unsigned hVV = L(wq.z, Q_VV), hVS = L(wq.z, Q_VS);
+                const unsigned h_first = pick.q0 == Q_VV ? hVV : hVS, h_second = pick.q0 == Q_VV ? hVS : hVV;
+                if (claim(pick.q0, h_first, pick.n0)) {
+                    kind = W3_VERTEX; q0 = pick.q0; pos0 = h_first; n0 = pick.n0;
+                    if (pick.n1 > 0u && claim(pick.q0 ^ 1u, h_second, pick.n1)) { pos1 = h_second; n1 = pick.n1; }
                 } else {
                     bump(W3_BUSY_V, -1);
                 }
-            };
-            const auto claim_segment = [&]() {
+            } else if (pick.kind == W3_SEGMENT) {
                 bump(W3_BUSY_S, 1);
-                const unsigned na = (unsigned)(aA < 64 ? aA : 64);
-                if (claim(Q_A, hA, na)) { kind = W3_SEGMENT; pos0 = hA; n0 = na; }
+                const unsigned hA = L(wq.z, Q_A);
+                if (claim(Q_A, hA, pick.n0)) { kind = W3_SEGMENT; pos0 = hA; n0 = pick.n0; }
                 else bump(W3_BUSY_S, -1);
-            };
-            const int aV = aVV + aVS;
-            // CARRY: the cursors are dry and every resumed path has ended -- the workgroup suspends what it holds (behind the loop)
-            if (CARRY && exh && old_word == 0u) kind = W3_EXIT;
-            else if (aVV >= 64) claim_vertex(aVV, hVV, Q_VV, 0, hVS, Q_VS);
-            else if (aVS >= 64) claim_vertex(aVS, hVS, Q_VS, 0, hVV, Q_VV);
-            else if (aA >= 64) claim_segment();
-            else if (aF >= 64) {
-                bump(W3_BUSY_S, 1);
-                bump(W3_LIVE, 64);  // BEFORE the tile is claimed: `live == 0` then says nobody can still start a path
+            } else if (pick.kind == W3_FRESH) {
+                bump_fresh(true);  // LIVE BEFORE the tile is claimed: `live == 0` then says nobody can still start a path
+                const unsigned hF = L(wq.z, Q_F);
                 if (claim(Q_F, hF, 64u)) {
                     kind = W3_FRESH; pos0 = hF; n0 = 64u;
                     // The claimed entries are read HERE, before the tile cursors are asked.  The free ring starts full (RES = COM = NP), so a
@@ -467,16 +560,8 @@ __device__ __forceinline__ void wg3_render(
                         ++wtried;
                     }
                 } else {
-                    bump(W3_LIVE, -64);
-                    bump(W3_BUSY_S, -1);
+                    bump_fresh(false);
                 }
-            } else if (aV >= 64 || (aV > 0 && busyS == 0u)) {
-                if (aVV >= aVS) claim_vertex(aVV, hVV, Q_VV, aVS, hVS, Q_VS);
-                else claim_vertex(aVS, hVS, Q_VS, aVV, hVV, Q_VV);
-            } else if (aA > 0 && busyV == 0u) {
-                claim_segment();
-            } else if (exh && live == 0u) {
-                kind = W3_EXIT;
             }
         }
         if (kind == W3_EXIT) break;
@@ -536,14 +621,9 @@ __device__ __forceinline__ void wg3_render(
                     freed = !restart;
                 }
             }
-            ring_push_all<NP>(cont || restart ? Q_A : (freed ? Q_F : -1), (unsigned)slot | (restart ? kRestartBit : 0u), s_ring, s_w);
-            const unsigned n_freed = (unsigned)__popcll(__ballot(freed));
-            const unsigned n_old = CARRY ? (unsigned)__popcll(__ballot(old_done)) : 0u;
-            if (w3_lane() == 0) {
-                if (CARRY && n_old) atomicSub(s_w + W3_OLD, n_old);
-                if (n_freed) atomicSub(s_w + W3_LIVE, n_freed);
-                atomicSub(s_w + W3_BUSY_V, 1u);
-            }
+            // (the chunk's tail -- OLD, LIVE, BUSY_V -- rides behind the push's commits; the slots freed are its Q_F lanes)
+            const unsigned n_old = CARRY ? (unsigned)__popcll(__builtin_amdgcn_ballot_w64(old_done)) : 0u;
+            ring_push_all<NP>(cont || restart ? Q_A : (freed ? Q_F : -1), (unsigned)slot | (restart ? kRestartBit : 0u), s_ring, s_w, n_old, 1);
             VSPG_W3T(tl.chunk_end(0u, n0 + n1));
             continue;
         }
@@ -659,15 +739,13 @@ __device__ __forceinline__ void wg3_render(
                     freed = !restart;
                 }
             }
-            ring_push_all<NP>(toVV ? Q_VV : toVS ? Q_VS : (toA || restart) ? Q_A : (freed ? Q_F : -1), (unsigned)slot | (restart ? kRestartBit : 0u), s_ring, s_w);
-            const unsigned n_freed = (unsigned)__popcll(__ballot(freed));
-            const unsigned n_old = CARRY ? (unsigned)__popcll(__ballot(old_done)) : 0u;
-            if (w3_lane() == 0) {
-                if (CARRY && n_old) atomicSub(s_w + W3_OLD, n_old);
-                if (fresh && !tile_ok) atomicExch(s_w + W3_EXH, 1u);
-                if (n_freed) atomicSub(s_w + W3_LIVE, n_freed);
-                atomicSub(s_w + W3_BUSY_S, 1u);
+            // (the chunk's tail -- OLD, BUSY_S, LIVE -- rides behind the push's commits; EXH before them, where it stood: a sibling
+            //  that sees LIVE == 0 sees the cursors dry)
+            const unsigned n_old = CARRY ? (unsigned)__popcll(__builtin_amdgcn_ballot_w64(old_done)) : 0u;
+            if (fresh && !tile_ok) {
+                if (w3_lane() == 0) atomicExch(s_w + W3_EXH, 1u);
             }
+            ring_push_all<NP>(toVV ? Q_VV : toVS ? Q_VS : (toA || restart) ? Q_A : (freed ? Q_F : -1), (unsigned)slot | (restart ? kRestartBit : 0u), s_ring, s_w, n_old, 0);
             VSPG_W3T(tl.chunk_end(fresh ? 2u : 1u, tile_ok ? n0 : 0u));
         }
     }
