@@ -231,6 +231,41 @@ typedef struct VspgPointLight {
 #define VSPG_TRI_INTERFACE 1
 #define VSPG_TRI_IFACE_SHIFT 1
 #define VSPG_TRI_FLIP_NORMAL 8
+
+/* Image textures on diffuse reflectance: SpectrumImageTexture ("imagemap", src/pbrt/textures.h:250-290, textures.cpp:359-387) under
+ * UVMapping (textures.h:86-106), bound to a DiffuseMaterial's "reflectance" (materials.h:369-380) on rectangles and triangles, evaluated
+ * as the reference does under `Option "bool disabletexturefiltering" true`: every ray differential is zero (interaction.cpp:43-47), so
+ * MIPMap::Filter (util/mipmap.cpp:229-298) takes level 0 for every filter -- "bilinear", "trilinear" and "ewa" all become Bilerp(0, st)
+ * (VSPG_TEXFILTER_BILINEAR), "point" becomes Texel(0, round(st * res - 0.5)).  With (u, v) the hit's surface parameters:
+ *   st = (su * u + du, sv * v + dv);  st[1] = 1 - st[1]
+ *   bilinear: x = st[0] * xres - 0.5f, xi = floor(x), dx = x - xi, likewise y; the texels (xi, yi) (xi+1, yi) (xi, yi+1) (xi+1, yi+1) through
+ *             RemapPixelCoords (util/image.h:93-146: repeat = Mod, non-negative; clamp; black = the texel counts as 0), summed as
+ *             ((1-dx)(1-dy) v0 + dx (1-dy) v1 + (1-dx) dy v2 + dx dy v3) per channel, in that order, no contraction (util/image.h:279-292)
+ *   point:    texel (round(x), round(y)), std::round (halves away from zero), through the same wrap
+ *   rgb = scale * filtered;  rgb = ClampZero(invert ? 1 - rgb : rgb);  R = Clamp(rgb, 0, 1) (the albedo spectrum type)
+ * A one-channel image broadcasts to grey.  A hit whose R is all zero has no BSDF lobes (DiffuseBxDF::Flags): the path ends there
+ * without next-event estimation, as at a Kd = 0 surface.
+ * (u, v) of a hit: a rectangle p00 + u e1 + v e2 has u = Dot(p - p00, e1) / |e1|^2, v = Dot(p - p00, e2) / |e2|^2 (pbrt's default
+ * patch uv (0,0) (1,0) (0,1) (1,1)); a triangle has uv = b0 uv0 + b1 uv1 + b2 uv2 (shapes.h, `uvHit`) with the mesh's "uv" or the
+ * default (0,0) (1,0) (1,1).
+ * Out of scope: filtered lookups (ray differentials, levels above 0, EWA), images whose resolution is no power of two
+ * (Image::GeneratePyramid resamples those before level 0 exists), 8-bit images and colour encodings, spheres, float textures, alpha,
+ * bump or displacement, textures on Le or on anything but diffuse reflectance, procedural textures. */
+#define VSPG_MAX_TEXTURES 8
+#define VSPG_TEXTURE_MAX_RES 4096
+enum { VSPG_TEXWRAP_REPEAT = 0, VSPG_TEXWRAP_CLAMP = 1, VSPG_TEXWRAP_BLACK = 2 };
+enum { VSPG_TEXFILTER_POINT = 0, VSPG_TEXFILTER_BILINEAR = 1 };
+typedef struct VspgTexture {
+    const float *pixels;      /* HOST pointer, xres * yres * channels floats, top row first; copied at create time */
+    int32_t xres, yres;       /* 1 .. VSPG_TEXTURE_MAX_RES, powers of two */
+    int32_t channels;         /* 1 (grey) or 3 (R, G, B) */
+    int32_t wrap;             /* VSPG_TEXWRAP_* */
+    int32_t filter;           /* VSPG_TEXFILTER_* */
+    int32_t invert;           /* 0 or 1 */
+    float scale;              /* "scale" */
+    float su, sv, du, dv;     /* UVMapping "uscale", "vscale", "udelta", "vdelta" */
+} VspgTexture;
+
 typedef struct VspgScene {
     int32_t n_quads;
     VspgQuad quads[VSPG_MAX_QUADS];
@@ -292,6 +327,27 @@ typedef struct VspgScene {
     float rgb_sigma_scale;
     float rgb_le_scale;
 } VspgScene;
+
+/* The scene's image textures (VspgTexture, above) and which surface carries which: a record BESIDE VspgScene, handed to
+ * vspg_renderer_create_textured.  VspgScene keeps its size and every offset (VSPG_ABI_VERSION stays 7): a caller that knows no textures
+ * calls vspg_renderer_create as ever.  A zeroed record holds no texture.
+ *   textures[k]        texture k, k < n_textures
+ *   quad_texture[i]    rectangle i of the scene: 0 = none (its Kd), k = texture k - 1 replaces Kd
+ *   tri_texture        one int32 per triangle of the scene with the same convention, HOST pointer, NULL = none
+ *   tri_uv             6 floats per triangle (uv0, uv1, uv2), HOST pointer, NULL = the default (0,0) (1,0) (1,1)
+ * VSPG_EINVAL at create: n_textures outside 0 .. VSPG_MAX_TEXTURES; a surface's index outside 0 .. n_textures; a texture on a
+ * surface whose material is VSPG_MATERIAL_INTERFACE; a NULL image; xres or yres outside 1 .. VSPG_TEXTURE_MAX_RES; channels other
+ * than 1 or 3; an unknown wrap or filter, an invert other than 0 or 1; a texel, parameter or uv that is NaN or infinite.
+ * VSPG_ESCOPE: a resolution that is not a power of two.  Spheres have no field: textures on them are out of scope.
+ * A scene with a textured surface runs the full-scene kernels (vspg_renderer_kernel_name); the kernels of untextured scenes are
+ * the ones they were. */
+typedef struct VspgSceneTextures {
+    int32_t n_textures;
+    VspgTexture textures[VSPG_MAX_TEXTURES];
+    int32_t quad_texture[VSPG_MAX_QUADS];
+    const int32_t *tri_texture;
+    const float *tri_uv;
+} VspgSceneTextures;
 
 /* ---- integrator parameters: same names and defaults as
  * GuidedVolPathVSPGIntegrator::Create (src/pbrt/cpu/guidedvolpathvspgintegrator.cpp:
@@ -442,6 +498,10 @@ int vspg_scene_fog_box(VspgScene *scene, int xres, int yres);
  * and path-state queues on `cfg->device`. */
 int vspg_renderer_create(const VspgScene *scene, const VspgIntegratorParams *params,
                          const VspgRenderConfig *cfg, VspgRenderer **out);
+/* The same with image textures on the diffuse reflectance of rectangles and triangles (VspgSceneTextures, above); textures == NULL or
+ * a zeroed record: exactly vspg_renderer_create. */
+int vspg_renderer_create_textured(const VspgScene *scene, const VspgSceneTextures *textures, const VspgIntegratorParams *params,
+                                  const VspgRenderConfig *cfg, VspgRenderer **out);
 /* Replaces ~GuidedVolPathVSPGIntegrator (guidedvolpathvspgintegrator.cpp:200-228). */
 int vspg_renderer_destroy(VspgRenderer *r);
 
@@ -931,6 +991,32 @@ int vspg_light_sample_batch(VspgRenderer *r, int n, const float *ctx_p /*3n*/, c
 #define VSPG_LIGHT_PDF_OUT 8
 int vspg_light_pdf_batch(VspgRenderer *r, int light_index, int n, const float *ctx_p /*3n*/, const float *ctx_perr /*3n or NULL*/,
                          const float *ctx_n /*3n*/, const float *wi /*3n*/, float *out /*8n*/, void *stream);
+
+/* Replaces the image of texture `texture_index` (0 .. n_textures - 1 of the scene the renderer was created with) on a live renderer,
+ * modelled on vspg_renderer_set_light_image.  host_pixels: xres * yres * channels floats (HOST array), top row first; the resolution and
+ * the channel count may differ from the old image's; wrap, filter, invert, scale and the mapping stay.  The host builds the device image
+ * (one float4 per texel: R, G, B -- or the grey value three times -- and a pad of 0), uploads it into an allocation of its own and swaps
+ * it in behind `stream`; the old image is released after the swap.  It finishes parked samples and suspended paths on `stream` first,
+ * synchronises `stream` before it returns, and keeps what vspg_renderer_set_environment_image keeps: film, VSP buffer, guiding fields
+ * and training state, counters and the error log persist.  Afterwards the renderer computes what one created with that image
+ * computes, bit for bit.
+ * VSPG_EINVAL, with the renderer exactly as it was and before any allocation: a null argument, an index that names no texture, a
+ * resolution outside 1 .. VSPG_TEXTURE_MAX_RES, channels other than 1 or 3, a texel that is NaN or infinite.  VSPG_ESCOPE, likewise: a
+ * resolution that is not a power of two. */
+int vspg_renderer_set_texture_image(VspgRenderer *r, int texture_index, const float *host_pixels, int xres, int yres, int channels,
+                                    void *stream);
+/* Batch driver of the texture lookup (parity tests): per element the reflectance a path vertex on primitive prim[i] with the three
+ * floats hit[3i..] gets -- tex_uv_quad / tex_uv_tri and texture_lookup (csrc/vspg_texture.h), the functions the path kernels call.
+ * HOST arrays.
+ *   prim   n int32: a rectangle's index (>= 0), or -2 - j for triangle j of the caller's soup
+ *   hit    3n floats: what a vertex carries -- the point on a rectangle, the barycentrics (b0, b1, b2) of a triangle hit
+ *   out    VSPG_TEXTURE_EVAL_OUT floats per element:
+ *   [0..1] (u, v)   [2..3] (s, t) after the flip   [4..6] R   [7] has_lobes (1 or 0)
+ *   An untextured primitive reports its (u, v), (s, t) = 0, its clamped Kd and whether that has a non-zero component.
+ * VSPG_EINVAL: a null argument, a prim that names no rectangle or triangle of the scene (a sphere, a degenerate triangle the build
+ * dropped). */
+#define VSPG_TEXTURE_EVAL_OUT 8
+int vspg_texture_eval_batch(VspgRenderer *r, int n, const int32_t *prim /*n*/, const float *hit /*3n*/, float *out /*8n*/, void *stream);
 
 #ifdef __cplusplus
 }

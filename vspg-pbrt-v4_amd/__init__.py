@@ -93,6 +93,19 @@ class VspgPointLight(C.Structure):
                 ("cone_angle_deg", C.c_float), ("cone_delta_deg", C.c_float)]
 
 
+VSPG_MAX_TEXTURES = 8
+TEXTURE_MAX_RES = 4096  # VSPG_TEXTURE_MAX_RES
+TEXWRAP_REPEAT, TEXWRAP_CLAMP, TEXWRAP_BLACK = 0, 1, 2
+TEXFILTER_POINT, TEXFILTER_BILINEAR = 0, 1
+TEXTURE_EVAL_OUT = 8    # VSPG_TEXTURE_EVAL_OUT: floats per element of vspg_texture_eval_batch
+
+
+class VspgTexture(C.Structure):
+    _fields_ = [("pixels", C.POINTER(C.c_float)), ("xres", C.c_int32), ("yres", C.c_int32), ("channels", C.c_int32),
+                ("wrap", C.c_int32), ("filter", C.c_int32), ("invert", C.c_int32), ("scale", C.c_float),
+                ("su", C.c_float), ("sv", C.c_float), ("du", C.c_float), ("dv", C.c_float)]
+
+
 class VspgScene(C.Structure):
     _fields_ = [("n_quads", C.c_int32), ("quads", VspgQuad * VSPG_MAX_QUADS),
                 ("camera", VspgCamera), ("medium", VspgMedium),
@@ -104,6 +117,12 @@ class VspgScene(C.Structure):
                 ("sphere_Le", f3 * VSPG_MAX_SPHERES), ("sphere_two_sided", C.c_int32 * VSPG_MAX_SPHERES),
                 ("rgb_sigma_a", C.POINTER(C.c_float)), ("rgb_sigma_s", C.POINTER(C.c_float)), ("rgb_Le", C.POINTER(C.c_float)),
                 ("rgb_sigma_scale", C.c_float), ("rgb_le_scale", C.c_float)]
+
+
+class VspgSceneTextures(C.Structure):
+    """The record beside VspgScene that vspg_renderer_create_textured takes (scene_textures(scene) keeps one with a scene)."""
+    _fields_ = [("n_textures", C.c_int32), ("textures", VspgTexture * VSPG_MAX_TEXTURES), ("quad_texture", C.c_int32 * VSPG_MAX_QUADS),
+                ("tri_texture", C.POINTER(C.c_int32)), ("tri_uv", C.POINTER(C.c_float))]
 
 
 class VspgIntegratorParams(C.Structure):
@@ -271,6 +290,7 @@ SYMBOLS = [
     ("vspg_scene_fog_box", C.c_int, [_P(VspgScene), C.c_int, C.c_int]),
     ("vspg_transform_inverse", C.c_int, [C.c_float * 16, C.c_float * 16]),
     ("vspg_renderer_create", C.c_int, [_P(VspgScene), _P(VspgIntegratorParams), _P(VspgRenderConfig), _P(_vp)]),
+    ("vspg_renderer_create_textured", C.c_int, [_P(VspgScene), _P(VspgSceneTextures), _P(VspgIntegratorParams), _P(VspgRenderConfig), _P(_vp)]),
     ("vspg_renderer_destroy", C.c_int, [_vp]),
     ("vspg_render_wave", C.c_int, [_vp, C.c_int, C.c_int, _vp]),
     ("vspg_render_window", C.c_int, [_vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _vp]),
@@ -326,6 +346,8 @@ SYMBOLS = [
     ("vspg_renderer_set_light_image", C.c_int, [_vp, C.c_int, _P(C.c_float), C.c_int, C.c_int, C.c_int, _vp]),
     ("vspg_light_sample_batch", C.c_int, [_vp, C.c_int, _P(C.c_float), _P(C.c_float), _P(C.c_float), _P(C.c_float), _vp]),
     ("vspg_light_pdf_batch", C.c_int, [_vp, C.c_int, C.c_int, _P(C.c_float), _P(C.c_float), _P(C.c_float), _P(C.c_float), _P(C.c_float), _vp]),
+    ("vspg_renderer_set_texture_image", C.c_int, [_vp, C.c_int, _P(C.c_float), C.c_int, C.c_int, C.c_int, _vp]),
+    ("vspg_texture_eval_batch", C.c_int, [_vp, C.c_int, _P(C.c_int32), _P(C.c_float), _P(C.c_float), _vp]),
     ("vspg_renderer_get_tr_buffer", C.c_int, [_vp, _P(C.c_float), _P(C.c_int32), _vp]),
     ("vspg_renderer_set_tr_buffer", C.c_int, [_vp, _P(C.c_float), _vp]),
     ("vspg_renderer_set_guiding_field", C.c_int, [_vp, _P(VspgField), _P(VspgField), _vp]),
@@ -703,6 +725,85 @@ def set_triangles(scene, tri_p, tri_kd=None):
     return scene
 
 
+def texture_image_source(image):
+    """What a texture's image is handed over as: a C-contiguous float32 NumPy array [yres, xres] or [yres, xres, 1] (grey) or
+    [yres, xres, 3] (R, G, B), top row first.  A torch tensor (on any device) is copied to such an array.  Anything else raises
+    ValueError -- here, before the library is called; the library judges the resolution and the texel values.
+    Returns (array, xres, yres, channels)."""
+    import numpy as np
+    if type(image).__module__.split(".")[0] == "torch" and hasattr(image, "data_ptr"):
+        import torch
+        if image.dtype != torch.float32:
+            raise ValueError("texture image must be float32, not %s" % image.dtype)
+        image = np.ascontiguousarray(image.detach().cpu().numpy())
+    if not isinstance(image, np.ndarray):
+        raise ValueError("texture image must be a NumPy array or a torch tensor, not %s" % type(image).__name__)
+    if image.dtype != np.float32:
+        raise ValueError("texture image must be float32, not %s" % image.dtype)
+    if image.ndim not in (2, 3) or (image.ndim == 3 and image.shape[2] not in (1, 3)):
+        raise ValueError("texture image must have shape [yres, xres], [yres, xres, 1] or [yres, xres, 3], not %s" % (tuple(image.shape),))
+    if not image.flags["C_CONTIGUOUS"]:
+        raise ValueError("texture image must be C-contiguous (top row first)")
+    return image, int(image.shape[1]), int(image.shape[0]), 1 if image.ndim == 2 else int(image.shape[2])
+
+
+def scene_textures(scene):
+    """The VspgSceneTextures record that travels with `scene` (created empty at first use): Renderer hands it to
+    vspg_renderer_create_textured.  quad_texture[i] binds rectangle i: 0 = none, k = add_texture's return value."""
+    if not hasattr(scene, "_textures"):
+        scene._textures = VspgSceneTextures()
+    return scene._textures
+
+
+def add_texture(scene, image, filter="bilinear", wrap="repeat", scale=1.0, invert=False, uscale=1.0, vscale=1.0, udelta=0.0, vdelta=0.0):
+    """One more image texture (`Texture "name" "spectrum" "imagemap"` under "uv" mapping): returns the value that binds it to a surface --
+    scene_textures(scene).quad_texture[i] = that value, or set_triangle_textures' entries -- which is its index + 1 (0 = no texture).
+    filter: "point" | "bilinear" ("trilinear" and "ewa" are bilinear at level 0); wrap: "repeat" | "clamp" | "black"."""
+    filters = {"point": TEXFILTER_POINT, "bilinear": TEXFILTER_BILINEAR, "trilinear": TEXFILTER_BILINEAR, "ewa": TEXFILTER_BILINEAR}
+    wraps = {"repeat": TEXWRAP_REPEAT, "clamp": TEXWRAP_CLAMP, "black": TEXWRAP_BLACK}
+    img, xres, yres, channels = texture_image_source(image)
+    tx = scene_textures(scene)
+    k = tx.n_textures
+    if k >= VSPG_MAX_TEXTURES:
+        raise ValueError("a scene holds at most %d textures" % VSPG_MAX_TEXTURES)
+    if isinstance(wrap, str) and wrap not in wraps:
+        raise ValueError("texture wrap must be one of %s, not %r" % (sorted(wraps), wrap))
+    if isinstance(filter, str) and filter not in filters:
+        raise ValueError("texture filter must be one of %s, not %r" % (sorted(filters), filter))
+    t = tx.textures[k]
+    t.pixels = img.ctypes.data_as(C.POINTER(C.c_float))
+    t.xres, t.yres, t.channels = xres, yres, channels
+    t.wrap = wraps[wrap] if isinstance(wrap, str) else int(wrap)
+    t.filter = filters[filter] if isinstance(filter, str) else int(filter)
+    t.invert = 1 if invert else 0
+    t.scale, t.su, t.sv, t.du, t.dv = scale, uscale, vscale, udelta, vdelta
+    if not hasattr(scene, "_tex_keepalive"):
+        scene._tex_keepalive = []
+    scene._tex_keepalive.append(img)
+    tx.n_textures = k + 1
+    return k + 1
+
+
+def set_triangle_textures(scene, tri_texture, tri_uv=None):
+    """Bind textures to the scene's triangles (after set_triangles): tri_texture holds per triangle 0 (none) or add_texture's return
+    value; tri_uv, if given, [n, 3, 2] per-vertex uv (else pbrt's default (0,0) (1,0) (1,1))."""
+    import numpy as np
+    tt = np.ascontiguousarray(tri_texture, dtype=np.int32).reshape(-1)
+    if tt.shape[0] != scene.n_triangles:
+        raise ValueError("tri_texture holds %d entries for %d triangles" % (tt.shape[0], scene.n_triangles))
+    tx = scene_textures(scene)
+    tx.tri_texture = tt.ctypes.data_as(C.POINTER(C.c_int32))
+    keep = [tt]
+    if tri_uv is not None:
+        uv = np.ascontiguousarray(tri_uv, dtype=np.float32).reshape(-1, 6)
+        if uv.shape[0] != scene.n_triangles:
+            raise ValueError("tri_uv holds %d triangles' uv for %d triangles" % (uv.shape[0], scene.n_triangles))
+        tx.tri_uv = uv.ctypes.data_as(C.POINTER(C.c_float))
+        keep.append(uv)
+    scene._tri_tex_keepalive = keep
+    return scene
+
+
 def app_f_params():
     """SURVEY.md App. F integrator line: primary-ray VSP guiding only."""
     p = default_params()
@@ -804,8 +905,12 @@ class Renderer:
         self.cfg = VspgRenderConfig(xres, yres, spp, seed, shard_index, shard_count, device)
         self.scene, self.params = scene, params
         self.h = _vp()
-        _check(self.lib, self.lib.vspg_renderer_create(C.byref(scene), C.byref(params), C.byref(self.cfg),
-                                                       C.byref(self.h)))
+        if hasattr(scene, "_textures"):   # image textures travel beside the scene (scene_textures)
+            _check(self.lib, self.lib.vspg_renderer_create_textured(C.byref(scene), C.byref(scene._textures), C.byref(params), C.byref(self.cfg),
+                                                                    C.byref(self.h)))
+        else:
+            _check(self.lib, self.lib.vspg_renderer_create(C.byref(scene), C.byref(params), C.byref(self.cfg),
+                                                           C.byref(self.h)))
         self.xres, self.yres = xres, yres
 
     def close(self):
@@ -1046,6 +1151,29 @@ class Renderer:
         channels = 1 if image.ndim == 2 else int(image.shape[2])
         _check(self.lib, self.lib.vspg_renderer_set_light_image(self.h, int(index), image.ctypes.data_as(_P(C.c_float)), int(image.shape[1]),
                                                                int(image.shape[0]), channels, _vp(stream or 0)))
+
+    def set_texture_image(self, index, image, stream=None):
+        """Replace the image of texture `index` (0-based) on the live renderer (vspg_renderer_set_texture_image): a float32 NumPy
+        array or torch tensor [yres, xres], [yres, xres, 1] or [yres, xres, 3], top row first (texture_image_source).  The resolution
+        and the channel count may change; the texture's other parameters stay, and so do film, statistics, VSP buffer, guiding fields
+        and counters."""
+        img, xres, yres, channels = texture_image_source(image)
+        _check(self.lib, self.lib.vspg_renderer_set_texture_image(self.h, int(index), img.ctypes.data_as(_P(C.c_float)), xres, yres, channels,
+                                                                 _vp(stream or 0)))
+
+    def texture_eval_batch(self, prim, hit):
+        """Per (primitive, three floats of a vertex): (u, v), (s, t) after the flip, R (3) and has_lobes, as the path kernels evaluate
+        them (vspg_texture_eval_batch).  prim: a rectangle's index or -2 - j for triangle j; hit: the point on the rectangle or the
+        triangle hit's barycentrics.  Returns an (n, TEXTURE_EVAL_OUT) float32 array."""
+        import numpy as np
+        pr = np.ascontiguousarray(np.asarray(prim, dtype=np.int32).reshape(-1))
+        h = np.ascontiguousarray(np.asarray(hit, dtype=np.float32).reshape(-1, 3))
+        if pr.shape[0] != h.shape[0]:
+            raise ValueError("texture_eval_batch: %d primitives but %d hits" % (pr.shape[0], h.shape[0]))
+        out = np.empty((pr.shape[0], TEXTURE_EVAL_OUT), dtype=np.float32)
+        _check(self.lib, self.lib.vspg_texture_eval_batch(self.h, pr.shape[0], pr.ctypes.data_as(_P(C.c_int32)), h.ctypes.data_as(_P(C.c_float)),
+                                                         out.ctypes.data_as(_P(C.c_float)), None))
+        return out
 
     def envlight_batch(self, index, dirs, u):
         """[n, 16] float32 per (direction, variate pair): Le (3), its uv (2), PDF_Li, then SampleLi(u): valid, uv (2), wi (3), pdf,

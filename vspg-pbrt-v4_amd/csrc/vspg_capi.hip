@@ -311,6 +311,11 @@ struct VspgRenderer {
     float *rgb_Le = nullptr;                  // ... its Le grid, raw
     float *env_buf[VSPG_MAX_INFINITE_LIGHTS] = {nullptr, nullptr, nullptr, nullptr};  // image infinite lights: one allocation per light (DEnvLight's arrays)
     void *light_img_buf[VSPG_MAX_POINT_LIGHTS] = {};  // projection / goniometric lights: one allocation per slot (DImageLight::texels)
+    float4 *tex_buf[VSPG_MAX_TEXTURES] = {};  // image textures: one allocation per texture (DTexture::texels)
+    float *tri_uv = nullptr;                  // ... the textured triangles' uv side array (DScene::tri_uv)
+    int n_textured = 0;                       // surfaces that carry a texture (ChoiceFacts::n_textured)
+    int n_texture_slots = 0;                  // VspgSceneTextures::n_textures of the scene the renderer was created with
+    std::vector<int32_t> tri_pos;             // triangle of the caller's soup -> position in `tris`, -1 = dropped (vspg_texture_eval_batch)
     DTri *tris = nullptr;          // triangle soup in BVH leaf order + the BVH (depth-first, skip links)
     DBvh4Node *bvh = nullptr;
     // wavefront pipeline (vspg_wavefront.h): path SoA, lists and per-iteration control blocks, allocated at first use
@@ -399,6 +404,25 @@ static int image_light_install(VspgRenderer *r, int k, const ImageLightTables &T
     r->hscene.image_light[k].texels = buf;
     *old_buf = r->light_img_buf[k];
     r->light_img_buf[k] = buf;
+    return 0;
+}
+
+// The same for a texture's image (texture k): `img` is texture_image_build's, one float4 per texel
+static int texture_install(VspgRenderer *r, int k, const std::vector<float> &img, int xres, int yres, hipStream_t s, float4 **old_buf) {
+    float4 *buf = nullptr;
+    HIPCHK(hipMalloc(&buf, img.size() * sizeof(float)));
+    hipError_t e = hipMemcpyAsync(buf, img.data(), img.size() * sizeof(float), hipMemcpyHostToDevice, s);
+    if (e == hipSuccess) e = hipStreamSynchronize(s);
+    if (e != hipSuccess) {
+        (void)hipFree(buf);
+        return fail(VSPG_EHIP, std::string("uploading the texture image: ") + hipGetErrorName(e));
+    }
+    DTexture &T = r->hscene.tex[k];
+    T.texels = buf;
+    T.xres = xres;
+    T.yres = yres;
+    *old_buf = r->tex_buf[k];
+    r->tex_buf[k] = buf;
     return 0;
 }
 
@@ -589,10 +613,17 @@ extern "C" {
 
 int vspg_renderer_create(const VspgScene *scene, const VspgIntegratorParams *params, const VspgRenderConfig *cfg,
                          VspgRenderer **out) {
+    return vspg_renderer_create_textured(scene, nullptr, params, cfg, out);
+}
+int vspg_renderer_create_textured(const VspgScene *scene, const VspgSceneTextures *textures, const VspgIntegratorParams *params,
+                                  const VspgRenderConfig *cfg, VspgRenderer **out) {
     if (!out) return fail(VSPG_EINVAL, "null out pointer");
     *out = nullptr;
     int rc = validate(scene, params, cfg);
     if (rc) return rc;
+    static const VspgSceneTextures no_textures = {};
+    const VspgSceneTextures &tx = textures ? *textures : no_textures;
+    if ((rc = validate_textures(*scene, tx))) return rc;
     int ndev = 0;
     hipError_t e = hipGetDeviceCount(&ndev);
     if (e != hipSuccess || ndev == 0)
@@ -606,6 +637,8 @@ int vspg_renderer_create(const VspgScene *scene, const VspgIntegratorParams *par
     r->cfg = *cfg;
     if (r->cfg.shard_count < 1) { r->cfg.shard_count = 1; r->cfg.shard_index = 0; }
     build_dscene(r->scene, r->prm, r->cfg, &r->hscene);
+    apply_scene_textures(r->scene, tx, &r->hscene);
+    r->n_texture_slots = tx.n_textures;
     {
         auto same = [](const float *v) { return std::memcmp(&v[0], &v[1], 4) == 0 && std::memcmp(&v[1], &v[2], 4) == 0; };
         const VspgMedium &m = r->scene.medium;
@@ -734,7 +767,7 @@ int vspg_renderer_create(const VspgScene *scene, const VspgIntegratorParams *par
     if (scene->n_triangles > 0) {
         std::vector<DTri> sorted;
         std::vector<DBvh4Node> nodes4;
-        if (const int brc = build_triangle_bvh(*scene, &sorted, &nodes4)) { vspg_renderer_destroy(r); return brc; }
+        if (const int brc = build_triangle_bvh(*scene, &sorted, &nodes4, tx.tri_texture)) { vspg_renderer_destroy(r); return brc; }
         if (!sorted.empty()) {
             CK(hipMalloc(&r->tris, sorted.size() * sizeof(DTri)));
             CK(hipMemcpy(r->tris, sorted.data(), sorted.size() * sizeof(DTri), hipMemcpyHostToDevice));
@@ -744,10 +777,29 @@ int vspg_renderer_create(const VspgScene *scene, const VspgIntegratorParams *par
             r->hscene.n_bvh_nodes = (int32_t)nodes4.size();
             r->hscene.tris = r->tris;
             r->hscene.bvh = r->bvh;
+            r->tri_pos.assign((size_t)scene->n_triangles, -1);
+            for (size_t i = 0; i < sorted.size(); ++i) r->tri_pos[(size_t)sorted[i].id] = (int32_t)i;
+            const std::vector<float> uv = build_tri_uv(tx.tri_uv, sorted);  // (empty: no triangle is textured)
+            if (!uv.empty()) {
+                CK(hipMalloc(&r->tri_uv, uv.size() * sizeof(float)));
+                CK(hipMemcpy(r->tri_uv, uv.data(), uv.size() * sizeof(float), hipMemcpyHostToDevice));
+                r->hscene.tri_uv = r->tri_uv;
+            }
         }
+        r->n_textured = count_textured(*scene, tx, sorted);
         r->scene.tri_p = nullptr;  // the host arrays belong to the caller
         r->scene.tri_kd = nullptr;
         r->scene.tri_flags = nullptr;
+    } else
+        r->n_textured = count_textured(*scene, tx, std::vector<DTri>());
+    r->hscene.n_textured = r->n_textured;
+    for (int k = 0; k < tx.n_textures; ++k) {  // image textures (vspg_texture.h): one float4 per texel, built on the host
+        const VspgTexture &t = tx.textures[k];
+        float4 *old = nullptr;
+        if (const int trc = texture_install(r, k, texture_image_build(t.pixels, t.xres, t.yres, t.channels), t.xres, t.yres, nullptr, &old)) {
+            vspg_renderer_destroy(r);
+            return trc;
+        }
     }
     for (int k = 0; k < r->hscene.n_inf; ++k)
         if (r->hscene.inf_type[k] == VSPG_LIGHT_IMAGE_INFINITE) {  // the 1 x 1 white image (include/vspg.h): the light is valid from creation on
@@ -885,6 +937,8 @@ int vspg_renderer_destroy(VspgRenderer *r) {
     if (r->train_cursor) (void)hipFree(r->train_cursor);
     if (r->train_nsorted) (void)hipFree(r->train_nsorted);
     if (r->train_nsplit) (void)hipFree(r->train_nsplit);
+    for (int k = 0; k < VSPG_MAX_TEXTURES; ++k) if (r->tex_buf[k]) (void)hipFree(r->tex_buf[k]);
+    if (r->tri_uv) (void)hipFree(r->tri_uv);
     if (r->tris) (void)hipFree(r->tris);
     if (r->bvh) (void)hipFree(r->bvh);
     for (int k = 0; k < 2; ++k) if (r->wave_samples[k]) (void)hipFree(r->wave_samples[k]);
@@ -923,9 +977,10 @@ static ChoiceFacts choice_facts(const VspgRenderer *r) {
     f.medium_type = r->scene.medium.type;
     f.n_tris = r->hscene.n_tris, f.n_inf = r->hscene.n_inf, f.n_spheres = r->hscene.n_spheres;
     f.n_point = r->hscene.n_point;
+    f.n_textured = r->n_textured;
     f.has_boundaries = r->hscene.has_boundaries != 0;
     f.lightsampler = r->hscene.lsamp.mode;
-    f.medium_grey = r->medium_grey, f.surfaces_grey = r->surfaces_grey, f.null_zero = r->null_zero;
+    f.medium_grey = r->medium_grey, f.surfaces_grey = r->surfaces_grey && r->n_textured == 0, f.null_zero = r->null_zero;
     f.guided = wants_guiding(r->prm), f.rrguiding = r->prm.rrguiding != 0, f.training = r->training;
     f.tr_calc = r->hscene.tr_calc != 0, f.has_temperature = r->hscene.temperature != nullptr;
     f.resampling = r->prm.vspsamplingmethod == VSPG_VSP_RESAMPLING;
@@ -2417,6 +2472,61 @@ int vspg_light_pdf_batch(VspgRenderer *r, int light_index, int n, const float *c
     HIPCHK(hipGetLastError());
     HIPCHK(hipMemcpyAsync(out, dout.p, (size_t)n * VSPG_LIGHT_PDF_OUT * 4, hipMemcpyDeviceToHost, s));
     HIPCHK(hipStreamSynchronize(s));
+    return 0;
+}
+
+int vspg_renderer_set_texture_image(VspgRenderer *r, int texture_index, const float *host_pixels, int xres, int yres, int channels, void *stream) {
+    // every refusal comes before anything of the renderer changes and before any allocation
+    if (!r || !host_pixels) return fail(VSPG_EINVAL, "null argument");
+    const int k = texture_index;
+    if (k < 0 || k >= r->n_texture_slots) return fail(VSPG_EINVAL, "texture_index names no texture of the scene");
+    if (const int rc = texture_image_refusal(host_pixels, xres, yres, channels)) return rc;
+    const std::vector<float> img = texture_image_build(host_pixels, xres, yres, channels);
+    HIPCHK(hipSetDevice(r->cfg.device));
+    hipStream_t s = (hipStream_t)stream;
+    if (const int rc = flush_parked_samples(r, s)) return rc;  // (paths in flight end under the image they started under)
+    HIPCHK(hipStreamSynchronize(s));  // no launch may still read the old image
+    float4 *old = nullptr;
+    if (const int rc = texture_install(r, k, img, xres, yres, s, &old)) return rc;
+    // the textures are the tail of the record (as in vspg_renderer_set_environment_image: the fields a training renderer updates in
+    // place on the device lie in front of lsamp)
+    const size_t tail = offsetof(DScene, lsamp);
+    HIPCHK(hipMemcpyAsync(reinterpret_cast<char *>(r->dscene) + tail, reinterpret_cast<const char *>(&r->hscene) + tail, sizeof(DScene) - tail,
+                          hipMemcpyHostToDevice, s));
+    HIPCHK(hipStreamSynchronize(s));
+    if (old) (void)hipFree(old);
+    return 0;
+}
+
+int vspg_texture_eval_batch(VspgRenderer *r, int n, const int32_t *prim, const float *hit, float *out, void *stream) {
+    if (!r || n < 0 || (n > 0 && (!prim || !hit || !out))) return fail(VSPG_EINVAL, "null argument");
+    if (n == 0) return 0;
+    std::vector<int32_t> dev_prim((size_t)n);  // the caller's triangle j -> its position in the device's leaf order
+    for (int i = 0; i < n; ++i) {
+        const int p = prim[i];
+        if (p >= 0) {
+            if (p >= r->hscene.n_quads) return fail(VSPG_EINVAL, "prim names no rectangle of the scene");
+            dev_prim[i] = p;
+        } else {
+            const long long j = -2ll - p;
+            if (p == -1 || j >= (long long)r->tri_pos.size() || r->tri_pos[(size_t)j] < 0)
+                return fail(VSPG_EINVAL, "prim names no triangle of the scene (or a degenerate one the build dropped)");
+            dev_prim[i] = -2 - r->tri_pos[(size_t)j];
+        }
+    }
+    HIPCHK(hipSetDevice(r->cfg.device));
+    hipStream_t s = (hipStream_t)stream;
+    DevBuf dp, dh, dout;
+    HIPCHK(hipMalloc(&dp.p, (size_t)n * 4));
+    HIPCHK(hipMalloc(&dh.p, (size_t)n * 12));
+    HIPCHK(hipMalloc(&dout.p, (size_t)n * VSPG_TEXTURE_EVAL_OUT * 4));
+    HIPCHK(hipMemcpyAsync(dp.p, dev_prim.data(), (size_t)n * 4, hipMemcpyHostToDevice, s));
+    HIPCHK(hipMemcpyAsync(dh.p, hit, (size_t)n * 12, hipMemcpyHostToDevice, s));
+    hipLaunchKernelGGL(k_texture_eval, dim3((n + kBlock - 1) / kBlock), dim3(kBlock), 0, s, r->dscene, n, (const int32_t *)dp.p, (const float *)dh.p,
+                       (float *)dout.p);
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipMemcpyAsync(out, dout.p, (size_t)n * VSPG_TEXTURE_EVAL_OUT * 4, hipMemcpyDeviceToHost, s));
+    HIPCHK(hipStreamSynchronize(s));  // (dev_prim is pageable and dropped on return)
     return 0;
 }
 

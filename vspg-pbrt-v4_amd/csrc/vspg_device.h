@@ -829,6 +829,20 @@ struct DSphereLight {
     float inv_area;
     float center[3];
 };
+// Image texture on diffuse reflectance (vspg_texture.h; include/vspg.h VspgTexture): the image as one float4 per texel {R, G, B, 0} (a
+// grey image broadcast), row-major, top row first -- a texel is one aligned 16-byte load -- and the lookup's parameters.  xres and yres
+// are powers of two.  Built on the host (texture_image_build, vspg_scene_build.hip) with the renderer and by
+// vspg_renderer_set_texture_image.
+struct DTexture {
+    const float4 *texels;
+    int32_t xres, yres;
+    int32_t wrap, filter, invert;  // VSPG_TEXWRAP_*, VSPG_TEXFILTER_*, 0 / 1
+    float scale, su, sv, du, dv;
+    int32_t pad;
+};
+// The texture of a triangle travels in DTri::flags above the SURF_* bits (0 = none, k = texture k - 1): DTri keeps its 80 bytes, and
+// the per-triangle uv side array (DScene::tri_uv) is read only for a textured triangle.
+enum { SURF_FLAG_MASK = 7, TRI_TEX_SHIFT = 8 };
 struct DScene {
     int32_t n_quads, n_lights;
     int32_t n_tris, n_bvh_nodes;
@@ -931,6 +945,14 @@ struct DScene {
     // portal image infinite lights: portal[k].res > 0 turns infinite light k (type VSPG_LIGHT_IMAGE_INFINITE) into a
     // PortalImageInfiniteLight (vspg_portallight.h).  Behind everything else: only FULL light code reads here.
     DPortalLight portal[VSPG_MAX_INFINITE_LIGHTS];
+    // image textures on diffuse reflectance (vspg_texture.h): n_textured = the surfaces that carry one (0: vertex_setup<FULL> skips the
+    // lookup wave-uniformly); quad_tex[i] = rectangle i's texture (0 = none, k = tex[k - 1]); tri_uv = 6 floats per triangle in the order
+    // of `tris` (uv0, uv1, uv2; the default (0,0) (1,0) (1,1) where the caller gave none), null when no triangle is textured.  Behind
+    // everything else: only vertex_setup<FULL> reads here.
+    int32_t n_textured;
+    int32_t quad_tex[VSPG_MAX_QUADS];
+    const float *tri_uv;
+    DTexture tex[VSPG_MAX_TEXTURES];
 };
 // the length of the scene's light list (full-scene kernels): one line per light kind
 __host__ __device__ __forceinline__ int light_list_size(const DScene &S) { return S.n_lights + S.n_inf + S.n_point + S.n_sphere_lights; }
@@ -1693,7 +1715,7 @@ VLEAF bool scene_intersect_any(const DScene &S, V3 o, V3 d, float tMax) {
 // ---- medium boundaries -----------------------------------------------------------------------------------------------
 // SURF_* flags of the surface a hit names (rectangle: LDS copy; triangle / sphere: the scene arrays)
 VDEV int surf_flags(const DScene &S, int prim) {
-    if (is_tri(prim)) return S.tris[tri_of(prim)].flags;
+    if (is_tri(prim)) return S.tris[tri_of(prim)].flags & SURF_FLAG_MASK;  // (the bits above name the triangle's texture)
     if (is_sphere(prim)) return S.spheres[sphere_of(prim)].flags;
     return quad_at(prim).flags;
 }

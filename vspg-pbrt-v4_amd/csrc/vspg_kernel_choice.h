@@ -13,6 +13,7 @@ struct ChoiceFacts {  // what the decision reads of a renderer
     int medium_type = VSPG_MEDIUM_NONE;
     int n_tris = 0, n_inf = 0, n_spheres = 0;
     int n_point = 0;  // point and spot lights
+    int n_textured = 0;  // surfaces whose reflectance is an image texture (vspg_texture.h)
     bool has_boundaries = false;
     int lightsampler = VSPG_LIGHTSAMPLER_UNIFORM;
     bool medium_grey = false, surfaces_grey = false, null_zero = false;  // bitwise grey sigma_a / sigma_s / Le; grey Kd; sigma_n == 0
@@ -69,8 +70,9 @@ inline KernelChoice choose_kernel(const ChoiceFacts &f, const ChoiceEnv &env) {
     // a scene of rectangles and area lights only, one medium filling it: what the workgroup kernel's specialised instantiations are built for
     // (HomogeneousMediumT::kSimpleScene).  Triangle hits carry a per-hit error bound the LDS pool record has no room for; medium boundaries,
     // interface materials and spheres are served by the full-scene code paths; so are power / BVH picks of a multi-light scene, and
-    // point and spot lights (sample_light<FULL> alone dispatches on them).
-    const bool simple = f.n_tris == 0 && f.n_inf == 0 && f.n_point == 0 && f.lightsampler == VSPG_LIGHTSAMPLER_UNIFORM && !f.has_boundaries && f.n_spheres == 0;
+    // point and spot lights (sample_light<FULL> alone dispatches on them), and textured surfaces (vertex_setup<FULL> alone looks a texel up).
+    const bool simple = f.n_tris == 0 && f.n_inf == 0 && f.n_point == 0 && f.lightsampler == VSPG_LIGHTSAMPLER_UNIFORM && !f.has_boundaries && f.n_spheres == 0 &&
+                        f.n_textured == 0;
     // guided renders over a homogeneous medium: the grey / zero-null-coefficient / rectangle-scene instantiation (the segment half of the
     // loop sheds the same per-channel work as the headline kernel's instantiation)
     const bool guided_grey_simple = hom && f.medium_grey && f.surfaces_grey && f.null_zero && simple && !env.no_grey_guided;

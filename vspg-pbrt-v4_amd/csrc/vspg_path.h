@@ -9,6 +9,7 @@
 #include "vspg_train.h"
 #include "vspg_envmap.h"     // what vspg_envlight.h shares with the host builders (its own namespace block: included out here)
 #include "vspg_portalmap.h"  // ... and vspg_portallight.h
+#include "vspg_texture.h"
 
 VSPG_NS_BEGIN
 
@@ -976,6 +977,16 @@ VDEV void vertex_setup(const DScene &S, const PathState &st, const Vertex &vx, V
             si.n = ld3(q.n);
             bsdf = bsdf_make<GREY_KD>(q);
             intr.pi = p3i_from_err(si.p, ld3(q.perr));
+        }
+        if constexpr (FULL) {  // an image texture on the reflectance replaces R and has_lobes, per hit (vspg_texture.h)
+            if (S.n_textured != 0 && !is_sphere(vx.quad)) {
+                const int k = tex_of_prim(S, vx.quad);
+                if (k != 0) {
+                    const TexEval e = texture_eval(S, k, vx.quad, vx.p);
+                    bsdf.R = e.R;
+                    bsdf.has_lobes = e.has_lobes;
+                }
+            }
         }
         intr.is_surface = true;
         intr.n = si.n;

@@ -244,6 +244,40 @@ __global__ __launch_bounds__(kBlock) void k_light_sample_batch(const DScene *__r
     o[11] = pl.x; o[12] = pl.y; o[13] = pl.z;
     o[14] = delta_light ? 1.f : 0.f;
 }
+// vspg_texture_eval_batch (include/vspg.h): the reflectance of a vertex on primitive prim[i] (device numbering: a rectangle's index, or
+// -2 - the triangle's position in S.tris) with the three floats hit[3i..], through tex_of_prim / texture_eval as vertex_setup<FULL> calls them
+__global__ __launch_bounds__(kBlock) void k_texture_eval(const DScene *__restrict__ Sp, int n, const int32_t *__restrict__ prim,
+                                                         const float *__restrict__ hit, float *__restrict__ out) {
+    const int i = blockIdx.x * kBlock + threadIdx.x;
+    const DScene &S = *Sp;
+    stage_scene_lds(S);  // tex_uv_quad reads the rectangle's record from the LDS copy
+    __syncthreads();
+    if (i >= n) return;
+    float *o = out + (size_t)VSPG_TEXTURE_EVAL_OUT * i;
+    const int pr = prim[i];
+    const V3 h = ld3(hit + 3 * (size_t)i);
+    const int k = S.n_textured != 0 ? tex_of_prim(S, pr) : 0;
+    if (k != 0) {
+        const TexEval e = texture_eval(S, k, pr, h);
+        o[0] = e.uv.u; o[1] = e.uv.v; o[2] = e.s; o[3] = e.t;
+        o[4] = e.R.r; o[5] = e.R.g; o[6] = e.R.b;
+        o[7] = e.has_lobes ? 1.f : 0.f;
+    } else {  // an untextured surface: its (u, v) and the constant reflectance of bsdf_make / bsdf_make_tri
+        TexUv uv;
+        Bsdf b;
+        if (is_tri(pr)) {
+            alignas(8) const float def[6] = {0.f, 0.f, 1.f, 0.f, 1.f, 1.f};  // the default uv (0,0) (1,0) (1,1)
+            uv = tex_uv_tri(def, h);
+            b = bsdf_make_tri(S.tris[tri_of(pr)]);
+        } else {
+            uv = tex_uv_quad(quad_at(pr), h);
+            b = bsdf_make<false>(quad_at(pr));
+        }
+        o[0] = uv.u; o[1] = uv.v; o[2] = 0.f; o[3] = 0.f;
+        o[4] = b.R.r; o[5] = b.R.g; o[6] = b.R.b;
+        o[7] = b.has_lobes ? 1.f : 0.f;
+    }
+}
 // vspg_light_pdf_batch (include/vspg.h): for one light with a shape (a rectangle or a sphere of the light list) what li_surface_pre
 // computes when a ray from the context along wi is weighed against it -- light_sampler_pmf, light_pdf_li / sphere_pdf_li, and the
 // shape's own intersection from ctx.SpawnRay(wi) with light_L / sphere_light_L at the hit.  ctx_perr == nullptr: exact points.

@@ -41,11 +41,31 @@ PcgJump pcg_jump(unsigned long long delta);
 bool wants_guiding(const VspgIntegratorParams &p);
 bool wants_training(const VspgIntegratorParams &p);
 
-// false: a degenerate triangle, which no ray hits
-bool derive_triangle(const float *p9, const float *kd, int id, DTri *T, const int32_t *flags = nullptr);
+// false: a degenerate triangle, which no ray hits.  tex: VspgSceneTextures::tri_texture (the triangle's texture goes above the SURF_* bits)
+bool derive_triangle(const float *p9, const float *kd, int id, DTri *T, const int32_t *flags = nullptr, const int32_t *tex = nullptr);
 // The triangle soup as the kernels read it: the accepted triangles in leaf order and the four-wide BVH over them (both empty when no
-// triangle is accepted).  0, or VSPG_ESCOPE when even median splits leave the tree too deep for the traversal's stack (kBvhStack).
-int build_triangle_bvh(const VspgScene &sc, std::vector<DTri> *tris, std::vector<DBvh4Node> *nodes);
+// triangle is accepted).  tri_texture: VspgSceneTextures::tri_texture or null.  0, or VSPG_ESCOPE when even median splits leave the tree too deep for the traversal's stack (kBvhStack).
+int build_triangle_bvh(const VspgScene &sc, std::vector<DTri> *tris, std::vector<DBvh4Node> *nodes, const int32_t *tri_texture = nullptr);
+
+// ---- image textures on diffuse reflectance: the host side of vspg_texture.h ---------------------------------------------------
+// The refusals of one image, shared by create and vspg_renderer_set_texture_image, in the header's order; 0, VSPG_EINVAL or
+// VSPG_ESCOPE with the message set
+int texture_image_refusal(const float *pixels, int xres, int yres, int channels);
+// ... of the record beside the scene (vspg_renderer_create_textured calls it behind validate): the textures, their parameters and
+// every surface's index
+int validate_textures(const VspgScene &sc, const VspgSceneTextures &tx);
+// the device image: one float4 {R, G, B, 0} per texel (a grey image broadcast), row-major, top row first; 4 * xres * yres floats
+std::vector<float> texture_image_build(const float *pixels, int xres, int yres, int channels);
+// everything of a DTexture but the image pointer
+void texture_apply(const VspgTexture &in, DTexture *T);
+// the textures' records and the rectangles' indices into a DScene that build_dscene made (the images, the triangles' uv and
+// n_textured are vspg_renderer_create_textured's)
+void apply_scene_textures(const VspgScene &sc, const VspgSceneTextures &tx, DScene *D);
+// the surfaces that carry a texture: rectangles, and triangles the build keeps
+int count_textured(const VspgScene &sc, const VspgSceneTextures &tx, const std::vector<DTri> &tris);
+// DScene::tri_uv for `tris` (build_triangle_bvh's leaf order): 6 floats per triangle, the caller's or the default (0,0) (1,0) (1,1);
+// empty when no triangle of `tris` is textured
+std::vector<float> build_tri_uv(const float *tri_uv, const std::vector<DTri> &tris);
 
 int majorant_res(const VspgMedium &m);
 std::vector<int2> majorant_axis_ranges(const VspgMedium &m);

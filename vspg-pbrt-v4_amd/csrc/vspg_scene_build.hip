@@ -1169,7 +1169,7 @@ struct Builder {
 }  // namespace bvhbuild
 
 // what Triangle::InteractionFromIntersection derives from the vertices alone (shapes.h:888-938), same float operations
-bool derive_triangle(const float *p9, const float *kd, int id, DTri *T, const int32_t *flags) {
+bool derive_triangle(const float *p9, const float *kd, int id, DTri *T, const int32_t *flags, const int32_t *tex) {
     using namespace hostmath;
     const H3 p0 = ld(p9), p1 = ld(p9 + 3), p2 = ld(p9 + 6);
     auto sub = [](H3 a, H3 b) { return H3{a.x - b.x, a.y - b.y, a.z - b.z}; };
@@ -1195,20 +1195,21 @@ bool derive_triangle(const float *p9, const float *kd, int id, DTri *T, const in
     for (int k = 0; k < 3; ++k) { float v = kd ? kd[3 * id + k] : 0.5f; T->Kd[k] = v < 0 ? 0 : (v > 1 ? 1 : v); }
     const int fl = flags ? flags[id] : 0;
     T->flags = surf_flags_of(fl & VSPG_TRI_INTERFACE, fl >> VSPG_TRI_IFACE_SHIFT);
+    if (tex && tex[id] > 0) T->flags |= tex[id] << TRI_TEX_SHIFT;  // (validate_textures: 1 .. n_textures, never on an interface triangle)
     if (fl & VSPG_TRI_FLIP_NORMAL) { T->nx = -T->nx; T->ny = -T->ny; T->nz = -T->nz; }  // reverseOrientation ^ transformSwapsHandedness (shapes.h:934-936)
     return true;
 }
 
 // The soup as the device reads it: derive the triangles, build the binary tree and collapse it to four-wide nodes, fall back to
 // median splits when that tree is too deep for the traversal's stack, then put the triangles in the final tree's leaf order.
-int build_triangle_bvh(const VspgScene &sc, std::vector<DTri> *tris, std::vector<DBvh4Node> *nodes4) {
+int build_triangle_bvh(const VspgScene &sc, std::vector<DTri> *tris, std::vector<DBvh4Node> *nodes4, const int32_t *tri_texture) {
     tris->clear();
     nodes4->clear();
     std::vector<DTri> all;
     all.reserve(sc.n_triangles);
     for (int i = 0; i < sc.n_triangles; ++i) {
         DTri T;
-        if (derive_triangle(sc.tri_p + 9 * (size_t)i, sc.tri_kd, i, &T, sc.tri_flags)) all.push_back(T);
+        if (derive_triangle(sc.tri_p + 9 * (size_t)i, sc.tri_kd, i, &T, sc.tri_flags, tri_texture)) all.push_back(T);
     }
     if (all.empty()) return 0;
     bvhbuild::Builder B;
@@ -1243,6 +1244,85 @@ int build_triangle_bvh(const VspgScene &sc, std::vector<DTri> *tris, std::vector
     for (size_t i = 0; i < all.size(); ++i) (*tris)[i] = all[B.order[i]];
     *nodes4 = B.nodes4;
     return 0;
+}
+
+// ---- image textures on diffuse reflectance (vspg_texture.h; include/vspg.h VspgTexture) ----
+static bool power_of_two(int v) { return v > 0 && (v & (v - 1)) == 0; }
+int texture_image_refusal(const float *pixels, int xres, int yres, int channels) {
+    if (!pixels) return fail(VSPG_EINVAL, "a texture without an image (null pixels)");
+    if (xres < 1 || xres > VSPG_TEXTURE_MAX_RES || yres < 1 || yres > VSPG_TEXTURE_MAX_RES)
+        return fail(VSPG_EINVAL, "texture resolution outside 1 .. VSPG_TEXTURE_MAX_RES (4096)");
+    if (channels != 1 && channels != 3) return fail(VSPG_EINVAL, "a texture image has 1 or 3 channels");
+    if (!power_of_two(xres) || !power_of_two(yres))
+        return fail(VSPG_ESCOPE, "texture resolution is not a power of two: the reference resamples such an image before level 0 exists, and that resampling is not built");
+    const size_t n = (size_t)xres * yres * channels;
+    for (size_t i = 0; i < n; ++i)
+        if (!std::isfinite(pixels[i])) return fail(VSPG_EINVAL, "a texture image holds a texel that is not-a-number or infinite");
+    return 0;
+}
+int validate_textures(const VspgScene &sc, const VspgSceneTextures &tx) {
+    if (tx.n_textures < 0 || tx.n_textures > VSPG_MAX_TEXTURES) return fail(VSPG_EINVAL, "n_textures out of range");
+    for (int k = 0; k < tx.n_textures; ++k) {
+        const VspgTexture &t = tx.textures[k];
+        if (t.wrap != VSPG_TEXWRAP_REPEAT && t.wrap != VSPG_TEXWRAP_CLAMP && t.wrap != VSPG_TEXWRAP_BLACK) return fail(VSPG_EINVAL, "unknown texture wrap mode");
+        if (t.filter != VSPG_TEXFILTER_POINT && t.filter != VSPG_TEXFILTER_BILINEAR) return fail(VSPG_EINVAL, "unknown texture filter");
+        if (t.invert != 0 && t.invert != 1) return fail(VSPG_EINVAL, "a texture's invert must be 0 or 1");
+        const float prm[5] = {t.scale, t.su, t.sv, t.du, t.dv};
+        for (int j = 0; j < 5; ++j)
+            if (!std::isfinite(prm[j])) return fail(VSPG_EINVAL, "a texture's scale, uscale, vscale, udelta or vdelta is not finite");
+        if (const int rc = texture_image_refusal(t.pixels, t.xres, t.yres, t.channels)) return rc;
+    }
+    for (int i = 0; i < sc.n_quads && i < VSPG_MAX_QUADS; ++i) {
+        const int k = tx.quad_texture[i];
+        if (k < 0 || k > tx.n_textures) return fail(VSPG_EINVAL, "a rectangle's texture index names no texture of the scene");
+        if (k != 0 && sc.quads[i].material == VSPG_MATERIAL_INTERFACE) return fail(VSPG_EINVAL, "a texture on a rectangle whose material is \"interface\"");
+    }
+    if (tx.tri_texture)
+        for (int i = 0; i < sc.n_triangles; ++i) {
+            const int k = tx.tri_texture[i];
+            if (k < 0 || k > tx.n_textures) return fail(VSPG_EINVAL, "a triangle's texture index names no texture of the scene");
+            if (k != 0 && sc.tri_flags && (sc.tri_flags[i] & VSPG_TRI_INTERFACE)) return fail(VSPG_EINVAL, "a texture on a triangle whose material is \"interface\"");
+        }
+    if (tx.tri_uv)
+        for (size_t i = 0; i < 6 * (size_t)sc.n_triangles; ++i)
+            if (!std::isfinite(tx.tri_uv[i])) return fail(VSPG_EINVAL, "a triangle's uv is not finite");
+    return 0;
+}
+std::vector<float> texture_image_build(const float *pixels, int xres, int yres, int channels) {
+    const size_t n = (size_t)xres * yres;
+    std::vector<float> img(4 * n);
+    for (size_t i = 0; i < n; ++i) {
+        for (int c = 0; c < 3; ++c) img[4 * i + c] = channels == 3 ? pixels[3 * i + c] : pixels[i];
+        img[4 * i + 3] = 0.f;
+    }
+    return img;
+}
+void texture_apply(const VspgTexture &in, DTexture *T) {
+    T->xres = in.xres; T->yres = in.yres;
+    T->wrap = in.wrap; T->filter = in.filter; T->invert = in.invert;
+    T->scale = in.scale; T->su = in.su; T->sv = in.sv; T->du = in.du; T->dv = in.dv;
+    T->pad = 0;
+}
+void apply_scene_textures(const VspgScene &sc, const VspgSceneTextures &tx, DScene *D) {
+    for (int k = 0; k < tx.n_textures && k < VSPG_MAX_TEXTURES; ++k) texture_apply(tx.textures[k], &D->tex[k]);
+    for (int i = 0; i < sc.n_quads && i < VSPG_MAX_QUADS; ++i) D->quad_tex[i] = tx.quad_texture[i];
+}
+int count_textured(const VspgScene &sc, const VspgSceneTextures &tx, const std::vector<DTri> &tris) {
+    int n = 0;
+    for (int i = 0; i < sc.n_quads && i < VSPG_MAX_QUADS; ++i) n += tx.quad_texture[i] != 0;
+    for (const DTri &T : tris) n += (T.flags >> TRI_TEX_SHIFT) != 0;
+    return n;
+}
+std::vector<float> build_tri_uv(const float *tri_uv, const std::vector<DTri> &tris) {
+    bool any = false;
+    for (const DTri &T : tris) any = any || (T.flags >> TRI_TEX_SHIFT) != 0;
+    std::vector<float> uv;
+    if (!any) return uv;
+    static const float def[6] = {0.f, 0.f, 1.f, 0.f, 1.f, 1.f};  // Triangle::InteractionFromIntersection's default uv (shapes.h)
+    uv.resize(6 * tris.size());
+    for (size_t i = 0; i < tris.size(); ++i)
+        for (int j = 0; j < 6; ++j) uv[6 * i + j] = tri_uv ? tri_uv[6 * (size_t)tris[i].id + j] : def[j];
+    return uv;
 }
 
 bool wants_guiding(const VspgIntegratorParams &p) {

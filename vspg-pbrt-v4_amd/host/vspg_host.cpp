@@ -87,6 +87,8 @@ ParameterDictionary ParameterDictionary::Parse(const std::string &text) {
             d.Bool(name, toks[0] == "true");
         } else if (type == "string") {
             d.String(name, toks[0]);
+        } else if (type == "texture") {  // a named texture bound to a parameter: kept as a string under "texture <name>"
+            d.String("texture " + name, toks[0]);
         } else if (type == "point3" && toks.size() > 3) {
             if (toks.size() % 3) throw Error("parameter \"" + name + "\": point3 values come in threes");
             std::vector<float> a; for (auto &t : toks) a.push_back(num(t));
@@ -434,10 +436,10 @@ VspgIntegratorParams ParseIntegratorParams(const ParameterDictionary &parameters
 
 std::unique_ptr<Integrator> Integrator::Create(const std::string &name, const ParameterDictionary &parameters,
                                                const VspgScene &scene, int xres, int yres, int pixelSamples, int seed,
-                                               int device) {
+                                               int device, const VspgSceneTextures *textures) {
     std::unique_ptr<Integrator> integrator;
     if (name == "guidedvolpathvspg")
-        integrator = GuidedVolPathVSPGIntegrator::Create(parameters, scene, xres, yres, pixelSamples, seed, device);
+        integrator = GuidedVolPathVSPGIntegrator::Create(parameters, scene, xres, yres, pixelSamples, seed, device, textures);
     else if (name == "guidedvolpath") {
         // the reference's "guidedvolpath" has no VSP guiding and rejects "vspguiding" as unused;
         // BASELINE.json nevertheless names `guidedvolpath` + vspguiding: accept that spelling as
@@ -445,7 +447,7 @@ std::unique_ptr<Integrator> Integrator::Create(const std::string &name, const Pa
         if (!parameters.GetOneBool("vspguiding", false))
             throw Error("integrator \"guidedvolpath\" without \"vspguiding\" true is outside this build's scope "
                         "(directional guiding only); use \"guidedvolpathvspg\"");
-        integrator = GuidedVolPathVSPGIntegrator::Create(parameters, scene, xres, yres, pixelSamples, seed, device);
+        integrator = GuidedVolPathVSPGIntegrator::Create(parameters, scene, xres, yres, pixelSamples, seed, device, textures);
     } else
         throw Error(name + ": integrator type unknown.");  // integrators.cpp:3760
     parameters.ReportUnused();  // integrators.cpp:3766
@@ -454,24 +456,25 @@ std::unique_ptr<Integrator> Integrator::Create(const std::string &name, const Pa
 
 std::unique_ptr<GuidedVolPathVSPGIntegrator> GuidedVolPathVSPGIntegrator::Create(const ParameterDictionary &parameters,
                                                                                  const VspgScene &scene, int xres, int yres,
-                                                                                 int pixelSamples, int seed, int device) {
+                                                                                 int pixelSamples, int seed, int device,
+                                                                                 const VspgSceneTextures *textures) {
     GuidingCacheSettings cache;
     TrBufferSettings tr;
     IsgBufferSettings isg;
     VspgIntegratorParams p = ParseIntegratorParams(parameters, &cache, &tr, &isg);
-    return std::make_unique<GuidedVolPathVSPGIntegrator>(p, scene, xres, yres, pixelSamples, seed, device, cache, tr, isg);
+    return std::make_unique<GuidedVolPathVSPGIntegrator>(p, scene, xres, yres, pixelSamples, seed, device, cache, tr, isg, textures);
 }
 
 GuidedVolPathVSPGIntegrator::GuidedVolPathVSPGIntegrator(const VspgIntegratorParams &p, const VspgScene &scene, int xres,
                                                          int yres, int pixelSamples, int seed, int device,
                                                          const GuidingCacheSettings &cache, const TrBufferSettings &tr,
-                                                         const IsgBufferSettings &isg)
+                                                         const IsgBufferSettings &isg, const VspgSceneTextures *textures)
     : params(p), spp(pixelSamples), cacheSettings(cache), trSettings(tr), isgSettings(isg) {
     std::memset(&cfg, 0, sizeof cfg);
     cfg.xres = xres; cfg.yres = yres; cfg.spp = pixelSamples; cfg.seed = seed;
     cfg.shard_index = 0; cfg.shard_count = 1; cfg.device = device;
     bounds[2] = xres; bounds[3] = yres;
-    int rc = vspg_renderer_create(&scene, &params, &cfg, &renderer);
+    int rc = vspg_renderer_create_textured(&scene, textures, &params, &cfg, &renderer);
     if (rc != 0) throw Error(std::string("GuidedVolPathVSPGIntegrator: ") + vspg_last_error());
     if (cacheSettings.load) {  // :116-125: FileExists() ? load (guideTraining = false) : warn and train a fresh field
         std::FILE *probe = std::fopen(cacheSettings.fileName.c_str(), "rb");

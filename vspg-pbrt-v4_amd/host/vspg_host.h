@@ -187,17 +187,19 @@ class Integrator {
     // the dictionary carries "vspguiding" (the option BASELINE.json names), see SURVEY.md 0.1
     static std::unique_ptr<Integrator> Create(const std::string &name, const ParameterDictionary &parameters,
                                               const VspgScene &scene, int xres, int yres, int pixelSamples,
-                                              int seed = 0, int device = 0);
+                                              int seed = 0, int device = 0, const VspgSceneTextures *textures = nullptr);
 };
 
 class GuidedVolPathVSPGIntegrator : public Integrator {
   public:
     static std::unique_ptr<GuidedVolPathVSPGIntegrator> Create(const ParameterDictionary &parameters,
                                                                const VspgScene &scene, int xres, int yres,
-                                                               int pixelSamples, int seed, int device);
+                                                               int pixelSamples, int seed, int device,
+                                                               const VspgSceneTextures *textures = nullptr);
     GuidedVolPathVSPGIntegrator(const VspgIntegratorParams &p, const VspgScene &scene, int xres, int yres,
                                 int pixelSamples, int seed, int device, const GuidingCacheSettings &cache = {},
-                                const TrBufferSettings &tr = {}, const IsgBufferSettings &isg = {});
+                                const TrBufferSettings &tr = {}, const IsgBufferSettings &isg = {},
+                                const VspgSceneTextures *textures = nullptr);  // image textures beside the scene (vspg_renderer_create_textured)
     ~GuidedVolPathVSPGIntegrator() override;
     void Render() override;       // wave loop: 1 spp per wave, PostProcessWave after each
     void PostProcessWave();       // guidedvolpathvspgintegrator.cpp:230-260

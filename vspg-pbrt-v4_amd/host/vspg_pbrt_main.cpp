@@ -89,6 +89,20 @@ int main(int argc, char **argv) {
             }
             std::printf("\n");
         }
+        {   // ... the image textures and the surfaces that carry one
+            const VspgSceneTextures &tx = sd->textures;
+            for (int k = 0; k < tx.n_textures; ++k) {
+                const VspgTexture &t = tx.textures[k];
+                std::printf("texture %d: %d x %d x %d wrap %d filter %d invert %d scale %.9g mapping (%.9g, %.9g, %.9g, %.9g)\n", k, t.xres, t.yres, t.channels,
+                            t.wrap, t.filter, t.invert, t.scale, t.su, t.sv, t.du, t.dv);
+            }
+            for (int i = 0; i < sd->scene.n_quads; ++i)
+                if (tx.quad_texture[i]) std::printf("rectangle %d: texture %d\n", i, tx.quad_texture[i] - 1);
+            for (int i = 0; tx.tri_texture && i < sd->scene.n_triangles; ++i)
+                if (tx.tri_texture[i])
+                    std::printf("triangle %d: texture %d uv (%.9g, %.9g) (%.9g, %.9g) (%.9g, %.9g)\n", i, tx.tri_texture[i] - 1, tx.tri_uv[6 * i], tx.tri_uv[6 * i + 1],
+                                tx.tri_uv[6 * i + 2], tx.tri_uv[6 * i + 3], tx.tri_uv[6 * i + 4], tx.tri_uv[6 * i + 5]);
+        }
         if (parseOnly) return 0;
         auto integrator = vspg::CreateIntegrator(*sd, device);
         std::printf("%s\n", integrator->ToString().c_str());

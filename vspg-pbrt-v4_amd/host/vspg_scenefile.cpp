@@ -107,6 +107,7 @@ struct GraphicsState {
     float Le[3] = {0, 0, 0};
     bool twoSided = false;
     bool reverseOrientation = false;
+    int texture = 0;                  // Material "diffuse" "texture reflectance" "name": 0 = none, k = texture k - 1 replaces Kd
     bool interfaceMaterial = false;   // Material "interface" (also "none", ""): no BSDF, the surface only separates media (scene.cpp:1340)
     std::string insideMedium, outsideMedium;
 };
@@ -144,6 +145,8 @@ class Parser {
     std::vector<VspgQuad> quads;
     std::vector<VspgSphere> spheres;
     std::vector<MediumNames> quadMedia, sphereMedia, triMedia;   // per rectangle / sphere / triangle
+    std::map<std::string, int> textures;   // Texture "name": its binding value (index + 1)
+    std::vector<int> quadTexture;          // per rectangle
 
     [[noreturn]] void fail(const std::string &msg) const {
         const int line = pos < tok.size() ? tok[pos].line : (tok.empty() ? 0 : tok.back().line);
@@ -243,10 +246,22 @@ class Parser {
         } else if (d == "Integrator") {
             sd->integratorName = str();
             sd->integratorParams = params_with_bare_bools();
+        } else if (d == "Option" && pos < tok.size() && tok[pos].kind == Token::String && tok[pos].text == "bool disabletexturefiltering") {
+            // Options->disableTextureFiltering (options.h): every texture lookup reads level 0 -- the only evaluation this build has
+            ++pos;
+            const bool br = pos < tok.size() && tok[pos].kind == Token::Open;
+            if (br) ++pos;
+            if (pos >= tok.size() || tok[pos].kind != Token::Word || (tok[pos].text != "true" && tok[pos].text != "false")) fail("Option \"bool disabletexturefiltering\": expected true or false");
+            sd->disableTextureFiltering = tok[pos++].text == "true";
+            if (br) { if (pos >= tok.size() || tok[pos].kind != Token::Close) fail("expected ]"); ++pos; }
         } else if (d == "Option" || d == "ColorSpace") {
             std::string what = d;
             while (pos < tok.size() && tok[pos].kind != Token::Word) what += " " + tok[pos++].text;
             sd->warnings.push_back("ignored: " + what);
+        } else if (d == "Texture") {
+            const std::string name = str(), type = str(), cls = str();
+            ParameterDictionary p = params_with_bare_bools();
+            texture(name, type, cls, p);
         } else if (d == "WorldBegin") {
             if (!haveCamera) fail("WorldBegin before Camera");
             world = true;
@@ -331,8 +346,15 @@ class Parser {
         }
         if (type != "diffuse") fail("Material \"" + type + "\": only \"diffuse\" and \"interface\" are inside this build's scope");
         gs.interfaceMaterial = false;
+        gs.texture = 0;
         float kd[3] = {0.5f, 0.5f, 0.5f};
-        if (!p.GetOneRGB("reflectance", kd) && p.Has("reflectance")) { const float f = p.GetOneFloat("reflectance", 0.5f); kd[0] = kd[1] = kd[2] = f; }
+        if (p.Has("texture reflectance")) {  // a named spectrum texture (Texture "name" "spectrum" "imagemap") replaces the constant
+            const std::string tname = p.GetOneString("texture reflectance", "");
+            auto it = textures.find(tname);
+            if (it == textures.end()) fail("Material \"diffuse\": texture \"" + tname + "\" is not defined (a \"spectrum\" \"imagemap\" Texture)");
+            if (p.Has("reflectance")) fail("Material \"diffuse\": \"reflectance\" is given twice (a value and a texture)");
+            gs.texture = it->second;
+        } else if (!p.GetOneRGB("reflectance", kd) && p.Has("reflectance")) { const float f = p.GetOneFloat("reflectance", 0.5f); kd[0] = kd[1] = kd[2] = f; }
         (void)p.GetOneString("type", "");
         p.ReportUnused();
         std::memcpy(gs.Kd, kd, sizeof kd);
@@ -528,7 +550,47 @@ class Parser {
         for (int k = 0; k < 3; ++k) il.L[k] = L[k] * sc;
         sd->scene.n_infinite_lights++;
     }
-    void add_triangle(const float *a, const float *b, const float *c) {
+    // Texture "name" "spectrum" "imagemap" (SpectrumImageTexture::Create, textures.cpp; TextureMapping2D::Create "uv"; include/vspg.h
+    // VspgTexture): the image by the host Image layer, everything else as the reference names and defaults it
+    void texture(const std::string &name, const std::string &type, const std::string &cls, ParameterDictionary &p) {
+        if (type == "float") fail("Texture \"" + name + "\": \"float\" textures are outside this build's scope (\"spectrum\" \"imagemap\" on a diffuse reflectance only)");
+        if (type != "spectrum") fail("Texture \"" + name + "\": texture type \"" + type + "\" is outside this build's scope (\"spectrum\" only)");
+        if (cls != "imagemap") fail("directive \"Texture\" with class \"" + cls + "\" is outside this build's scope (Texture \"" + name + "\": \"imagemap\" only)");
+        if (sd->textures.n_textures >= VSPG_MAX_TEXTURES) fail("more than " + std::to_string(VSPG_MAX_TEXTURES) + " textures");
+        const std::string mapping = p.GetOneString("mapping", "uv");
+        if (mapping != "uv") fail("Texture \"" + name + "\": mapping \"" + mapping + "\" is outside this build's scope (\"uv\" only)");
+        std::string fn = p.GetOneString("filename", "");
+        const std::string filter = p.GetOneString("filter", "bilinear"), wrap = p.GetOneString("wrap", "repeat");
+        VspgTexture t;
+        std::memset(&t, 0, sizeof t);
+        t.scale = p.GetOneFloat("scale", 1.f);
+        t.invert = p.GetOneBool("invert", false) ? 1 : 0;
+        t.su = p.GetOneFloat("uscale", 1.f); t.sv = p.GetOneFloat("vscale", 1.f);
+        t.du = p.GetOneFloat("udelta", 0.f); t.dv = p.GetOneFloat("vdelta", 0.f);
+        (void)p.GetOneFloat("maxanisotropy", 8.f);   // read and ignored: level 0 has no ellipse
+        (void)p.GetOneString("encoding", "sRGB");    // read and ignored: float images carry linear values
+        p.ReportUnused();
+        if (filter == "point") t.filter = VSPG_TEXFILTER_POINT;
+        else if (filter == "bilinear" || filter == "trilinear" || filter == "ewa" || filter == "EWA") t.filter = VSPG_TEXFILTER_BILINEAR;  // all Bilerp(0, st) at level 0
+        else fail("Texture \"" + name + "\": filter \"" + filter + "\" unknown");
+        if (wrap == "repeat") t.wrap = VSPG_TEXWRAP_REPEAT;
+        else if (wrap == "clamp") t.wrap = VSPG_TEXWRAP_CLAMP;
+        else if (wrap == "black") t.wrap = VSPG_TEXWRAP_BLACK;
+        else fail("Texture \"" + name + "\": wrap mode \"" + wrap + "\" is outside this build's scope (\"repeat\", \"clamp\", \"black\")");
+        if (fn.empty()) fail("Texture \"" + name + "\": \"imagemap\" needs a \"filename\"");
+        const size_t dot = fn.find_last_of('.');
+        const std::string ext = dot == std::string::npos ? "" : fn.substr(dot);
+        if (ext != ".pfm" && ext != ".exr") fail("Texture \"" + name + "\": " + fn + ": 8-bit images and colour encodings are outside this build's scope (.pfm / .exr float images only)");
+        if (fn[0] != '/' && !baseDir.empty()) fn = baseDir + "/" + fn;  // ResolveFilename
+        const Image img = ReadImage(fn);
+        const bool rgb = img.ChannelIndex("R") >= 0 && img.ChannelIndex("G") >= 0 && img.ChannelIndex("B") >= 0;
+        if (!rgb && img.ChannelIndex("Y") < 0) fail(fn + ": a texture image needs R, G and B channels, or Y");
+        t.xres = img.xres; t.yres = img.yres; t.channels = rgb ? 3 : 1;
+        sd->texturePixels.push_back(rgb ? img.Gather({"R", "G", "B"}, fn) : img.Gather({"Y"}, fn));
+        sd->textures.textures[sd->textures.n_textures++] = t;   // (finish() points `pixels` at the stored image)
+        textures[name] = sd->textures.n_textures;
+    }
+    void add_triangle(const float *a, const float *b, const float *c, const float *uva = nullptr, const float *uvb = nullptr, const float *uvc = nullptr) {
         if (gs.areaLight) fail("emissive triangles are outside this build's scope (emission lives on rectangles: use a planar \"bilinearmesh\" patch)");
         const float *v[3] = {a, b, c};
         for (int i = 0; i < 3; ++i)
@@ -538,6 +600,11 @@ class Parser {
         // (shapes.h:934-936) -- the vertices above are already in render space, as the reference's TriangleMesh keeps them
         sd->triFlags.push_back((gs.interfaceMaterial ? VSPG_TRI_INTERFACE : 0) | (gs.reverseOrientation != swaps_handedness(gs.ctm) ? VSPG_TRI_FLIP_NORMAL : 0));
         triMedia.push_back(MediumNames{gs.insideMedium, gs.outsideMedium});
+        sd->triTexture.push_back(gs.texture);
+        static const float def[3][2] = {{0, 0}, {1, 0}, {1, 1}};   // Triangle::InteractionFromIntersection's default uv
+        const float *uv[3] = {uva ? uva : def[0], uvb ? uvb : def[1], uvc ? uvc : def[2]};
+        for (int i = 0; i < 3; ++i)
+            for (int k = 0; k < 2; ++k) sd->triUv.push_back(uv[i][k]);
     }
     static bool swaps_handedness(const M4 &m) {  // Transform::SwapsHandedness (util/transform.cpp): det of the upper 3x3 < 0
         const float det = m.m[0][0] * (m.m[1][1] * m.m[2][2] - m.m[1][2] * m.m[2][1]) - m.m[0][1] * (m.m[1][0] * m.m[2][2] - m.m[1][2] * m.m[2][0]) +
@@ -559,6 +626,8 @@ class Parser {
             if (gs.areaLight)
                 fail("emissive spheres are not read from scene files yet -- build the scene through the C-ABI (VspgScene.sphere_Le / sphere_two_sided; "
                      "add_sphere_light in the Python binding)");
+            if (gs.texture)
+                fail("Shape \"sphere\" with a textured material (\"texture reflectance\"): textures on spheres are outside this build's scope");
             if (spheres.size() >= VSPG_MAX_SPHERES) fail("more than " + std::to_string(VSPG_MAX_SPHERES) + " spheres");
             VspgSphere sp;
             std::memset(&sp, 0, sizeof sp);
@@ -574,7 +643,8 @@ class Parser {
             return;
         }
         std::vector<float> P = p.GetPoint3Array("P");
-        if (p.Has("N") || p.Has("uv") || p.Has("S")) fail("shading normals / tangents / (u,v) on meshes are outside this build's scope");
+        if (p.Has("N") || p.Has("S")) fail("shading normals / tangents (\"N\", \"S\") on meshes are outside this build's scope");
+        const std::vector<float> uv = p.GetFloatArray("uv");   // "point2 uv": one pair per vertex
         std::vector<float> W(P.size());
         for (size_t i = 0; i + 2 < P.size(); i += 3) xf_point(gs.ctm, &P[i], &W[i]);
         if (type == "bilinearmesh") {
@@ -583,6 +653,13 @@ class Parser {
             if (idx.empty()) idx = {0, 1, 2, 3};
             if (P.size() % 3) fail("bilinearmesh: \"P\" must hold whole points (a multiple of three floats)");
             if (idx.size() != 4 || W.size() < 12) fail("bilinearmesh: one patch of four points is supported");
+            static const float patchUv[4][2] = {{0, 0}, {1, 0}, {0, 1}, {1, 1}};   // BilinearPatch's default parametrisation
+            if (!uv.empty()) {
+                bool def = uv.size() == 2 * (W.size() / 3);
+                for (int k = 0; def && k < 4; ++k)
+                    def = idx[k] >= 0 && 2 * (size_t)idx[k] + 1 < uv.size() && uv[2 * idx[k]] == patchUv[k][0] && uv[2 * idx[k] + 1] == patchUv[k][1];
+                if (!def) fail("bilinearmesh: only the default \"uv\" (0,0) (1,0) (0,1) (1,1) is inside this build's scope");
+            }
             const int nv = (int)(W.size() / 3);
             for (int k = 0; k < 4; ++k)
                 if (idx[k] < 0 || idx[k] >= nv) fail("bilinearmesh: vertex index out of range");
@@ -605,10 +682,11 @@ class Parser {
                 q.reverse_orientation = gs.reverseOrientation != swaps_handedness(gs.ctm);
                 q.material = gs.interfaceMaterial ? VSPG_MATERIAL_INTERFACE : VSPG_MATERIAL_DIFFUSE;
                 quads.push_back(q);
+                quadTexture.push_back(gs.texture);
                 quadMedia.push_back(MediumNames{gs.insideMedium, gs.outsideMedium});
             } else {
-                add_triangle(p00, p10, p11);
-                add_triangle(p00, p11, p01);
+                add_triangle(p00, p10, p11, patchUv[0], patchUv[1], patchUv[3]);
+                add_triangle(p00, p11, p01, patchUv[0], patchUv[3], patchUv[2]);
             }
         } else if (type == "trianglemesh") {
             // (a triangle's orientation -- reverseOrientation ^ transformSwapsHandedness, shapes.h:934-936 -- travels as a flag: only a
@@ -619,9 +697,11 @@ class Parser {
             const int nv = (int)(W.size() / 3);
             if (idx.empty()) { if (nv != 3) fail("trianglemesh without indices must have exactly three points"); idx = {0, 1, 2}; }
             if (idx.size() % 3) fail("trianglemesh: indices come in threes");
+            if (!uv.empty() && uv.size() != 2 * (size_t)nv) fail("trianglemesh: \"uv\" must hold one pair per vertex");
             for (size_t i = 0; i < idx.size(); i += 3) {
                 for (int k = 0; k < 3; ++k) if (idx[i + k] < 0 || idx[i + k] >= nv) fail("trianglemesh: vertex index out of range");
-                add_triangle(&W[3 * idx[i]], &W[3 * idx[i + 1]], &W[3 * idx[i + 2]]);
+                if (uv.empty()) add_triangle(&W[3 * idx[i]], &W[3 * idx[i + 1]], &W[3 * idx[i + 2]]);
+                else add_triangle(&W[3 * idx[i]], &W[3 * idx[i + 1]], &W[3 * idx[i + 2]], &uv[2 * idx[i]], &uv[2 * idx[i + 1]], &uv[2 * idx[i + 2]]);
             }
         } else {
             fail("Shape \"" + type + "\": only \"bilinearmesh\", \"trianglemesh\" and \"sphere\" are inside this build's scope");
@@ -685,6 +765,15 @@ class Parser {
             s.tri_kd = sd->triKd.data();
             s.tri_flags = sd->triFlags.data();
         }
+        // image textures: the record beside the scene (vspg_renderer_create_textured)
+        VspgSceneTextures &tx = sd->textures;
+        for (int k = 0; k < tx.n_textures; ++k) tx.textures[k].pixels = sd->texturePixels[k].data();
+        for (int i = 0; i < s.n_quads; ++i) tx.quad_texture[i] = quadTexture[i];
+        bool triTextured = false;
+        for (int v : sd->triTexture) triTextured = triTextured || v != 0;
+        if (triTextured) { tx.tri_texture = sd->triTexture.data(); tx.tri_uv = sd->triUv.data(); }
+        if (tx.n_textures > 0 && !sd->disableTextureFiltering)
+            sd->warnings.push_back("textures are evaluated at level 0 (point or bilinear), as under Option \"bool disabletexturefiltering\" true");
     }
 };
 
@@ -708,7 +797,8 @@ std::unique_ptr<Integrator> CreateIntegrator(const SceneDescription &sd, int dev
         ResolvePixelBounds(own);
         b[0] = own.boundsX0; b[1] = own.boundsY0; b[2] = own.boundsX1; b[3] = own.boundsY1;
     }
-    auto integrator = Integrator::Create(sd.integratorName, sd.integratorParams, sd.scene, sd.xres, sd.yres, sd.pixelSamples, sd.seed, device);
+    auto integrator = Integrator::Create(sd.integratorName, sd.integratorParams, sd.scene, sd.xres, sd.yres, sd.pixelSamples, sd.seed, device,
+                                         sd.textures.n_textures > 0 ? &sd.textures : nullptr);
     integrator->SetPixelBounds(b[0], b[1], b[2], b[3]);
     for (const SceneDescription::EnvImage &e : sd.envImages) integrator->SetEnvironmentImage(e.light, e.rgb, e.res, e.renderFromLight);
     for (const SceneDescription::LightImage &l : sd.lightImages) integrator->SetLightImage(l.slot, l.pixels, l.xres, l.yres, l.channels);

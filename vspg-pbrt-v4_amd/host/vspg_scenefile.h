@@ -8,8 +8,12 @@
 // unused-parameter error are the reference's.
 //
 // Directives: LookAt, Camera "perspective" (fov), Sampler (pixelsamples, seed), PixelFilter "box", Film "rgb"
-// (xresolution, yresolution, filename, savefp16, cropwindow, pixelbounds), Integrator, Option (ignored), ColorSpace (ignored), WorldBegin, AttributeBegin/End,
-// Identity, Translate, Scale, Rotate, Transform, ConcatTransform, ReverseOrientation, Material "diffuse" (reflectance) / "interface",
+// (xresolution, yresolution, filename, savefp16, cropwindow, pixelbounds), Integrator, Option (ignored but "disabletexturefiltering"), ColorSpace (ignored), WorldBegin, AttributeBegin/End,
+// Identity, Translate, Scale, Rotate, Transform, ConcatTransform, ReverseOrientation, Material "diffuse" (reflectance: rgb, float, or
+// "texture reflectance" "name") / "interface", Texture "name" "spectrum" "imagemap" (filename: .pfm / .exr with R, G, B or Y; filter, wrap,
+// scale, invert, mapping "uv", uscale, vscale, udelta, vdelta; maxanisotropy and encoding are read and ignored; other classes, other
+// mappings and "float" textures are refused by name; a textured material on Shape "sphere" is refused by name; "uv" on trianglemesh,
+// the default uv only on bilinearmesh; a scene with textures that does not set Option "bool disabletexturefiltering" true gets a warning),
 // MakeNamedMaterial / NamedMaterial ("diffuse", "interface"), AreaLightSource "diffuse" (L, scale, twosided), LightSource "infinite"
 // (L, scale; or "filename": an equal-area octahedral environment map, .exr / .pfm, square, with R, G, B -- the CTM in effect is the
 // light's transform; no "portal", no "illuminance") / "distant" (L, scale, from, to) / "point" (I, scale, power, from under the CTM: a
@@ -57,6 +61,13 @@ struct SceneDescription {
         std::vector<float> pixels;
     };
     std::vector<LightImage> lightImages;
+    // Texture "name" "spectrum" "imagemap" and the surfaces that `Material "diffuse" "texture reflectance" "name"` binds them to: the
+    // record vspg_renderer_create_textured takes beside the scene (CreateIntegrator hands it over); its pointers refer to the vectors here
+    VspgSceneTextures textures = {};
+    std::vector<std::vector<float>> texturePixels;   // per texture, xres * yres * channels floats, top row first
+    std::vector<int32_t> triTexture;                 // per triangle: 0 = none, k = texture k - 1
+    std::vector<float> triUv;                        // per triangle: uv0, uv1, uv2 (the mesh's "uv" or the default)
+    bool disableTextureFiltering = false;            // Option "bool disabletexturefiltering": what the library evaluates either way
     std::string integratorName = "volpath";
     ParameterDictionary integratorParams;
     int xres = 1280, yres = 720;         // Film defaults (film.cpp)
