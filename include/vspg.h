@@ -94,7 +94,8 @@ typedef struct VspgSphere {
 /* Pinhole camera: raster point (x,y) -> camera-space point (sx*x+ox, sy*y+oy, 1),
  * normalised, then rotated into render space by the orthonormal frame (right, up, fwd).
  * Replaces PerspectiveCamera::GenerateRayDifferential (src/pbrt/cameras.cpp:435-447)
- * for lensRadius == 0.  Fill with vspg_camera_look_at(). */
+ * for lensRadius == 0.  Fill with vspg_camera_look_at().  A renderer is created with this pinhole; a thin lens, an
+ * orthographic or a spherical camera is set on the live renderer (vspg_renderer_set_camera, below), which reads the same record. */
 typedef struct VspgCamera {
     float origin[3];
     float right[3], up[3], fwd[3];
@@ -600,7 +601,7 @@ int vspg_renderer_get_arithmetic(VspgRenderer *r);
  * The same contract covers PATHS: a one-sample wave of the barrier-free workgroup kernel may also leave the paths that were in flight
  * when its tiles ran out suspended beside the film; the next such wave resumes them, and until then the film, the statistics and
  * the counters lack them as well as the parked samples.  vspg_flush and every accessor named above -- and vspg_get_counters,
- * vspg_reset_counters, vspg_renderer_set_arithmetic, the buffer setters, the due update of vspg_post_process_step -- finish them
+ * vspg_reset_counters, vspg_renderer_set_arithmetic, vspg_renderer_set_camera, the buffer setters, the due update of vspg_post_process_step -- finish them
  * first (one short launch on the call's stream); vspg_renderer_destroy drops them.  VSPG_WG3_CARRY=0 in the environment (read
  * per wave) makes every wave finish its own paths.
  * vspg_film_error_enqueue and vspg_film_resolve (below) read the film and belong to this list: each finishes parked samples and
@@ -1017,6 +1018,44 @@ int vspg_renderer_set_texture_image(VspgRenderer *r, int texture_index, const fl
  * dropped). */
 #define VSPG_TEXTURE_EVAL_OUT 8
 int vspg_texture_eval_batch(VspgRenderer *r, int n, const int32_t *prim /*n*/, const float *hit /*3n*/, float *out /*8n*/, void *stream);
+
+/* ---- Camera models: thin-lens perspective, orthographic, spherical (csrc/vspg_camera.h) -----------------------------------------
+ * GenerateRay of PerspectiveCamera, OrthographicCamera and SphericalCamera (src/pbrt/cameras.cpp:410-433, :290-312, :616-636).
+ * VspgScene keeps its size and VSPG_ABI_VERSION stays 7: a renderer is created with the pinhole perspective its VspgCamera describes,
+ * and the model is set on the live renderer.  A VspgCamera serves every model: the frame and origin place the camera; sx, ox, sy, oy
+ * map a raster point to the screen window (perspective: at camera depth 1; orthographic: in camera-space units on the plane z = 0;
+ * spherical: not read).  Out of scope: RealisticCamera, motion blur (the time sample is drawn and unused), ray differentials, We /
+ * SampleWi / PDF_We, projective transforms, a second camera per renderer. */
+enum { VSPG_CAMERA_PERSPECTIVE = 0, VSPG_CAMERA_ORTHOGRAPHIC = 1,
+       VSPG_CAMERA_SPHERICAL_EQUALAREA = 2, VSPG_CAMERA_SPHERICAL_EQUIRECT = 3 };
+typedef struct VspgCameraModel { int32_t model; float lens_radius; float focal_distance; } VspgCameraModel;  /* zeroed = today's pinhole */
+/* Replaces the camera of a live renderer; model NULL = the pinhole perspective.  It belongs to the calls that finish parked samples
+ * and suspended paths first (vspg_flush's list above) -- they end under the camera they started with --, then synchronises `stream`
+ * and copies the camera into the scene record.  It CLEARS NOTHING: the film, the image-space statistics, the VSP buffer, TrBuffer,
+ * guiding fields, counters and the error log keep their contents, which were gathered under the old camera; vspg_film_clear and its
+ * peers are the caller's business.  A model other than the pinhole perspective is served by the full-scene kernels
+ * (vspg_renderer_kernel_name tells); perspective with lens_radius == 0 is exactly the pinhole: the same kernel, the same film bits as
+ * without the call.  A spherical model ignores both lens fields, as the reference does.
+ * VSPG_EINVAL, with the renderer exactly as it was: a null renderer or camera; an unknown model; a non-finite frame, origin or
+ * affine term; lens_radius negative or non-finite; focal_distance not finite and positive while lens_radius > 0 (perspective and
+ * orthographic). */
+int vspg_renderer_set_camera(VspgRenderer *r, const VspgCamera *cam, const VspgCameraModel *model /* NULL = pinhole perspective */, void *stream);
+/* vspg_camera_look_at with the model's screen window (cameras.cpp:375-404, :474-503).  Host only.  The default window is
+ * [-a, a] x [-1, 1] for a = frame_aspect > 1, else [-1, 1] x [-1/a, 1/a]; frame_aspect 0 = xres / yres ("frameaspectratio");
+ * screen_window {xmin, xmax, ymin, ymax} overrides it ("screenwindow").  Perspective scales the window by tan(fov / 2); orthographic
+ * takes it as it is (fov_degrees is not read); spherical fills the frame and origin only (sx = ox = sy = oy = 0).  Raster y points
+ * down.  With a NULL window, frame_aspect 0 and the perspective model the result equals vspg_camera_look_at's bit for bit.
+ * VSPG_EINVAL: vspg_camera_look_at's refusals, an unknown model, a frame_aspect that is negative or not finite, a window with a
+ * non-finite value. */
+int vspg_camera_look_at_window(VspgCamera *cam, int model, const float eye[3], const float look[3], const float up[3],
+                               float fov_degrees, const float screen_window[4] /* or NULL */, float frame_aspect /* 0 = xres/yres */, int xres, int yres);
+/* Batch driver of the camera ray (parity tests): the render-space ray start_path gives sample sample_index[i] of pixel
+ * pixel_xy[2i..] under the renderer's camera -- camera_generate_ray (csrc/vspg_camera.h), the function the full-scene kernels call.
+ * u: per element the filter's and the lens's two variates (4n floats), or NULL: the renderer's own sampler draws them in its order
+ * (wavelength, filter 2, time, lens 2).  out_o, out_d: 3n floats each.  HOST arrays.
+ * VSPG_EINVAL: a null argument, a pixel outside the frame, a negative sample index. */
+int vspg_camera_ray_batch(VspgRenderer *r, int n, const int32_t *pixel_xy, const int32_t *sample_index,
+                          const float *u /* 4n: filter u0 u1, lens u0 u1; NULL = the renderer's sampler */, float *out_o, float *out_d, void *stream);
 
 #ifdef __cplusplus
 }

@@ -57,6 +57,14 @@ class VspgCamera(C.Structure):
                 ("sx", C.c_float), ("ox", C.c_float), ("sy", C.c_float), ("oy", C.c_float)]
 
 
+CAMERA_PERSPECTIVE, CAMERA_ORTHOGRAPHIC, CAMERA_SPHERICAL_EQUALAREA, CAMERA_SPHERICAL_EQUIRECT = 0, 1, 2, 3   # VSPG_CAMERA_*
+
+
+class VspgCameraModel(C.Structure):
+    """The camera model of vspg_renderer_set_camera; zeroed = the pinhole perspective."""
+    _fields_ = [("model", C.c_int32), ("lens_radius", C.c_float), ("focal_distance", C.c_float)]
+
+
 class VspgMedium(C.Structure):
     _fields_ = [("type", C.c_int32), ("sigma_a", f3), ("sigma_s", f3), ("g", C.c_float),
                 ("Le", f3), ("nx", C.c_int32), ("ny", C.c_int32), ("nz", C.c_int32),
@@ -348,6 +356,9 @@ SYMBOLS = [
     ("vspg_light_pdf_batch", C.c_int, [_vp, C.c_int, C.c_int, _P(C.c_float), _P(C.c_float), _P(C.c_float), _P(C.c_float), _P(C.c_float), _vp]),
     ("vspg_renderer_set_texture_image", C.c_int, [_vp, C.c_int, _P(C.c_float), C.c_int, C.c_int, C.c_int, _vp]),
     ("vspg_texture_eval_batch", C.c_int, [_vp, C.c_int, _P(C.c_int32), _P(C.c_float), _P(C.c_float), _vp]),
+    ("vspg_renderer_set_camera", C.c_int, [_vp, _P(VspgCamera), _P(VspgCameraModel), _vp]),
+    ("vspg_camera_look_at_window", C.c_int, [_P(VspgCamera), C.c_int, f3, f3, f3, C.c_float, _P(C.c_float), C.c_float, C.c_int, C.c_int]),
+    ("vspg_camera_ray_batch", C.c_int, [_vp, C.c_int, _P(C.c_int32), _P(C.c_int32), _P(C.c_float), _P(C.c_float), _P(C.c_float), _vp]),
     ("vspg_renderer_get_tr_buffer", C.c_int, [_vp, _P(C.c_float), _P(C.c_int32), _vp]),
     ("vspg_renderer_set_tr_buffer", C.c_int, [_vp, _P(C.c_float), _vp]),
     ("vspg_renderer_set_guiding_field", C.c_int, [_vp, _P(VspgField), _P(VspgField), _vp]),
@@ -400,6 +411,17 @@ def fog_box_scene(xres, yres):
     s = VspgScene()
     _check(lib, lib.vspg_scene_fog_box(C.byref(s), xres, yres))
     return s
+
+
+def camera_look_at_window(model, eye, look, up, fov, xres, yres, screen_window=None, frame_aspect=0.0):
+    """A VspgCamera for camera model `model` (CAMERA_*): LookAt and the model's screen window (vspg_camera_look_at_window).
+    screen_window: (xmin, xmax, ymin, ymax) or None = the default window of frame_aspect (0 = xres / yres)."""
+    lib = load()
+    cam = VspgCamera()
+    sw = None if screen_window is None else (C.c_float * 4)(*[float(v) for v in screen_window])
+    _check(lib, lib.vspg_camera_look_at_window(C.byref(cam), int(model), f3(*eye), f3(*look), f3(*up), float(fov), sw, float(frame_aspect),
+                                               int(xres), int(yres)))
+    return cam
 
 
 def procedural_cloud_density(n, seed=5, shape="noise"):
@@ -1160,6 +1182,33 @@ class Renderer:
         img, xres, yres, channels = texture_image_source(image)
         _check(self.lib, self.lib.vspg_renderer_set_texture_image(self.h, int(index), img.ctypes.data_as(_P(C.c_float)), xres, yres, channels,
                                                                  _vp(stream or 0)))
+
+    def set_camera(self, cam, model=0, lens_radius=0.0, focal_distance=1e6, stream=None):
+        """Replace the camera of the live renderer (vspg_renderer_set_camera): a VspgCamera (camera_look_at_window) and the model
+        CAMERA_* with its thin lens; model=None passes a null record (the pinhole perspective).  Nothing is cleared: film, statistics
+        and buffers keep what they gathered under the old camera."""
+        m = None if model is None else C.byref(VspgCameraModel(int(model), float(lens_radius), float(focal_distance)))
+        _check(self.lib, self.lib.vspg_renderer_set_camera(self.h, C.byref(cam), m, _vp(stream or 0)))
+
+    def camera_ray_batch(self, pixel_xy, sample_index, u=None):
+        """The render-space camera ray (origins [n, 3], directions [n, 3]) of sample sample_index[i] of pixel pixel_xy[i], as the path
+        kernels generate it (vspg_camera_ray_batch).  u: [n, 4] filter and lens variates, or None = the renderer's own sampler."""
+        import numpy as np
+        pix = np.ascontiguousarray(pixel_xy, dtype=np.int32).reshape(-1, 2)
+        si = np.ascontiguousarray(sample_index, dtype=np.int32).reshape(-1)
+        n = si.shape[0]
+        if pix.shape[0] != n:
+            raise ValueError("camera_ray_batch: %d pixels but %d sample indices" % (pix.shape[0], n))
+        fp = _P(C.c_float)
+        uu = None
+        if u is not None:
+            uu = np.ascontiguousarray(u, dtype=np.float32).reshape(-1, 4)
+            if uu.shape[0] != n:
+                raise ValueError("camera_ray_batch: %d pixels but %d variate rows" % (n, uu.shape[0]))
+        o, d = np.empty((n, 3), dtype=np.float32), np.empty((n, 3), dtype=np.float32)
+        _check(self.lib, self.lib.vspg_camera_ray_batch(self.h, n, pix.ctypes.data_as(_P(C.c_int32)), si.ctypes.data_as(_P(C.c_int32)),
+                                                       None if uu is None else uu.ctypes.data_as(fp), o.ctypes.data_as(fp), d.ctypes.data_as(fp), None))
+        return o, d
 
     def texture_eval_batch(self, prim, hit):
         """Per (primitive, three floats of a vertex): (u, v), (s, t) after the flip, R (3) and has_lobes, as the path kernels evaluate

@@ -177,9 +177,9 @@ __global__ __launch_bounds__(kBlock, kWavesPerSimd) void k_render_wave(const DSc
                 s = first_sample;
                 if (win_has(win, px, py) && s < wave_end) {
                     if (single_sample)
-                        start_path(S, vsp_buf, vsp_ready, px, py, jump, sampler, st, &ch, isg);
+                        start_path<!Medium::kSimpleScene>(S, vsp_buf, vsp_ready, px, py, jump, sampler, st, &ch, isg);
                     else
-                        start_path(S, vsp_buf, vsp_ready, px, py, s, sampler, st, &ch, isg);
+                        start_path<!Medium::kSimpleScene>(S, vsp_buf, vsp_ready, px, py, s, sampler, st, &ch, isg);
                     has = true;
                     if constexpr (GUIDED) load_contribution_estimate(S, px, py, st);
                     if constexpr (TRAIN) {
@@ -214,7 +214,7 @@ __global__ __launch_bounds__(kBlock, kWavesPerSimd) void k_render_wave(const DSc
         if (finished) {
             s += S.shard_count > 1 ? S.shard_count : 1;
             if (!TRAIN && s < wave_end) {
-                start_path(S, vsp_buf, vsp_ready, px, py, s, sampler, st, &ch, isg);  // next sample of the same pixel
+                start_path<!Medium::kSimpleScene>(S, vsp_buf, vsp_ready, px, py, s, sampler, st, &ch, isg);  // next sample of the same pixel
                 if constexpr (GUIDED) load_contribution_estimate(S, px, py, st);
             } else {
                 has = false;
@@ -984,6 +984,7 @@ static ChoiceFacts choice_facts(const VspgRenderer *r) {
     f.guided = wants_guiding(r->prm), f.rrguiding = r->prm.rrguiding != 0, f.training = r->training;
     f.tr_calc = r->hscene.tr_calc != 0, f.has_temperature = r->hscene.temperature != nullptr;
     f.resampling = r->prm.vspsamplingmethod == VSPG_VSP_RESAMPLING;
+    f.camera_general = camera_model_general(VspgCameraModel{r->hscene.cam_model, r->hscene.cam_lens_radius, r->hscene.cam_focal_distance});
     return f;
 }
 // The samples a one-sample wg2 launch parked are resolved by the next such launch; anything else that reads or writes the film or
@@ -2527,6 +2528,66 @@ int vspg_texture_eval_batch(VspgRenderer *r, int n, const int32_t *prim, const f
     HIPCHK(hipGetLastError());
     HIPCHK(hipMemcpyAsync(out, dout.p, (size_t)n * VSPG_TEXTURE_EVAL_OUT * 4, hipMemcpyDeviceToHost, s));
     HIPCHK(hipStreamSynchronize(s));  // (dev_prim is pageable and dropped on return)
+    return 0;
+}
+
+int vspg_renderer_set_camera(VspgRenderer *r, const VspgCamera *cam, const VspgCameraModel *model, void *stream) {
+    // every refusal comes before anything of the renderer changes
+    if (!r) return fail(VSPG_EINVAL, "null renderer");
+    if (const int rc = camera_refusal(cam, model)) return rc;
+    const VspgCameraModel rec = camera_model_record(model);
+    if (r->arith != VSPG_ARITH_EXACT) {  // (the tolerance modes cover fewer kernels: the camera must not move the renderer out of them)
+        ChoiceFacts f = choice_facts(r);
+        f.camera_general = camera_model_general(rec);
+        const KernelChoice c = choose_kernel(f, read_choice_env());
+        if (!c.arith_covered)
+            return fail(VSPG_ESCOPE, "the tolerance-mode instantiations do not cover " + kernel_name(c) + ", which this camera needs: set exact arithmetic first");
+    }
+    HIPCHK(hipSetDevice(r->cfg.device));
+    hipStream_t s = (hipStream_t)stream;
+    if (const int rc = flush_parked_samples(r, s)) return rc;  // (samples and paths in flight end under the camera they started with)
+    HIPCHK(hipStreamSynchronize(s));  // no launch may still read the old camera
+    r->scene.camera = *cam;
+    r->hscene.cam = *cam;
+    r->hscene.cam_model = rec.model;
+    r->hscene.cam_lens_radius = rec.lens_radius;
+    r->hscene.cam_focal_distance = rec.focal_distance;
+    // two pieces of the record: `cam` in its first 4 KB and the model at its end (a training renderer updates fields between them in
+    // place on the device: they are not the host copy's to overwrite)
+    HIPCHK(hipMemcpyAsync(reinterpret_cast<char *>(r->dscene) + offsetof(DScene, cam), &r->hscene.cam, sizeof r->hscene.cam, hipMemcpyHostToDevice, s));
+    const size_t tail = offsetof(DScene, cam_model);
+    HIPCHK(hipMemcpyAsync(reinterpret_cast<char *>(r->dscene) + tail, reinterpret_cast<const char *>(&r->hscene) + tail, sizeof(DScene) - tail,
+                          hipMemcpyHostToDevice, s));
+    HIPCHK(hipStreamSynchronize(s));
+    return 0;
+}
+
+int vspg_camera_ray_batch(VspgRenderer *r, int n, const int32_t *pixel_xy, const int32_t *sample_index, const float *u, float *out_o, float *out_d,
+                          void *stream) {
+    if (!r || n < 0 || (n > 0 && (!pixel_xy || !sample_index || !out_o || !out_d))) return fail(VSPG_EINVAL, "null argument");
+    if (n == 0) return 0;
+    for (int i = 0; i < n; ++i) {
+        const int x = pixel_xy[2 * (size_t)i], y = pixel_xy[2 * (size_t)i + 1];
+        if (x < 0 || x >= r->cfg.xres || y < 0 || y >= r->cfg.yres) return fail(VSPG_EINVAL, "pixel outside the frame");
+        if (sample_index[i] < 0) return fail(VSPG_EINVAL, "negative sample index");
+    }
+    HIPCHK(hipSetDevice(r->cfg.device));
+    hipStream_t s = (hipStream_t)stream;
+    DevBuf dp, ds, du, doo, dd;
+    HIPCHK(hipMalloc(&dp.p, (size_t)n * 8));
+    HIPCHK(hipMalloc(&ds.p, (size_t)n * 4));
+    if (u) HIPCHK(hipMalloc(&du.p, (size_t)n * 16));
+    HIPCHK(hipMalloc(&doo.p, (size_t)n * 12));
+    HIPCHK(hipMalloc(&dd.p, (size_t)n * 12));
+    HIPCHK(hipMemcpyAsync(dp.p, pixel_xy, (size_t)n * 8, hipMemcpyHostToDevice, s));
+    HIPCHK(hipMemcpyAsync(ds.p, sample_index, (size_t)n * 4, hipMemcpyHostToDevice, s));
+    if (u) HIPCHK(hipMemcpyAsync(du.p, u, (size_t)n * 16, hipMemcpyHostToDevice, s));
+    hipLaunchKernelGGL(k_camera_ray, dim3((n + kBlock - 1) / kBlock), dim3(kBlock), 0, s, r->dscene, n, (const int32_t *)dp.p, (const int32_t *)ds.p,
+                       (const float *)du.p, (float *)doo.p, (float *)dd.p);
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipMemcpyAsync(out_o, doo.p, (size_t)n * 12, hipMemcpyDeviceToHost, s));
+    HIPCHK(hipMemcpyAsync(out_d, dd.p, (size_t)n * 12, hipMemcpyDeviceToHost, s));
+    HIPCHK(hipStreamSynchronize(s));
     return 0;
 }
 

@@ -953,6 +953,11 @@ struct DScene {
     int32_t quad_tex[VSPG_MAX_QUADS];
     const float *tri_uv;
     DTexture tex[VSPG_MAX_TEXTURES];
+    // the camera model (vspg_camera.h; vspg_renderer_set_camera): cam_model = VSPG_CAMERA_*, and the thin lens of the perspective and
+    // orthographic cameras (cam_lens_radius 0 = none; a spherical camera holds 0 here).  A zeroed tail is the pinhole `cam` describes.
+    // Behind everything else: only start_path_common<true> reads here, and no scalar load of the rectangle-scene kernels moves.
+    int32_t cam_model;
+    float cam_lens_radius, cam_focal_distance;
 };
 // the length of the scene's light list (full-scene kernels): one line per light kind
 __host__ __device__ __forceinline__ int light_list_size(const DScene &S) { return S.n_lights + S.n_inf + S.n_point + S.n_sphere_lights; }

@@ -20,6 +20,7 @@ struct ChoiceFacts {  // what the decision reads of a renderer
     bool guided = false, rrguiding = false, training = false;            // guided: wants_guiding(prm)
     bool tr_calc = false, has_temperature = false;
     bool resampling = true;  // vspsamplingmethod == VSPG_VSP_RESAMPLING (else NDS / NDS+)
+    bool camera_general = false;  // the camera is not the pinhole perspective: another model, or lens_radius > 0 (vspg_camera.h)
 };
 struct ChoiceEnv {  // ... and of the process environment
     std::string kernel;           // VSPG_KERNEL=wg|lane|wf picks a path kernel where several serve a configuration (tests, A/B runs); empty == unset
@@ -70,9 +71,10 @@ inline KernelChoice choose_kernel(const ChoiceFacts &f, const ChoiceEnv &env) {
     // a scene of rectangles and area lights only, one medium filling it: what the workgroup kernel's specialised instantiations are built for
     // (HomogeneousMediumT::kSimpleScene).  Triangle hits carry a per-hit error bound the LDS pool record has no room for; medium boundaries,
     // interface materials and spheres are served by the full-scene code paths; so are power / BVH picks of a multi-light scene, and
-    // point and spot lights (sample_light<FULL> alone dispatches on them), and textured surfaces (vertex_setup<FULL> alone looks a texel up).
+    // point and spot lights (sample_light<FULL> alone dispatches on them), and textured surfaces (vertex_setup<FULL> alone looks a texel up),
+    // and every camera but the pinhole perspective (start_path_common<true> alone generates their rays).
     const bool simple = f.n_tris == 0 && f.n_inf == 0 && f.n_point == 0 && f.lightsampler == VSPG_LIGHTSAMPLER_UNIFORM && !f.has_boundaries && f.n_spheres == 0 &&
-                        f.n_textured == 0;
+                        f.n_textured == 0 && !f.camera_general;
     // guided renders over a homogeneous medium: the grey / zero-null-coefficient / rectangle-scene instantiation (the segment half of the
     // loop sheds the same per-channel work as the headline kernel's instantiation)
     const bool guided_grey_simple = hom && f.medium_grey && f.surfaces_grey && f.null_zero && simple && !env.no_grey_guided;

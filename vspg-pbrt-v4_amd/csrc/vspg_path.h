@@ -127,6 +127,7 @@ struct LsCtx {  // LightSampleContext
     V3 n;
 };
 #include "vspg_spherelight.h"  // DiffuseAreaLight on a sphere: sphere_sample_li / sphere_pdf_li / sphere_light_L
+#include "vspg_camera.h"  // thin-lens, orthographic and spherical cameras: camera_generate_ray (start_path_common<true>)
 // light.SampleLi(ctx, uLight, lambda, allowIncompletePDF = true) for light `lightIndex` of the scene's light list.  `ctxp` is ctx.p();
 // `lctx` is the whole context (error bounds and normal), which sphere lights alone read: only FULL callers fill it.
 template <bool FULL = true>
@@ -1395,31 +1396,34 @@ VDEV bool li_vertex_guided_impl(const DScene &S, const Medium &medium, PathState
 }
 
 // EvaluatePixelSample up to the camera ray (src/pbrt/cpu/integrators.cpp:272-304)
-VDEV void start_path_common(const DScene &S, int px, int py, Sampler &sampler, PathState &st, int *ch, IsgSample &isg);
-VDEV void start_path(const DScene &S, const float *vsp_buf, int vsp_ready, int px, int py, int sampleIndex, Sampler &sampler,
+// CAM: the instantiation serves every camera model (vspg_camera.h) -- the full-scene kernels, which take one wave-uniform branch on
+// the scene's camera record; false: the rectangle-scene instantiations (Medium::kSimpleScene, every k_render_wave_wg3), which the kernel
+// choice keeps to the pinhole (ChoiceFacts::camera_general) and which compile to the code they had before the record existed.
+template <bool CAM> VDEV void start_path_common(const DScene &S, int px, int py, Sampler &sampler, PathState &st, int *ch, IsgSample &isg);
+template <bool CAM> VDEV void start_path(const DScene &S, const float *vsp_buf, int vsp_ready, int px, int py, int sampleIndex, Sampler &sampler,
                      PathState &st, int *ch, IsgSample &isg) {
     st.vsp0 = (vsp_ready & VSP_READY) ? vsp_buf[(size_t)py * S.xres + px] : 0.5f;
     sampler.start_pixel_sample(px, py, S.seed, sampleIndex);
-    start_path_common(S, px, py, sampler, st, ch, isg);
+    start_path_common<CAM>(S, px, py, sampler, st, ch, isg);
 }
-VDEV void start_path(const DScene &S, const float *vsp_buf, int vsp_ready, int px, int py, PcgJump jump, Sampler &sampler,
+template <bool CAM> VDEV void start_path(const DScene &S, const float *vsp_buf, int vsp_ready, int px, int py, PcgJump jump, Sampler &sampler,
                      PathState &st, int *ch, IsgSample &isg) {
     st.vsp0 = (vsp_ready & VSP_READY) ? vsp_buf[(size_t)py * S.xres + px] : 0.5f;
     sampler.start_pixel_sample(px, py, S.seed, jump);
-    start_path_common(S, px, py, sampler, st, ch, isg);
+    start_path_common<CAM>(S, px, py, sampler, st, ch, isg);
 }
 // ... with the pixel's VSP in hand (0.5 until the buffer counts): k_render_wave_wg3 loads it beside the pixel's other reads
-VDEV void start_path(const DScene &S, float vsp0, int px, int py, int sampleIndex, Sampler &sampler, PathState &st, int *ch, IsgSample &isg) {
+template <bool CAM> VDEV void start_path(const DScene &S, float vsp0, int px, int py, int sampleIndex, Sampler &sampler, PathState &st, int *ch, IsgSample &isg) {
     st.vsp0 = vsp0;
     sampler.start_pixel_sample(px, py, S.seed, sampleIndex);
-    start_path_common(S, px, py, sampler, st, ch, isg);
+    start_path_common<CAM>(S, px, py, sampler, st, ch, isg);
 }
-VDEV void start_path(const DScene &S, float vsp0, int px, int py, PcgJump jump, Sampler &sampler, PathState &st, int *ch, IsgSample &isg) {
+template <bool CAM> VDEV void start_path(const DScene &S, float vsp0, int px, int py, PcgJump jump, Sampler &sampler, PathState &st, int *ch, IsgSample &isg) {
     st.vsp0 = vsp0;
     sampler.start_pixel_sample(px, py, S.seed, jump);
-    start_path_common(S, px, py, sampler, st, ch, isg);
+    start_path_common<CAM>(S, px, py, sampler, st, ch, isg);
 }
-VDEV void start_path_common(const DScene &S, int px, int py, Sampler &sampler, PathState &st, int *ch, IsgSample &isg) {
+template <bool CAM> VDEV void start_path_common(const DScene &S, int px, int py, Sampler &sampler, PathState &st, int *ch, IsgSample &isg) {
     float lu = sampler.get1d();
     st.lu = lu;
     int c = (int)__builtin_floorf(lu * 3);  // SampledWavelengths::SampleVisible (spectrum.h:380-384)
@@ -1430,13 +1434,16 @@ VDEV void start_path_common(const DScene &S, int px, int py, Sampler &sampler, P
     float fpy = (1 - f1) * -0.5f + f1 * 0.5f;
     float pfx = ((float)px + fpx) + 0.5f, pfy = ((float)py + fpy) + 0.5f;
     (void)sampler.get1d();  // time
-    (void)sampler.get1d();  // pLens
-    (void)sampler.get1d();
-    V3 pc_ = mk(S.cam.sx * pfx + S.cam.ox, S.cam.sy * pfy + S.cam.oy, 1.f);
-    V3 dir = normalize(pc_);
-    Frame f{ld3(S.cam.right), ld3(S.cam.up), ld3(S.cam.fwd)};
-    st.ro = ld3(S.cam.origin);
-    st.rd = f.from_local(dir);
+    const float uLens0 = sampler.get1d(), uLens1 = sampler.get1d();  // pLens: drawn for every camera, read by a lens alone
+    if (CAM && camera_is_general(S)) {  // (wave-uniform)
+        camera_generate_ray(S, pfx, pfy, uLens0, uLens1, &st.ro, &st.rd);
+    } else {
+        V3 pc_ = mk(S.cam.sx * pfx + S.cam.ox, S.cam.sy * pfy + S.cam.oy, 1.f);
+        V3 dir = normalize(pc_);
+        Frame f{ld3(S.cam.right), ld3(S.cam.up), ld3(S.cam.fwd)};
+        st.ro = ld3(S.cam.origin);
+        st.rd = f.from_local(dir);
+    }
     st.L = sp(0.f);
     st.beta = sp(1.f);
     st.r_u = sp(1.f);

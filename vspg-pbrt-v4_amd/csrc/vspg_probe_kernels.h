@@ -278,6 +278,35 @@ __global__ __launch_bounds__(kBlock) void k_texture_eval(const DScene *__restric
         o[7] = b.has_lobes ? 1.f : 0.f;
     }
 }
+// vspg_camera_ray_batch (include/vspg.h): the render-space camera ray of sample sample_index[i] of pixel pixel_xy[2i..] -- the raster
+// point as start_path_common forms it (BoxFilter radius .5) and camera_generate_ray (vspg_camera.h) itself.  u: the filter's and the
+// lens's variates per element, or null: the renderer's sampler in start_path_common's order (wavelength, filter 2, time, lens 2).
+__global__ __launch_bounds__(kBlock) void k_camera_ray(const DScene *__restrict__ Sp, int n, const int32_t *__restrict__ pixel_xy,
+                                                       const int32_t *__restrict__ sample_index, const float *__restrict__ u,
+                                                       float *__restrict__ out_o, float *__restrict__ out_d) {
+    const int i = blockIdx.x * kBlock + threadIdx.x;
+    if (i >= n) return;
+    const DScene &S = *Sp;
+    const int px = pixel_xy[2 * (size_t)i], py = pixel_xy[2 * (size_t)i + 1];
+    float f0, f1, l0, l1;
+    if (u) {
+        f0 = u[4 * (size_t)i], f1 = u[4 * (size_t)i + 1], l0 = u[4 * (size_t)i + 2], l1 = u[4 * (size_t)i + 3];
+    } else {
+        Sampler sampler;
+        sampler.start_pixel_sample(px, py, S.seed, sample_index[i]);
+        (void)sampler.get1d();  // wavelength
+        f0 = sampler.get1d(), f1 = sampler.get1d();
+        (void)sampler.get1d();  // time
+        l0 = sampler.get1d(), l1 = sampler.get1d();
+    }
+    const float fpx = (1 - f0) * -0.5f + f0 * 0.5f, fpy = (1 - f1) * -0.5f + f1 * 0.5f;
+    const float pfx = ((float)px + fpx) + 0.5f, pfy = ((float)py + fpy) + 0.5f;
+    V3 ro, rd;
+    camera_generate_ray(S, pfx, pfy, l0, l1, &ro, &rd);
+    float *o = out_o + 3 * (size_t)i, *d = out_d + 3 * (size_t)i;
+    o[0] = ro.x; o[1] = ro.y; o[2] = ro.z;
+    d[0] = rd.x; d[1] = rd.y; d[2] = rd.z;
+}
 // vspg_light_pdf_batch (include/vspg.h): for one light with a shape (a rectangle or a sphere of the light list) what li_surface_pre
 // computes when a ray from the context along wi is weighed against it -- light_sampler_pmf, light_pdf_li / sphere_pdf_li, and the
 // shape's own intersection from ctx.SpawnRay(wi) with light_L / sphere_light_L at the hit.  ctx_perr == nullptr: exact points.

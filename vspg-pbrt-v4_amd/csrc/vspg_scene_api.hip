@@ -15,6 +15,33 @@ int vspg_host::fail(int code, const std::string &msg) {
     return code;
 }
 
+// The refusals of vspg_renderer_set_camera, in the header's order (no renderer, no HIP call: tests/camera_build_check.cpp links it)
+int vspg_host::camera_refusal(const VspgCamera *cam, const VspgCameraModel *model) {
+    if (!cam) return fail(VSPG_EINVAL, "null camera");
+    const int m = model ? model->model : VSPG_CAMERA_PERSPECTIVE;
+    if (m < VSPG_CAMERA_PERSPECTIVE || m > VSPG_CAMERA_SPHERICAL_EQUIRECT) return fail(VSPG_EINVAL, "unknown camera model " + std::to_string(m));
+    for (int k = 0; k < 3; ++k)
+        if (!std::isfinite(cam->origin[k]) || !std::isfinite(cam->right[k]) || !std::isfinite(cam->up[k]) || !std::isfinite(cam->fwd[k]))
+            return fail(VSPG_EINVAL, "camera origin or frame is not finite");
+    if (!std::isfinite(cam->sx) || !std::isfinite(cam->ox) || !std::isfinite(cam->sy) || !std::isfinite(cam->oy))
+        return fail(VSPG_EINVAL, "camera affine term is not finite");
+    if (model && m <= VSPG_CAMERA_ORTHOGRAPHIC) {  // (a spherical camera ignores both lens fields)
+        if (!(model->lens_radius >= 0) || !std::isfinite(model->lens_radius)) return fail(VSPG_EINVAL, "lens_radius is negative or not finite");
+        if (model->lens_radius > 0 && (!(model->focal_distance > 0) || !std::isfinite(model->focal_distance)))
+            return fail(VSPG_EINVAL, "focal_distance must be finite and positive under a lens");
+    }
+    return 0;
+}
+// What the scene record holds for an accepted model: a spherical camera carries no lens, a lens of radius 0 no focal distance worth reading
+VspgCameraModel vspg_host::camera_model_record(const VspgCameraModel *model) {
+    VspgCameraModel o = {VSPG_CAMERA_PERSPECTIVE, 0.f, 0.f};
+    if (!model) return o;
+    o.model = model->model;
+    if (o.model <= VSPG_CAMERA_ORTHOGRAPHIC && model->lens_radius > 0) { o.lens_radius = model->lens_radius; o.focal_distance = model->focal_distance; }
+    return o;
+}
+bool vspg_host::camera_model_general(const VspgCameraModel &rec) { return rec.model != VSPG_CAMERA_PERSPECTIVE || rec.lens_radius > 0; }
+
 extern "C" {
 
 int vspg_abi_version(void) { return VSPG_ABI_VERSION; }
@@ -42,16 +69,14 @@ void vspg_integrator_params_default(VspgIntegratorParams *p) {
     p->volumerrguiding = 1;
 }
 
-int vspg_camera_look_at(VspgCamera *cam, const float eye[3], const float look[3], const float up[3], float fov_degrees,
-                        int xres, int yres) {
-    if (!cam || xres <= 0 || yres <= 0) return fail(VSPG_EINVAL, "bad camera arguments");
+// LookAt's frame (pbrt LookAt: right = Normalize(Cross(Normalize(up), dir)); newUp = Cross(dir, right)), in double, rounded once
+static int look_at_frame(VspgCamera *cam, const float eye[3], const float look[3], const float up[3]) {
     double e[3], f[3], u[3];
     for (int i = 0; i < 3; ++i) { e[i] = eye[i]; f[i] = (double)look[i] - eye[i]; u[i] = up[i]; }
     double fl = std::sqrt(f[0] * f[0] + f[1] * f[1] + f[2] * f[2]);
     double ul = std::sqrt(u[0] * u[0] + u[1] * u[1] + u[2] * u[2]);
     if (fl == 0 || ul == 0) return fail(VSPG_EINVAL, "degenerate LookAt");
     for (int i = 0; i < 3; ++i) { f[i] /= fl; u[i] /= ul; }
-    // pbrt LookAt: right = Normalize(Cross(Normalize(up), dir)); newUp = Cross(dir, right)
     double r[3] = {u[1] * f[2] - u[2] * f[1], u[2] * f[0] - u[0] * f[2], u[0] * f[1] - u[1] * f[0]};
     double rl = std::sqrt(r[0] * r[0] + r[1] * r[1] + r[2] * r[2]);
     if (rl == 0) return fail(VSPG_EINVAL, "up vector parallel to view direction");
@@ -63,15 +88,42 @@ int vspg_camera_look_at(VspgCamera *cam, const float eye[3], const float look[3]
         cam->up[i] = (float)nu[i];
         cam->fwd[i] = (float)f[i];
     }
-    // screen window spans [-1,1] on the shorter axis (cameras.cpp:474-489); raster y points down
-    double aspect = (double)xres / (double)yres;
-    double wx = aspect > 1 ? aspect : 1.0, wy = aspect > 1 ? 1.0 : 1.0 / aspect;
-    double th = std::tan(fov_degrees * 3.14159265358979323846 / 360.0);
-    cam->sx = (float)(2.0 * wx * th / xres);
-    cam->ox = (float)(-wx * th);
-    cam->sy = (float)(-2.0 * wy * th / yres);
-    cam->oy = (float)(wy * th);
     return 0;
+}
+
+int vspg_camera_look_at_window(VspgCamera *cam, int model, const float eye[3], const float look[3], const float up[3], float fov_degrees,
+                               const float screen_window[4], float frame_aspect, int xres, int yres) {
+    if (!cam || !eye || !look || !up || xres <= 0 || yres <= 0) return fail(VSPG_EINVAL, "bad camera arguments");
+    if (model < VSPG_CAMERA_PERSPECTIVE || model > VSPG_CAMERA_SPHERICAL_EQUIRECT) return fail(VSPG_EINVAL, "unknown camera model");
+    if (!(frame_aspect >= 0) || !std::isfinite(frame_aspect)) return fail(VSPG_EINVAL, "frame_aspect is negative or not finite");
+    if (screen_window)
+        for (int k = 0; k < 4; ++k)
+            if (!std::isfinite(screen_window[k])) return fail(VSPG_EINVAL, "screen_window is not finite");
+    VspgCamera c;
+    memset(&c, 0, sizeof c);
+    if (const int rc = look_at_frame(&c, eye, look, up)) return rc;
+    if (model == VSPG_CAMERA_PERSPECTIVE || model == VSPG_CAMERA_ORTHOGRAPHIC) {
+        // the screen window spans [-1,1] on the shorter axis (cameras.cpp:375-389, :474-489), "screenwindow" replaces it
+        // (:390-404); raster y points down
+        const double aspect = frame_aspect != 0 ? (double)frame_aspect : (double)xres / (double)yres;
+        const double wx = aspect > 1 ? aspect : 1.0, wy = aspect > 1 ? 1.0 : 1.0 / aspect;
+        double x0 = -wx, x1 = wx, y0 = -wy, y1 = wy;
+        if (screen_window) { x0 = screen_window[0]; x1 = screen_window[1]; y0 = screen_window[2]; y1 = screen_window[3]; }
+        // perspective: the window lies on the plane z = 1 of a 90-degree frustum scaled by tan(fov / 2) (Perspective's Scale(1 / tan),
+        // transform.cpp); orthographic: camera-space units, fov is not read
+        const double th = model == VSPG_CAMERA_PERSPECTIVE ? std::tan(fov_degrees * 3.14159265358979323846 / 360.0) : 1.0;
+        c.sx = (float)((x1 - x0) * th / xres);
+        c.ox = (float)(x0 * th);
+        c.sy = (float)(-((y1 - y0) * th / yres));
+        c.oy = (float)(y1 * th);
+    }
+    *cam = c;
+    return 0;
+}
+
+int vspg_camera_look_at(VspgCamera *cam, const float eye[3], const float look[3], const float up[3], float fov_degrees,
+                        int xres, int yres) {
+    return vspg_camera_look_at_window(cam, VSPG_CAMERA_PERSPECTIVE, eye, look, up, fov_degrees, nullptr, 0.f, xres, yres);
 }
 
 int vspg_transform_inverse(const float m[16], float inv[16]) {

@@ -38,6 +38,11 @@ namespace lsb {
 void build(const VspgScene &sc, const VspgIntegratorParams &prm, DScene *D);  // the light sampler alone (a light's power changed)
 }
 PcgJump pcg_jump(unsigned long long delta);
+// ---- camera models (vspg_camera.h; vspg_scene_api.hip): the refusals of vspg_renderer_set_camera in the header's order (0, or
+// VSPG_EINVAL with the message set), the record an accepted model leaves in DScene, and ChoiceFacts::camera_general of that record
+int camera_refusal(const VspgCamera *cam, const VspgCameraModel *model);
+VspgCameraModel camera_model_record(const VspgCameraModel *model);
+bool camera_model_general(const VspgCameraModel &rec);
 bool wants_guiding(const VspgIntegratorParams &p);
 bool wants_training(const VspgIntegratorParams &p);
 

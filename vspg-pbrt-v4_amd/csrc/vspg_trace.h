@@ -34,7 +34,7 @@ __global__ __launch_bounds__(kTraceBlock) void k_trace_paths(const DScene *__res
     int ch;
     float *glds = nullptr;
     if constexpr (GUIDED) glds = guide_lds();
-    start_path(S, vsp_buf, vsp_ready, px, py, sample_index[i], sampler, st, &ch, isg);
+    start_path<true>(S, vsp_buf, vsp_ready, px, py, sample_index[i], sampler, st, &ch, isg);
     if constexpr (GUIDED) load_contribution_estimate(S, px, py, st);
     while (li_segment<Medium, GUIDED>(S, medium, vsp_buf, vsp_ready, px, py, st, ch, sampler, isg, pc, glds, kTraceBlock)) {
     }

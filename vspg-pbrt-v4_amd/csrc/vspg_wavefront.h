@@ -917,7 +917,7 @@ __global__ __launch_bounds__(kWfBlock, 3) void k_wf_start(WfArgs a) {
                 Sampler sampler;
                 IsgSample isg;
                 int ch = 0;
-                start_path(S, a.vsp_buf, a.vsp_ready, px, py, a.jump, sampler, st, &ch, isg);
+                start_path<true>(S, a.vsp_buf, a.vsp_ready, px, py, a.jump, sampler, st, &ch, isg);
                 alive = true;
                 if constexpr (TRAIN) {
                     wf_rec_load(a, slot, pc.rec);
@@ -1610,7 +1610,7 @@ __global__ __launch_bounds__(kWfBlock, 2) void k_wf_segment_vertex(WfArgs a, int
             bool run = false;
             if (first) {
                 if (win_has(a.win, px, py)) {
-                    start_path(S, a.vsp_buf, a.vsp_ready, px, py, a.jump, sampler, st, &ch, isg);
+                    start_path<true>(S, a.vsp_buf, a.vsp_ready, px, py, a.jump, sampler, st, &ch, isg);
                     if constexpr (TRAIN) {
                         wf_rec_load(a, slot, pc.rec);
                         pc.rec.reset();

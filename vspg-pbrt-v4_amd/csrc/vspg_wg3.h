@@ -690,9 +690,9 @@ __device__ __forceinline__ void wg3_render(
                     if (valid) {
                         if (!fresh && (w3_at_use(vsp_ready) & VSP_READY)) vsp0 = vsp_buf[(size_t)py * W + px];
                         if (w3_at_use(single_sample))
-                            start_path(S, vsp0, px, py, jump, sampler, st, &ch, isg);
+                            start_path<false>(S, vsp0, px, py, jump, sampler, st, &ch, isg);
                         else
-                            start_path(S, vsp0, px, py, smp, sampler, st, &ch, isg);
+                            start_path<false>(S, vsp0, px, py, smp, sampler, st, &ch, isg);
                         P.i(LY::PIXEL, slot) = pxy;
                         P.i(LY::SAMPLE, slot) = smp;
                         if constexpr (TRAIN) { (void)rec_bind(pxy); pc.rec.reset(); }

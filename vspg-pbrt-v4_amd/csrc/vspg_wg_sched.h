@@ -298,9 +298,9 @@ __global__ __launch_bounds__(kWgBlock, kWgWavesPerSimd) void k_render_wave_wg(
                     valid = win_has(win, px, py) && smp < wave_end;  // tile padding: the slot stays free
                     if (valid) {
                         if (single_sample)
-                            start_path(S, vsp_buf, vsp_ready, px, py, jump, sampler, st, &ch, isg);
+                            start_path<!Medium::kSimpleScene>(S, vsp_buf, vsp_ready, px, py, jump, sampler, st, &ch, isg);
                         else
-                            start_path(S, vsp_buf, vsp_ready, px, py, smp, sampler, st, &ch, isg);
+                            start_path<!Medium::kSimpleScene>(S, vsp_buf, vsp_ready, px, py, smp, sampler, st, &ch, isg);
                         P.i(LY::PIXEL, slot) = pxy;
                         P.i(LY::SAMPLE, slot) = smp;
                         alive = li_segment_a<Medium, GUIDED, SEG_PRIMARY>(S, medium, vsp_buf, vsp_ready, px, py, st, ch, sampler,
@@ -609,9 +609,9 @@ __global__ __launch_bounds__(kWgBlock, kWgWavesPerSimd) void k_render_wave_wg2(
                     valid = valid && win_has(win, px, py) && smp < wave_end;  // tile padding: the slot stays free
                     if (valid) {
                         if (single_sample)
-                            start_path(S, vsp_buf, vsp_ready, px, py, jump, sampler, st, &ch, isg);
+                            start_path<!Medium::kSimpleScene>(S, vsp_buf, vsp_ready, px, py, jump, sampler, st, &ch, isg);
                         else
-                            start_path(S, vsp_buf, vsp_ready, px, py, smp, sampler, st, &ch, isg);
+                            start_path<!Medium::kSimpleScene>(S, vsp_buf, vsp_ready, px, py, smp, sampler, st, &ch, isg);
                         P.i(LY::PIXEL, slot) = pxy;
                         P.i(LY::SAMPLE, slot) = smp;
                         if constexpr (TRAIN) { (void)rec_bind(pxy); pc.rec.reset(); }

@@ -742,6 +742,9 @@ void GuidedVolPathVSPGIntegrator::SetLightImage(int slot, const std::vector<floa
     if (xres < 1 || yres < 1 || channels < 1 || pixels.size() != (size_t)xres * yres * channels) throw Error("the light image does not hold xres * yres * channels values");
     if (vspg_renderer_set_light_image(renderer, slot, pixels.data(), xres, yres, channels, nullptr) != 0) throw Error(vspg_last_error());
 }
+void GuidedVolPathVSPGIntegrator::SetCamera(const VspgCamera &camera, const VspgCameraModel &model) {
+    if (vspg_renderer_set_camera(renderer, &camera, &model, nullptr) != 0) throw Error(vspg_last_error());
+}
 void GuidedVolPathVSPGIntegrator::SetMediumDensity(const std::vector<float> &values) {
     if (vspg_renderer_update_grid(renderer, VSPG_GRID_DENSITY, values.data(), values.size(), VSPG_MEM_HOST, nullptr) != 0) throw Error(vspg_last_error());
 }

@@ -183,6 +183,8 @@ class Integrator {
     // The image of the projection / goniometric light in point-light slot `slot`: xres * yres * channels floats, top row first, 3 channels
     // (R, G, B) or 1 (Y) (vspg_renderer_set_light_image).  Throws on refusal.
     virtual void SetLightImage(int slot, const std::vector<float> &pixels, int xres, int yres, int channels) = 0;
+    // The camera of the live renderer: a thin lens, an orthographic or a spherical model (vspg_renderer_set_camera).  Throws on refusal.
+    virtual void SetCamera(const VspgCamera &camera, const VspgCameraModel &model) = 0;
     // Integrator::Create: "guidedvolpathvspg"; "guidedvolpath" is accepted as an alias ONLY when
     // the dictionary carries "vspguiding" (the option BASELINE.json names), see SURVEY.md 0.1
     static std::unique_ptr<Integrator> Create(const std::string &name, const ParameterDictionary &parameters,
@@ -208,6 +210,7 @@ class GuidedVolPathVSPGIntegrator : public Integrator {
     void SetPixelBounds(int x0, int y0, int x1, int y1) override;
     void SetEnvironmentImage(int light, const std::vector<float> &rgb, int res, const float *renderFromLight) override;
     void SetLightImage(int slot, const std::vector<float> &pixels, int xres, int yres, int channels) override;
+    void SetCamera(const VspgCamera &camera, const VspgCameraModel &model) override;
     VspgCounters Counters();
     VspgTrainStats TrainingStats();      // guideTraining / guiding_field->GetIteration()
     GuidingCache GetGuidingCache();      // the field as it stands (trained in-loop or loaded)

@@ -71,6 +71,11 @@ int main(int argc, char **argv) {
         if (sd->scene.medium.temperature) std::printf("; temperature grid (blackbody emission under \"vspsamplingmethod\" \"nds\")");
         std::printf("\n");
         std::printf("pixel bounds: [ (%d, %d) - (%d, %d) ]\n", sd->boundsX0, sd->boundsY0, sd->boundsX1, sd->boundsY1);
+        {   // the camera: the model (VSPG_CAMERA_*), its lens and the raster map (%.9g round-trips a float)
+            const VspgCamera &c = sd->scene.camera;
+            std::printf("camera: model %d lens_radius %.9g focal_distance %.9g raster (%.9g, %.9g, %.9g, %.9g)\n", sd->cameraModel.model, sd->cameraModel.lens_radius,
+                        sd->cameraModel.focal_distance, c.sx, c.ox, c.sy, c.oy);
+        }
         std::vector<float> mseImage;
         if (!mseImagePath.empty()) {
             mseImage = vspg::LoadMseReferenceImage(mseImagePath, sd->xres, sd->yres, sd->boundsX0, sd->boundsY0, sd->boundsX1, sd->boundsY1);

@@ -49,6 +49,8 @@ int main(int argc, char **argv) {
         cfg.xres = sd->xres; cfg.yres = sd->yres; cfg.spp = sd->pixelSamples; cfg.seed = sd->seed;
         cfg.shard_index = rank; cfg.shard_count = world; cfg.device = local;
         if (vspg_renderer_create_textured(&sd->scene, &sd->textures, &prm, &cfg, &r) != 0) throw vspg::Error(vspg_last_error());
+        if (sd->cameraModel.model != VSPG_CAMERA_PERSPECTIVE || sd->cameraModel.lens_radius > 0)  // a lens, an orthographic or a spherical camera
+            if (vspg_renderer_set_camera(r, &sd->scene.camera, &sd->cameraModel, nullptr) != 0) throw vspg::Error(vspg_last_error());
         for (const auto &e : sd->envImages)  // LightSource "infinite" "string filename": every rank holds the whole image
             if (vspg_renderer_set_environment_image(r, e.light, e.rgb.data(), e.res, e.renderFromLight, nullptr) != 0) throw vspg::Error(vspg_last_error());
         for (const auto &l : sd->lightImages)  // LightSource "projection" / "goniometric" "string filename"

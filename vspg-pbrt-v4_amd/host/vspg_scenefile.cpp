@@ -141,6 +141,8 @@ class Parser {
     std::map<std::string, ParameterDictionary> materials;
     bool haveCamera = false, haveLookAt = false, world = false;
     float eye[3] = {0, 0, 0}, look[3] = {0, 0, -1}, up[3] = {0, 1, 0}, fov = 90.f;
+    float frameAspect = 0.f;             // Camera "frameaspectratio" (0 = the film's)
+    std::vector<float> screenWindow;     // Camera "screenwindow": empty or four values
     std::string cameraMedium;
     std::vector<VspgQuad> quads;
     std::vector<VspgSphere> spheres;
@@ -212,9 +214,31 @@ class Parser {
         } else if (d == "Camera") {
             const std::string type = str();
             ParameterDictionary p = params_with_bare_bools();
-            if (type != "perspective") fail("Camera \"" + type + "\": only \"perspective\" is inside this build's scope");
-            fov = p.GetOneFloat("fov", 90.f);
-            if (p.GetOneFloat("lensradius", 0.f) != 0.f) fail("thin-lens cameras are outside this build's scope");
+            // PerspectiveCamera / OrthographicCamera / SphericalCamera::Create (cameras.cpp:366-407, :459-509, :638-692)
+            if (type == "realistic") fail("Camera \"realistic\" (RealisticCamera) is outside this build's scope");
+            if (type != "perspective" && type != "orthographic" && type != "spherical")
+                fail("Camera \"" + type + "\": only \"perspective\", \"orthographic\" and \"spherical\" are inside this build's scope");
+            if (type == "perspective") fov = p.GetOneFloat("fov", 90.f);
+            const float lensradius = p.GetOneFloat("lensradius", 0.f);
+            const float focaldistance = p.GetOneFloat("focaldistance", type == "spherical" ? 1e30f : 1e6f);
+            frameAspect = p.GetOneFloat("frameaspectratio", 0.f);   // (0: the film's, known at the end of the file)
+            screenWindow = p.GetFloatArray("screenwindow");
+            if (!screenWindow.empty() && screenWindow.size() != 4) fail("\"screenwindow\" should have four values");
+            VspgCameraModel &cm = sd->cameraModel;
+            cm.model = VSPG_CAMERA_PERSPECTIVE, cm.lens_radius = 0.f, cm.focal_distance = 0.f;
+            if (type == "spherical") {  // (the lens parameters and the window are read and not used, as the reference does)
+                const std::string mapping = p.GetOneString("mapping", "equalarea");
+                if (mapping == "equalarea") cm.model = VSPG_CAMERA_SPHERICAL_EQUALAREA;
+                else if (mapping == "equirectangular") cm.model = VSPG_CAMERA_SPHERICAL_EQUIRECT;
+                else fail("Camera \"spherical\": unknown mapping \"" + mapping + "\" (\"equalarea\" or \"equirectangular\")");
+            } else {
+                cm.model = type == "orthographic" ? VSPG_CAMERA_ORTHOGRAPHIC : VSPG_CAMERA_PERSPECTIVE;
+                if (!(lensradius >= 0) || !std::isfinite(lensradius)) fail("Camera: \"lensradius\" must be finite and not negative");
+                if (lensradius > 0) {
+                    if (!(focaldistance > 0) || !std::isfinite(focaldistance)) fail("Camera: \"focaldistance\" must be finite and positive under a lens");
+                    cm.lens_radius = lensradius, cm.focal_distance = focaldistance;
+                }
+            }
             p.ReportUnused();
             haveCamera = true;
             cameraMedium = gs.outsideMedium;  // the camera takes the current OUTSIDE medium (scene.cpp:153-155, 664-665)
@@ -714,7 +738,9 @@ class Parser {
         s.n_quads = (int)quads.size();
         for (int i = 0; i < s.n_quads; ++i) s.quads[i] = quads[i];
         if (!haveLookAt) { eye[0] = eye[1] = eye[2] = 0; look[0] = 0; look[1] = 0; look[2] = 1; up[0] = 0; up[1] = 1; up[2] = 0; }
-        if (vspg_camera_look_at(&s.camera, eye, look, up, fov, sd->xres, sd->yres) != 0) throw Error(std::string("Camera: ") + vspg_last_error());
+        if (vspg_camera_look_at_window(&s.camera, sd->cameraModel.model, eye, look, up, fov, screenWindow.empty() ? nullptr : screenWindow.data(), frameAspect,
+                                       sd->xres, sd->yres) != 0)
+            throw Error(std::string("Camera: ") + vspg_last_error());
         s.n_spheres = (int)spheres.size();
         for (int i = 0; i < s.n_spheres; ++i) s.spheres[i] = spheres[i];
         // The scene's medium: the library holds ONE (include/vspg.h).  Every name a camera or a shape refers to must be that one
@@ -800,6 +826,8 @@ std::unique_ptr<Integrator> CreateIntegrator(const SceneDescription &sd, int dev
     auto integrator = Integrator::Create(sd.integratorName, sd.integratorParams, sd.scene, sd.xres, sd.yres, sd.pixelSamples, sd.seed, device,
                                          sd.textures.n_textures > 0 ? &sd.textures : nullptr);
     integrator->SetPixelBounds(b[0], b[1], b[2], b[3]);
+    // a thin lens, an orthographic or a spherical camera is set on the live renderer (a pinhole perspective is what it was created with)
+    if (sd.cameraModel.model != VSPG_CAMERA_PERSPECTIVE || sd.cameraModel.lens_radius > 0) integrator->SetCamera(sd.scene.camera, sd.cameraModel);
     for (const SceneDescription::EnvImage &e : sd.envImages) integrator->SetEnvironmentImage(e.light, e.rgb, e.res, e.renderFromLight);
     for (const SceneDescription::LightImage &l : sd.lightImages) integrator->SetLightImage(l.slot, l.pixels, l.xres, l.yres, l.channels);
     return integrator;

@@ -7,7 +7,9 @@
 // (lights.cpp).  Everything is routed through the adapter's ParameterDictionary, so parameter names, defaults and the
 // unused-parameter error are the reference's.
 //
-// Directives: LookAt, Camera "perspective" (fov), Sampler (pixelsamples, seed), PixelFilter "box", Film "rgb"
+// Directives: LookAt, Camera "perspective" (fov, lensradius, focaldistance, screenwindow, frameaspectratio) / "orthographic" (the same
+// without fov) / "spherical" (mapping "equalarea" | "equirectangular"; its lens parameters and window are read and ignored, as in the
+// reference; "realistic" is refused by name), Sampler (pixelsamples, seed), PixelFilter "box", Film "rgb"
 // (xresolution, yresolution, filename, savefp16, cropwindow, pixelbounds), Integrator, Option (ignored but "disabletexturefiltering"), ColorSpace (ignored), WorldBegin, AttributeBegin/End,
 // Identity, Translate, Scale, Rotate, Transform, ConcatTransform, ReverseOrientation, Material "diffuse" (reflectance: rgb, float, or
 // "texture reflectance" "name") / "interface", Texture "name" "spectrum" "imagemap" (filename: .pfm / .exr with R, G, B or Y; filter, wrap,
@@ -42,6 +44,9 @@ namespace vspg {
 
 struct SceneDescription {
     VspgScene scene;                     // pointers inside refer to the vectors below: keep the description alive while creating
+    // Camera "perspective" (lensradius, focaldistance) / "orthographic" / "spherical" (mapping): the model beside scene.camera.  A host
+    // hands both to vspg_renderer_set_camera after create when this is not the pinhole perspective (CreateIntegrator does).
+    VspgCameraModel cameraModel = {VSPG_CAMERA_PERSPECTIVE, 0.f, 0.f};
     std::vector<float> density, leScale, temperature, triP, triKd;
     std::vector<int32_t> triFlags;       // VSPG_TRI_* per triangle (material, MediumInterface, orientation)
     RgbGridStorage rgb;                  // MakeNamedMedium "string type" "rgbgrid": the grids scene.rgb_* point at
